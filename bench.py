@@ -6,13 +6,28 @@ batch of 1024 synthetic 40x40 fields resident in HBM: HIP U-Net forward (train-m
 HIP MSE, HIP backward, RCCL gradient all-reduce (N>1, overlapped with backward), fused
 clip_grad_norm_(1.0) + AdamW(lr 2e-4, wd 1e-4).  Nothing is skipped in the timed region.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...      (one process per GPU, RCCL)
 
-Rank 0 prints ONE JSON line.  ``roofline`` prices the dominant kernel (the implicit-GEMM
-conv forward of the layer named by --roofline-layer) from HIP events recorded around its
-launch on the compute stream; ``cpu_baseline`` times the oracle (torch-CPU restatement of
-the same step) on the host cores for a bounded sample.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the
+headline record (metric, value, unit, ms_per_step, ...); nothing else is measured.
+
+``--dump-outputs DIR`` writes, after the timed steps, what the last timed step computed as
+``DIR/<name>.npy`` (float32 / float64, under 64 MB in all; an array too large for its share is a
+fixed, seeded sample of its elements).  The inputs are seeded, so two builds run with the same
+arguments can be compared file for file:
+    train    loss, grad_norm (the clip's total norm), output (the forward's prediction), params and
+             buffers (every parameter / BN buffer after the update, concatenated in named_parameters /
+             named_buffers order), grads_sample (the gradients, same order, sampled)
+    poisson  u_n<N> (the solutions of the last batch at each size, sampled), iters_n<N>
+    cascade  pred (the 640 x 640 prediction)
+
+``--full`` adds everything that takes runs or time of its own: ``roofline`` prices the dominant
+kernel (the implicit-GEMM conv forward of the layer named by --roofline-layer) from HIP events
+recorded around its launch on the compute stream, with the kernel's HBM traffic from rocprofv3
+PMC passes and the forward-alone timings; ``cpu_baseline`` times the oracle (torch-CPU
+restatement of the same step) on the host cores for a bounded sample.  --no-cpu-baseline and
+--no-live-traffic drop single parts of a --full run.
 """
 from __future__ import annotations
 
@@ -107,12 +122,56 @@ def forward_roofline(model, x, peak_tf):
     return out
 
 
+# --dump-outputs: the seed of the element sample taken from an array too large for its share of the 64 MB
+DUMP_SEED = 20240229
+
+
+def _dump_array(d, name, a, max_elems):
+    """DIR/<name>.npy, float32 or float64; a fixed seeded sample (sorted flat indices) of an array with
+    more than max_elems elements."""
+    import numpy as np
+    if torch.is_tensor(a):
+        a = a.detach().cpu().numpy()
+    a = np.asarray(a)
+    if a.dtype not in (np.float32, np.float64):
+        a = a.astype(np.float64)
+    if a.size > max_elems:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, int(max_elems), replace=False))
+        a = a.reshape(-1)[idx]
+    np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a))
+
+
+def dump_train_outputs(d, model, opt, loss, out):
+    """What a caller of the training step holds after the last timed step: the loss, the clip's total norm, the
+    prediction, the updated parameters and BN buffers, and the gradients.  Caps (elements): 2 M + 9 M + 4 M
+    float32 = 60 MB; the U-Net at batch 1024 has 1.64 M outputs and 7.83 M parameters, so only the gradients
+    are sampled."""
+    os.makedirs(d, exist_ok=True)
+    _dump_array(d, "loss", loss.detach().reshape(1).float(), 1)
+    if opt.last_total_norm is not None:
+        _dump_array(d, "grad_norm", opt.last_total_norm.detach().reshape(1).float(), 1)
+    _dump_array(d, "output", out.detach().float(), 2_000_000)
+    named = list(model.named_parameters())
+    _dump_array(d, "params", torch.cat([p.detach().reshape(-1).float() for _, p in named]), 9_000_000)
+    bufs = [b.detach().reshape(-1).float() for _, b in model.named_buffers()]
+    if bufs:
+        _dump_array(d, "buffers", torch.cat(bufs), 1_000_000)
+    _dump_array(d, "grads_sample", torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach()
+                                              .reshape(-1).float() for _, p in named]), 4_000_000)
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=1024, help="per-GPU batch (BASELINE config: 1024)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy "
+                         "(see the module docstring); rank 0 only")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the roofline record (per-kernel HIP "
+                         "events, rocprofv3 PMC traffic passes, the forward alone) and the CPU baseline")
     ap.add_argument("--roofline-layer", default="bridge.3")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
@@ -282,6 +341,8 @@ def run_poisson(args, world, rank, dev, pmc=None):
     sizes = [tuple(int(v) for v in s.split(":")) for s in args.poisson_sizes.split(",")]
     rng = np.random.default_rng(100 + rank)
     levels = {}
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
     for n, B in sizes:
         k = rng.uniform(0.5, 12.0, (B, 2))
         f = P.forcing_batched(k, n, device=dev)
@@ -304,6 +365,9 @@ def run_poisson(args, world, rank, dev, pmc=None):
             el = float(tt)
         iters = float(it.double().mean())
         t = el / reps
+        if args.dump_outputs and rank == 0:   # the last timed batch's solutions, 60 MB over the sizes
+            _dump_array(args.dump_outputs, f"u_n{n}", u, 7_000_000 // len(sizes))
+            _dump_array(args.dump_outputs, f"iters_n{n}", it, 100_000 // len(sizes))
         pts_it = B * n * n * iters
         lv = {"B": B, "solves_per_s": round(world * B / t, 2), "ms_per_batch": round(1e3 * t, 3),
               "mean_iters": round(iters, 1)}
@@ -352,7 +416,7 @@ def run_poisson(args, world, rank, dev, pmc=None):
                                               "grid barrier's polls and arrivals (device-scope atomics) dominate; "
                                               "the solve's own HBM data is f, theta, u and the edge rows",
                                       "exit_fault": pmc.get("exit_fault")}
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         cb = cpu_baseline_poisson(min(args.cpu_seconds, 10.0))
         rec["cpu_baseline"] = {"value": round(cb[80], 2), "unit": "solves/s", "cores": 1, "kind": "port",
                                "sample": "scipy spsolve(diag(theta) L, f) per problem (the reference's call), "
@@ -437,6 +501,9 @@ def run_cascade(args, world, rank, dev):
         el = float(tt)
     if rank != 0:
         return
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        _dump_array(args.dump_outputs, "pred", pred, 15_000_000)
     m = RC.cascade_metrics(pred.cpu().numpy(), data["u"][640])
     ref_err = None
     if args.cascade_fixture:
@@ -455,7 +522,7 @@ def run_cascade(args, world, rank, dev):
                       "gt_solve_s": round(gt_s, 3), "rmse_vs_gt640": m["rmse"], "mae_vs_gt640": m["mae"],
                       "tiles_per_s": round(tiles / (ms * 1e-3), 1),
                       "rel_err_vs_reference_output": ref_err}}
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         st = {k: v.detach().cpu() for k, v in model.state_dict().items()}
         rec["cpu_baseline"] = cpu_baseline_cascade(st, data, args.cpu_seconds)
     emit(rec)
@@ -574,14 +641,14 @@ def main():
         print(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={ws} (launch one rank per GPU)", file=sys.stderr)
         sys.exit(2)
     live_traffic = None
-    if (ws is None and args.workload == "train" and not args.no_live_traffic and args.traffic_json is None
-            and not args.ddp):
+    if (args.full and ws is None and args.workload == "train" and not args.no_live_traffic
+            and args.traffic_json is None and not args.ddp):
         live_traffic = measure_traffic_live(args.roofline_layer)   # before this process touches the GPU
     step_traffic = (None, "not measured (--no-live-traffic / N > 1)")
-    if ws is None and args.workload == "train" and not args.no_live_traffic and not args.ddp:
+    if args.full and ws is None and args.workload == "train" and not args.no_live_traffic and not args.ddp:
         step_traffic = measure_step_traffic(args.batch)
     pmc_poisson = None
-    if ws is None and args.workload == "poisson" and not args.no_live_traffic:
+    if args.full and ws is None and args.workload == "poisson" and not args.no_live_traffic:
         sz = args.poisson_sizes.split(",")
         head = [s for s in sz if int(s.split(":")[0]) <= 128]
         # the headline LDS CG and the largest grid-CG size: a counter run that makes a cooperative launch
@@ -658,28 +725,29 @@ def main():
         loss = mse_loss(out, tgt)
         loss.backward()
         opt.step()
-        return loss
+        return loss, out
 
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
 
-    # timed region: exactly K steps between barrier+sync pairs; roofline-layer conv
+    # timed region: exactly K steps between barrier+sync pairs; with --full the roofline-layer conv
     # launches are bracketed with HIP events on the compute stream (the stream they run on)
     timed = []
-    X.TIMED_LAYERS[args.roofline_layer] = timed
-    # every conv launch of the timed region is bracketed with HIP events on its stream and labelled with the
+    # and every conv launch of the timed region is bracketed with HIP events on its stream and labelled with the
     # kernel it ran (hipops.LAUNCH_TAP, srpde_last_kernel): the roofline prices the kernel with the largest
     # total time
     from superresolution_for_pdes_amd import hipops as H
     launches = []
-    H.LAUNCH_TAP = launches
+    if args.full:
+        X.TIMED_LAYERS[args.roofline_layer] = timed
+        H.LAUNCH_TAP = launches
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss = step()
+        loss, out = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -690,8 +758,34 @@ def main():
         tt = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt)
-    # after the timed region: the forward alone (every rank runs it; rank 0 reports)
+    if args.dump_outputs and rank == 0:   # before anything else runs the model: the last timed step's results
+        dump_train_outputs(args.dump_outputs, model, opt, loss, out)
     math = H.conv_math()
+    head = {
+        "metric": "20->40 SR training samples/sec at batch 1024 per GPU (fwd+MSE bwd+clip+AdamW)",
+        "value": round(world * B * args.steps / elapsed, 2),
+        "unit": "samples/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(1e3 * elapsed / args.steps, 3),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": {"h3": "f32 (h3: fp32 products from power-of-two-scaled 2-piece fp16 splits on fp16 MFMA, "
+                        "fp32 accumulate)"}.get(math, "f32"),
+        "data": "synthetic (x~N(0,1), theta channel=1, t~N(0,1)), resident in HBM",
+        "config": {"workload": "UNet 20->40 train step, fp32, batch 1024/GPU, 40x40",
+                   "global_batch": world * B, "per_gpu_batch": B, "hw": "40x40",
+                   "parallelism": f"dp{world}", "final_loss": round(float(loss.detach()), 6)},
+    }
+    if not args.full:   # a plain run: the headline record alone
+        if rank == 0:
+            emit(head)
+        if use_pg:
+            dist.destroy_process_group()
+        return
+    # --full, after the timed region: the forward alone (every rank runs it; rank 0 reports)
     # dense MFMA peak of the instruction the kernel runs, in fp32-product units: fp32 MFMA
     # 157.3 TF; bf16 / fp16 MFMA run at 16x that (2516.8 TF), divided by the partial
     # products per fp32 product: 3 for h3 (838.9 TF)
@@ -728,29 +822,13 @@ def main():
                 tsource = (os.path.relpath(tfile, ROOT) + " (rocprofv3 FETCH_SIZE x2 + WRITE_SIZE per launch, "
                            "tools/gpu/round_evidence.sh)" +
                            (f"; live measurement unavailable: {live_traffic[1]}" if live_traffic else ""))
-        samples = world * B * args.steps
         # whole-step fraction: algorithmic FLOP of every 3x3 conv pass the step runs (forward,
         # dgrad except enc1.conv1's, whose input needs no gradient, and wgrad) at batch B, over the
         # step time, against the same roof -- BN / attention / pooling / optimizer time included
         step_flop = sum(conv_flops(c, o, h) * B * (3 if n != "enc1.conv1" else 2) for n, c, o, h in CONV3)
         step_ach = step_flop / (elapsed / args.steps) / 1e12
         rec = {
-            "metric": "20->40 SR training samples/sec at batch 1024 per GPU (fwd+MSE bwd+clip+AdamW)",
-            "value": round(samples / elapsed, 2),
-            "unit": "samples/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(1e3 * elapsed / args.steps, 3),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": {"h3": "f32 (h3: fp32 products from power-of-two-scaled 2-piece fp16 splits on fp16 MFMA, "
-                            "fp32 accumulate)"}.get(math, "f32"),
-            "data": "synthetic (x~N(0,1), theta channel=1, t~N(0,1)), resident in HBM",
-            "config": {"workload": "UNet 20->40 train step, fp32, batch 1024/GPU, 40x40",
-                       "global_batch": world * B, "per_gpu_batch": B, "hw": "40x40",
-                       "parallelism": f"dp{world}", "final_loss": round(float(loss.detach()), 6)},
+            **head,
             "roofline": {"bound": "mfma",
                          "kernel": top_name,
                          "kernel_note": "the conv kernel with the largest total time in the timed region (HIP events "

@@ -35,8 +35,6 @@ def conv_math():
 
 @pytest.fixture(scope="session")
 def golden():
-    import numpy as np
+    from state import load_fixture   # (tests/golden: a fixture over 1 MiB is stored in several files)
 
-    d = os.path.join(ROOT, "tests", "golden")
-    return {k: np.load(os.path.join(d, f"{k}_fixture.npz")) for k in ("unet", "poisson", "datagen", "cascade",
-                                                                             "unet_b1024", "cascade640")}
+    return {k: load_fixture(k) for k in ("unet", "poisson", "datagen", "cascade", "unet_b1024", "cascade640")}

@@ -26,8 +26,10 @@ Fixtures:
                        memory; running stats are read before the recompute touches them.
   cascade640_fixture.npz  solve_multi_resolution(40,[80..640]) + ml_multi_level_upscale to
                        320 and 640, plus the bilinear / bicubic multi-level and direct baselines
-                       (resolution_comparison_enhanced.py:19-65, :355-408) and their metrics
-  init_fixture.npz     torch.manual_seed(42); UNet().apply(init_weights) as train_enhanced.main
+                       (resolution_comparison_enhanced.py:19-65, :355-408) and their metrics;
+                       its dense arrays are stored beside it as cascade640_fixture.<key>.<i>.npz
+                       (state.save_fixture / load_fixture) so that no file passes 1 MiB
+  init_fixture.npz    torch.manual_seed(42); UNet().apply(init_weights) as train_enhanced.main
                        does (:187-189, :303-304): per-parameter norms, sums and strided samples
   report_fixture.npz   compare_test_cases.generate_test_data + evaluate_dataset (:12-247) with
                        seeded np.random, constant and varying theta: the test sets and the
@@ -80,7 +82,7 @@ import data_generation as ref_dg  # noqa: E402
 import enhanced_data_generation as ref_edg  # noqa: E402
 import resolution_comparison as ref_rc  # noqa: E402
 
-from state import fixture_state_torch, fixture_inputs, sample_indices  # noqa: E402
+from state import fixture_state_torch, fixture_inputs, sample_indices, save_fixture  # noqa: E402
 from oracle.unet_ref import trainable_names  # noqa: E402
 
 
@@ -326,7 +328,10 @@ def cascade640_fixture():
     out["ml640_from20"] = ml[::3, ::5].astype(np.float32)
     out["ml640_from20_metrics"] = np.array([np.mean(np.abs(e)), np.sqrt(np.mean(e ** 2))])
     out["u20"] = d20["u"][20]
-    np.savez_compressed(os.path.join(HERE, "cascade640_fixture.npz"), **out)
+    # the dense ML predictions (ml640 in row blocks) and the 640^2 baselines go beside the main file, each file
+    # under 1 MiB
+    save_fixture("cascade640", out, parts={"ml160": 1, "ml320": 1, "ml640": 3, "blm640": 1, "cbm640": 1,
+                                           "bld640": 1, "cbd640": 1})
 
 
 def init_fixture():

@@ -23,6 +23,37 @@ GOLDEN_DIR = os.path.dirname(os.path.abspath(__file__))
 SEED = 20250227
 
 
+def save_fixture(name: str, arrays, parts=None):
+    """``NAME_fixture.npz``, with the arrays named in ``parts`` ({key: row blocks}) stored beside it as
+    ``NAME_fixture.<key>.<i>.npz`` (key ``<key>#<i>``, equal blocks of rows), so that no committed file passes
+    1 MiB."""
+    parts = parts or {}
+    np.savez_compressed(os.path.join(GOLDEN_DIR, f"{name}_fixture.npz"),
+                        **{k: v for k, v in arrays.items() if k not in parts})
+    for k, n in parts.items():
+        for i, blk in enumerate(np.array_split(np.asarray(arrays[k]), n, axis=0)):
+            np.savez_compressed(os.path.join(GOLDEN_DIR, f"{name}_fixture.{k}.{i}.npz"), **{f"{k}#{i}": blk})
+
+
+def load_fixture(name: str):
+    """The fixture ``save_fixture`` wrote: the NpzFile itself when it is one file, else a dict with the row
+    blocks of the split arrays joined again."""
+    import glob
+    z = np.load(os.path.join(GOLDEN_DIR, f"{name}_fixture.npz"))
+    extra = glob.glob(os.path.join(GOLDEN_DIR, f"{name}_fixture.*.npz"))
+    if not extra:
+        return z
+    out, blocks = {k: z[k] for k in z.files}, {}
+    for f in extra:
+        p = np.load(f)
+        for k in p.files:
+            key, i = k.rsplit("#", 1)
+            blocks.setdefault(key, {})[int(i)] = p[k]
+    for key, b in blocks.items():
+        out[key] = np.concatenate([b[i] for i in range(len(b))], axis=0)
+    return out
+
+
 def fixture_state_np(seed: int = SEED):
     """name -> float32 ndarray (int64 for num_batches_tracked), reference key order."""
     rng = np.random.default_rng(seed)

@@ -57,7 +57,7 @@ def test_bench_self_launches_ranks():
     env["SRPDE_BENCH_BACKEND"] = "gloo"
     env.pop("WORLD_SIZE", None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--batch", "64", "--no-cpu-baseline"]
+           "--batch", "64", "--full", "--no-cpu-baseline"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

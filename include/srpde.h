@@ -56,8 +56,10 @@ typedef struct ihipStream_t* hipStream_t;
  *      srpde_conv_h3_stats_rows_for's new flags argument, the grid-CG abort hook a negative rtol;
  *      srpde_conv_wgrad_h3g_supported, srpde_att_pool_bn_bwd(_blocks); srpde_att_bwd takes dx == NULL
  *  11  srpde_upsample_bilinear_bwd_gated_bn, srpde_upsample_bwd_bn_supported, srpde_gating_bn_reduce(_blocks),
- *      srpde_att_bwd_params_lowres, srpde_conv_wgrad_bnb */
-#define SRPDE_ABI_VERSION 11
+ *      srpde_att_bwd_params_lowres, srpde_conv_wgrad_bnb
+ *  12  the batched cascade: srpde_cascade_level_stats(_workspace_size), srpde_cascade_level_assemble,
+ *      srpde_cascade_stitch_denorm, srpde_field_metrics(_workspace_size) */
+#define SRPDE_ABI_VERSION 12
 
 /* Kernel-family bits (per call; bit 0 of the same argument is the accumulate flag): the forward / dgrad
  * families compute the same outputs, statistics and stored splits bit for bit, so these only route a call to
@@ -350,6 +352,38 @@ int srpde_maxpool2x2_bwd(const float* x, int ldx, const float* dout, int lddo, f
 int srpde_pde_dataset_assemble(const float* u_coarse, const float* u_fine, const float* theta_fine,
                                const float* f_fine, const float* stats, int theta_constant, int n, int hc, int wc,
                                int hf, int wf, float* inputs, float* targets, hipStream_t stream);
+
+/* ---- batched cascade levels: E examples side by side (src/resolution_comparison.py:160-229 run per example
+ *      by src/resolution_comparison_statistical.py:98-205).  Fields are contiguous fp64 [E][n][n] device arrays,
+ *      model tensors contiguous fp32 NCHW.  Tiles are ordered example-major, then row-major over the
+ *      (S / tile)^2 tiles of one example.  stats = [E][6] fp32 rows {u_mean, u_std, f_mean, f_std, theta_mean,
+ *      theta_std}.  All reductions run in a fixed order without atomics: results are bit-reproducible. -------- */
+/* GlobalNormalization (resolution_comparison.py:160-181) of every example from the next level's ground truth
+ * u / f / theta [E][S2][S2]: mean and unbiased std of the fp32-cast values, accumulated in fp64 and rounded once
+ * to fp32.  theta_const[e] (int32) = 1 when theta's fp32 std < 1e-6; that row then holds theta_mean = 0,
+ * theta_std = 1, so normalising theta with the row is an exact identity.  The decision stays on the device (no
+ * host synchronisation).  Two launches; workspace: srpde_cascade_level_stats_workspace_size bytes, 8-byte aligned. */
+size_t srpde_cascade_level_stats_workspace_size(int E, int S2);
+int srpde_cascade_level_stats(const double* u, const double* f, const double* theta, int E, int S2, float* stats,
+                              int* theta_const, void* workspace, size_t ws_bytes, hipStream_t stream);
+/* The U-Net input of one level, x [E (S/tile)^2][3][2 tile][2 tile]: channel 0 = the tile^2 tile of u_cur
+ * [E][S][S] cast to fp32, normalised (v - u_mean) / u_std and resized bilinearly (align_corners=True,
+ * srpde_upsample_bilinear_fwd's expression) to (2 tile)^2; channels 1 / 2 = the matching tiles of theta_next /
+ * f_next [E][2S][2S], normalised.  Bit for bit the torch chain cast, subtract, divide, upsample, cat run per
+ * example with the same statistics.  S must be a multiple of tile. */
+int srpde_cascade_level_assemble(const double* u_cur, const double* f_next, const double* theta_next,
+                                 const float* stats, int E, int S, int tile, float* x, hipStream_t stream);
+/* The way back: u_next [E][2S][2S] fp64 = y * u_std + u_mean (an fp32 multiply, then an fp32 add, widened) of
+ * the U-Net output y [E (S/tile)^2][1][2 tile][2 tile], every tile at its place.  S is the level's INPUT size, as
+ * in srpde_cascade_level_assemble. */
+int srpde_cascade_stitch_denorm(const float* y, const float* stats, int E, int S, int tile, double* u_next,
+                                hipStream_t stream);
+/* Error metrics per example (resolution_comparison_statistical.py:171-178): out [E][3] fp64 = {mean |d|,
+ * sqrt(mean d^2), max |d|}, d = pred - gt in fp64; pred [E][n][n] is fp32 (pred_is_f32 != 0) or fp64, gt fp64.
+ * Two launches; workspace: srpde_field_metrics_workspace_size bytes, 8-byte aligned. */
+size_t srpde_field_metrics_workspace_size(int E, int n);
+int srpde_field_metrics(const void* pred, int pred_is_f32, const double* gt, int E, int n, double* out,
+                        void* workspace, size_t ws_bytes, hipStream_t stream);
 
 /* ---- bicubic, align_corners=True, single-channel fields [planes][h][w] -> [planes][ho][wo]:
  *      F.interpolate(mode='bicubic') of the cascade's interpolation baselines

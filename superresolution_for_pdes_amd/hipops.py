@@ -804,6 +804,73 @@ def pde_dataset_assemble(u_coarse, u_fine, theta_fine, f_fine, stats, theta_cons
     return inputs, targets
 
 
+# ------------------------------ batched cascade levels ------------------------------
+def _fields(name, dtype, *ts):
+    for t in ts:
+        if not (t.is_cuda and t.dtype == dtype and t.is_contiguous()):
+            raise RuntimeError(f"{name}: contiguous {dtype} ROCm tensors only (no CPU fallback)")
+
+
+def cascade_level_stats(u, f, theta):
+    """srpde_cascade_level_stats: GlobalNormalization of E examples from their [E, S2, S2] fp64 fields ->
+    (stats [E, 6] fp32, theta_const [E] int32); nothing is read back to the host."""
+    _fields("cascade_level_stats", torch.float64, u, f, theta)
+    if u.dim() != 3 or u.shape[1] != u.shape[2] or f.shape != u.shape or theta.shape != u.shape:
+        raise ValueError("cascade_level_stats: u, f, theta must share one [E, S2, S2] shape")
+    E, S2, _ = u.shape
+    stats = torch.empty(E, 6, dtype=F32, device=u.device)
+    flags = torch.empty(E, dtype=torch.int32, device=u.device)
+    nbytes = int(query("srpde_cascade_level_stats_workspace_size", E, S2))
+    ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=u.device)
+    call("srpde_cascade_level_stats", u.data_ptr(), f.data_ptr(), theta.data_ptr(), E, S2, stats.data_ptr(),
+         flags.data_ptr(), ws.data_ptr(), nbytes, stream_ptr())
+    return stats, flags
+
+
+def cascade_level_assemble(u_cur, f_next, theta_next, stats, tile=20):
+    """srpde_cascade_level_assemble: u_cur [E, S, S], f_next / theta_next [E, 2S, 2S] (fp64), stats [E, 6] ->
+    the U-Net input [E (S/tile)^2, 3, 2 tile, 2 tile] fp32, tiles example-major then row-major."""
+    _fields("cascade_level_assemble", torch.float64, u_cur, f_next, theta_next)
+    _fields("cascade_level_assemble", F32, stats)
+    E, S, _ = u_cur.shape
+    if u_cur.shape != (E, S, S) or f_next.shape != (E, 2 * S, 2 * S) or theta_next.shape != f_next.shape or \
+            stats.shape != (E, 6):
+        raise ValueError("cascade_level_assemble: u_cur [E, S, S], f_next / theta_next [E, 2S, 2S], stats [E, 6]")
+    x = torch.empty(E * (S // max(tile, 1)) ** 2, 3, 2 * tile, 2 * tile, dtype=F32, device=u_cur.device)
+    call("srpde_cascade_level_assemble", u_cur.data_ptr(), f_next.data_ptr(), theta_next.data_ptr(), stats.data_ptr(),
+         E, S, tile, x.data_ptr(), stream_ptr())
+    return x
+
+
+def cascade_stitch_denorm(y, stats, E, S, tile=20):
+    """srpde_cascade_stitch_denorm: the U-Net output y [E (S/tile)^2, 1, 2 tile, 2 tile] -> the next level's
+    fields [E, 2S, 2S] fp64 = y * u_std + u_mean (fp32), every tile at its place."""
+    _fields("cascade_stitch_denorm", F32, y, stats)
+    if y.numel() != E * 4 * S * S or stats.shape != (E, 6):
+        raise ValueError("cascade_stitch_denorm: y must hold E (2S)^2 values, stats [E, 6]")
+    out = torch.empty(E, 2 * S, 2 * S, dtype=torch.float64, device=y.device)
+    call("srpde_cascade_stitch_denorm", y.data_ptr(), stats.data_ptr(), E, S, tile, out.data_ptr(), stream_ptr())
+    return out
+
+
+def field_metrics(pred, gt):
+    """srpde_field_metrics: pred [E, n, n] (fp32 or fp64) against gt [E, n, n] fp64 -> [E, 3] fp64 device
+    tensor of (MAE, RMSE, max error) per example."""
+    _fields("field_metrics", torch.float64, gt)
+    if pred.dtype not in (F32, torch.float64):
+        raise RuntimeError("field_metrics: pred must be fp32 or fp64")
+    _fields("field_metrics", pred.dtype, pred)
+    if gt.dim() != 3 or gt.shape[1] != gt.shape[2] or pred.shape != gt.shape:
+        raise ValueError("field_metrics: pred and gt must share one [E, n, n] shape")
+    E, n, _ = gt.shape
+    out = torch.empty(E, 3, dtype=torch.float64, device=gt.device)
+    nbytes = int(query("srpde_field_metrics_workspace_size", E, n))
+    ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=gt.device)
+    call("srpde_field_metrics", pred.data_ptr(), int(pred.dtype == F32), gt.data_ptr(), E, n, out.data_ptr(),
+         ws.data_ptr(), nbytes, stream_ptr())
+    return out
+
+
 def upsample_bwd(dout, dx, n, h, w, ho, wo, accumulate, gate=None, bn=None):
     """``gate = (dsa, wg)``: the upsampled tensor's gradient is dout + dsa (x) wg (the attention
     gating gradient left unapplied by att_bwd(dg=None)).  ``bn = (y, mean, invstd, gamma, beta)``: the BN +

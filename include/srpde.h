@@ -58,8 +58,10 @@ typedef struct ihipStream_t* hipStream_t;
  *  11  srpde_upsample_bilinear_bwd_gated_bn, srpde_upsample_bwd_bn_supported, srpde_gating_bn_reduce(_blocks),
  *      srpde_att_bwd_params_lowres, srpde_conv_wgrad_bnb
  *  12  the batched cascade: srpde_cascade_level_stats(_workspace_size), srpde_cascade_level_assemble,
- *      srpde_cascade_stitch_denorm, srpde_field_metrics(_workspace_size) */
-#define SRPDE_ABI_VERSION 12
+ *      srpde_cascade_stitch_denorm, srpde_field_metrics(_workspace_size)
+ *  13  the direct sine-transform Poisson solver: srpde_poisson_dst_plan(_size), srpde_poisson_dst_lds_max_n,
+ *      srpde_poisson_dst_workspace_size, srpde_poisson_dst_batched, srpde_poisson_dst_apply */
+#define SRPDE_ABI_VERSION 13
 
 /* Kernel-family bits (per call; bit 0 of the same argument is the accumulate flag): the forward / dgrad
  * families compute the same outputs, statistics and stored splits bit for bit, so these only route a call to
@@ -558,6 +560,35 @@ int srpde_poisson_cg_grid_iterate(int B, int n, double rtol, int k_begin, int k_
 size_t srpde_poisson_cg_grid_done_offset(int B, int n);
 int srpde_poisson_cg_grid_finish(double* u, int* iters, int B, int n, int maxit, void* ws, size_t ws_bytes,
                                  hipStream_t stream);
+
+/* ---- Direct Poisson solve by the 2-D sine transform (DST-I): the same system as srpde_poisson_cg_batched,
+ *      solved exactly.  L = (T (x) I + I (x) T) / h^2 with T = tridiag(1, -2, 1); the symmetric orthogonal
+ *      S[j][k] = sqrt(2 / (n + 1)) sin(pi (j + 1)(k + 1) / (n + 1)) diagonalises T with eigenvalues
+ *      lam_k = -4 sin^2(pi (k + 1) / (2 (n + 1))), so
+ *          U = S ( (S (F / Theta) S) o h^2 / (lam_i + lam_j) ) S
+ *      -- four dense fp64 products against one matrix per problem (fp64 MFMA): no iteration, no cooperative
+ *      launch, no grid barrier, any n up to 16384.  Results are bit-reproducible and independent of B. ---- */
+/* The plan is a caller-owned device buffer (the library keeps no state): S [n][n] then lam [n], fp64.
+ * A plan belongs to one n; the solve entries take it with its exact size, srpde_poisson_dst_plan_size(n)
+ * bytes (0 for an n outside 1 .. 16384), and refuse any other size. */
+size_t srpde_poisson_dst_plan_size(int n);
+/* Fills the plan for n (one launch; plan_bytes >= srpde_poisson_dst_plan_size(n), plan 8-byte aligned). */
+int srpde_poisson_dst_plan(int n, void* plan, size_t plan_bytes, hipStream_t stream);
+/* n up to which one workgroup solves one problem with S and the field in LDS (one launch, no workspace). */
+int srpde_poisson_dst_lds_max_n(void);
+/* Workspace of the two entries below: 0 for n <= srpde_poisson_dst_lds_max_n() (and for B <= 0), else one
+ * [B][n][n] fp64 field; 16-byte aligned. */
+size_t srpde_poisson_dst_workspace_size(int B, int n);
+/* u = solution of theta * L u = f for B problems: f, theta, u are [B][n][n] fp64 device arrays, n >= 2.
+ * Above the LDS limit: four launches of a batched tiled product (f / theta at the first one's load, the
+ * eigenvalue scaling at the second one's store); u must not alias f or theta there.  Stream-ordered, no host
+ * sync, no state: capturable in a graph. */
+int srpde_poisson_dst_batched(const double* f, const double* theta, double* u, int B, int n, const void* plan,
+                              size_t plan_bytes, void* ws, size_t ws_bytes, hipStream_t stream);
+/* y = S x S, the orthonormal 2-D DST-I of B fields [B][n][n] (its own inverse); y must not alias x above the
+ * LDS limit. */
+int srpde_poisson_dst_apply(const double* x, double* y, int B, int n, const void* plan, size_t plan_bytes, void* ws,
+                            size_t ws_bytes, hipStream_t stream);
 
 /* ---- Row-sharded CG for ONE n x n problem over `world` ranks (the 640^2 ground
  *      truth of solve_multi_resolution, src/resolution_comparison.py:62-73).  Rank `rank` owns the

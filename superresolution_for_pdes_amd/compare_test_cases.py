@@ -29,15 +29,16 @@ from .models import PDEDataset, upsample_bilinear
 
 
 def generate_test_data(k_range: tuple, n_samples: int = 10, label: str = "test", constant_theta: bool = True,
-                       save_dir: str | None = None, device: str = "cuda") -> dict:
+                       save_dir: str | None = None, device: str = "cuda", solver: str = "cg") -> dict:
     """compare_test_cases.py:12-79.  ``constant_theta``: theta = 1 (the solves of
     ``generate_dataset`` already are theta = 1, so re-solving reproduces them); otherwise one
     U(0.5, 2) theta field per sample, drawn in sample order after the k draws, coarse theta =
     theta_fine[::2, ::2], and both grids re-solved.  ``save_dir``: also np.savez the set as
-    ``{label}_dataset.npz`` there (the reference always saves under data/)."""
-    solver = PoissonSolver(device=device)
-    data = solver.generate_dataset(n_samples=n_samples, k_range=k_range)
-    nf = solver.n_fine
+    ``{label}_dataset.npz`` there (the reference always saves under data/).  ``solver``: "cg" or "dst"
+    (poisson.solve_batched's method) for every solve of the set."""
+    gen = PoissonSolver(device=device, solver=solver)
+    data = gen.generate_dataset(n_samples=n_samples, k_range=k_range)
+    nf = gen.n_fine
     if constant_theta:
         data["theta_fine"] = np.ones_like(data["theta_fine"])
         data["theta_coarse"] = np.ones_like(data["theta_coarse"])
@@ -47,8 +48,8 @@ def generate_test_data(k_range: tuple, n_samples: int = 10, label: str = "test",
             th_f[i] = np.random.uniform(0.5, 2.0, size=(nf, nf))
         th_c = np.ascontiguousarray(th_f[:, ::2, ::2])
         data["theta_fine"], data["theta_coarse"] = th_f, th_c
-        data["u_fine"] = P.solve_batched(data["f_fine"], th_f, device=device).cpu().numpy()
-        data["u_coarse"] = P.solve_batched(data["f_coarse"], th_c, device=device).cpu().numpy()
+        data["u_fine"] = P.solve_batched(data["f_fine"], th_f, device=device, method=solver).cpu().numpy()
+        data["u_coarse"] = P.solve_batched(data["f_coarse"], th_c, device=device, method=solver).cpu().numpy()
     if save_dir is not None:
         path = Path(save_dir)
         path.mkdir(parents=True, exist_ok=True)

@@ -1,0 +1,361 @@
+// Direct Poisson solve by the 2-D sine transform (DST-I), gfx950, fp64 MFMA.
+//
+// The operator of srpde_poisson_cg_batched, theta * L u = f with L the 5-point Laplacian on all n^2 nodes of an
+// n x n grid (zero ghost ring, h = 1 / (n - 1)), is L = (T (x) I + I (x) T) / h^2 with T = tridiag(1, -2, 1).
+// The symmetric orthogonal sine matrix S[j][k] = sqrt(2 / (n + 1)) sin(pi (j + 1)(k + 1) / (n + 1)) diagonalises
+// T with eigenvalues lam_k = -4 sin^2(pi (k + 1) / (2 (n + 1))), hence exactly
+//
+//     U = S ( (S (F / Theta) S) o h^2 / (lam_i + lam_j) ) S
+//
+// four dense n x n products per problem against one fixed matrix: no iteration, no convergence test, no
+// cooperative launch, no grid barrier.
+//
+//   srpde_poisson_dst_plan     fills the caller-owned plan: S [n][n] then lam [n] (the library keeps no state).
+//                              The sine argument is reduced in integers, m = (j + 1)(k + 1) mod 2 (n + 1), and
+//                              evaluated as sinpi(m / (n + 1)): sin(pi j k / (n + 1)) loses ~1e-13 at n = 640.
+//   n <= kDstLdsMaxN           dst_fused_kernel: one workgroup per problem, S and the field in LDS (zero-padded
+//                              to whole 16 x 16 tiles), every product accumulated in registers and written back
+//                              after a barrier; f and theta are read once, u is written once.  One launch.
+//   any other n                dst_gemm_kernel: a batched 64 x 64-tile product C[b] = A[b] B[b] where either
+//                              operand may be the shared S (batch stride 0): X S, then S X, X S, S X.  The
+//                              division by theta is in the first product's operand load, the multiplication by
+//                              h^2 / (lam_i + lam_j) in the second product's store.  Four launches.
+//
+// Both use v_mfma_f64_16x16x4_f64.  Lane l gives A[row l & 15][k = l >> 4] and B[k = l >> 4][col l & 15] and
+// holds C[row (l >> 4) + 4 r][col l & 15] in register r = 0..3 (not the f32 16x16 map).
+//
+// The k order of every sum is ascending and fixed by n alone, there are no atomics, and a problem's blocks
+// never see another problem: results are bit-reproducible and independent of B.
+#include "common.h"
+
+namespace srpde {
+
+using d4 = __attribute__((ext_vector_type(4))) double;
+
+constexpr int kDstLdsMaxN = 96;     // two [96][98] fp64 buffers: 150,528 of the CU's 163,840 bytes of LDS
+constexpr int kDstMaxN = 16384;     // n^2 stays inside int
+
+static size_t dst_plan_bytes(int n) { return ((size_t)n * n + (size_t)n) * sizeof(double); }
+
+__device__ __forceinline__ d4 mfma_f64(double a, double b, d4 c) {
+  return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
+}
+
+__global__ __launch_bounds__(256) void dst_plan_kernel(int n, double* __restrict__ S, double* __restrict__ lam) {
+  const long long total = (long long)n * n;
+  const int n1 = n + 1;
+  const double scale = sqrt(2.0 / (double)n1);
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const int j = (int)(i / n), k = (int)(i - (long long)j * n);
+    const long long m = ((long long)(j + 1) * (k + 1)) % (2LL * n1);
+    S[i] = scale * sinpi((double)m / (double)n1);
+    if (i < n) {
+      const double s = sinpi((double)(i + 1) / (2.0 * (double)n1));
+      lam[i] = -4.0 * s * s;
+    }
+  }
+}
+
+// ---- general path ------------------------------------------------------------------------------------------
+constexpr int kGT = 64;            // block tile (rows and columns); four waves, 32 x 32 each
+constexpr int kGK = 16;            // k per LDS stage
+constexpr int kGLdA = kGK + 1;     // As[m][k]: lanes 0..15 read 16 rows at one k, 17 spreads them over the banks
+constexpr int kGLdB = kGT + 16;    // Bs[k][c]: the two k rows of a half wave land 32 banks apart
+
+// C[b] = A[b] B[b], all [n][n] row-major, batch strides sA / sB / sC in elements (0: shared by every problem).
+// DIV: A's elements are divided by th's (same indexing as A) as they are loaded.
+// SCALE: C[i][j] is multiplied by h2 / (lam[i] + lam[j]) as it is stored.
+template <bool DIV, bool SCALE>
+__global__ __launch_bounds__(256) void dst_gemm_kernel(const double* __restrict__ A, long long sA,
+                                                       const double* __restrict__ Bm, long long sB,
+                                                       double* __restrict__ C, long long sC,
+                                                       const double* __restrict__ th, const double* __restrict__ lam,
+                                                       double h2, int n, int nbatch) {
+  __shared__ double As[kGT * kGLdA];
+  __shared__ double Bs[kGK * kGLdB];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wr = (wave >> 1) * 32, wc = (wave & 1) * 32;
+  const int m0 = blockIdx.y * kGT, c0 = blockIdx.x * kGT;
+  const int l15 = lane & 15, l4 = lane >> 4;
+  const int ka = tid & 15, ma = tid >> 4;   // A stage: rows ma + 16 i, column ka
+  const int cb = tid & 63, kb = tid >> 6;   // B stage: rows kb + 4 i, column cb
+
+  for (int b = blockIdx.z; b < nbatch; b += gridDim.z) {
+    const double* Ab = A + (long long)b * sA;
+    const double* Tb = DIV ? th + (long long)b * sA : nullptr;
+    const double* Bb = Bm + (long long)b * sB;
+    double* Cb = C + (long long)b * sC;
+    d4 acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) acc[i][j] = d4{0.0, 0.0, 0.0, 0.0};
+    double ra[4], rb[4];
+
+    auto fetch = [&](int k0) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int r = m0 + ma + 16 * i, c = k0 + ka;
+        double v = 0.0;
+        if (r < n && c < n) {
+          const long long at = (long long)r * n + c;
+          v = Ab[at];
+          if (DIV) v = v / Tb[at];
+        }
+        ra[i] = v;
+        const int rk = k0 + kb + 4 * i, cc = c0 + cb;
+        rb[i] = (rk < n && cc < n) ? Bb[(long long)rk * n + cc] : 0.0;
+      }
+    };
+
+    fetch(0);
+    for (int k0 = 0; k0 < n; k0 += kGK) {
+      __syncthreads();   // the previous stage's reads are over
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        As[(ma + 16 * i) * kGLdA + ka] = ra[i];
+        Bs[(kb + 4 * i) * kGLdB + cb] = rb[i];
+      }
+      __syncthreads();
+      if (k0 + kGK < n) fetch(k0 + kGK);
+#pragma unroll
+      for (int ks = 0; ks < kGK / 4; ++ks) {
+        const int k = 4 * ks + l4;
+        const double a0 = As[(wr + l15) * kGLdA + k], a1 = As[(wr + 16 + l15) * kGLdA + k];
+        const double b0 = Bs[k * kGLdB + wc + l15], b1 = Bs[k * kGLdB + wc + 16 + l15];
+        acc[0][0] = mfma_f64(a0, b0, acc[0][0]);
+        acc[0][1] = mfma_f64(a0, b1, acc[0][1]);
+        acc[1][0] = mfma_f64(a1, b0, acc[1][0]);
+        acc[1][1] = mfma_f64(a1, b1, acc[1][1]);
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int col = c0 + wc + 16 * j + l15;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = m0 + wr + 16 * i + l4 + 4 * r;
+          if (row < n && col < n) {
+            double v = acc[i][j][r];
+            if (SCALE) v = v * (h2 / (lam[row] + lam[col]));
+            Cb[(long long)row * n + col] = v;
+          }
+        }
+      }
+  }
+}
+
+// ---- fused small-n path ------------------------------------------------------------------------------------
+// One workgroup per problem; np = n rounded up to 16, ld = np + 2, LDS = Sl[np][ld] then Xl[np][ld], both
+// zero outside [n][n] so no product needs an edge guard.  The np / 16 row strips of a product are split into
+// column groups of at most three 16 x 16 tiles; each wave owns one (strip, group) -- the launch has exactly
+// that many waves (at most 12).  Products alternate X S (even) and S X (odd; S's fragment is read through its
+// symmetry, S[m][k] = S[k][m], so S is always read along its rows); the last one goes to global memory.
+// SOLVE: x / theta at the load, h^2 / (lam_i + lam_j) after the second product, four products; else two
+// (y = S x S).
+constexpr int kFusedGroupTiles = 3;
+
+static int dst_fused_np(int n) { return (n + 15) & ~15; }
+static int dst_fused_waves(int n) {
+  const int nt = dst_fused_np(n) / 16;
+  return nt * ((nt + kFusedGroupTiles - 1) / kFusedGroupTiles);
+}
+static size_t dst_fused_lds(int n) {
+  const int np = dst_fused_np(n);
+  return (size_t)2 * np * (np + 2) * sizeof(double);
+}
+
+template <bool SOLVE>
+__global__ __launch_bounds__(768) void dst_fused_kernel(const double* __restrict__ x, const double* __restrict__ th,
+                                                        double* __restrict__ y, const double* __restrict__ S,
+                                                        const double* __restrict__ lam, double h2, int n) {
+  extern __shared__ double dst_lds[];
+  const int np = (n + 15) & ~15, ld = np + 2;
+  double* Sl = dst_lds;
+  double* Xl = dst_lds + np * ld;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int l15 = lane & 15, l4 = lane >> 4;
+  const long long base = (long long)blockIdx.x * n * n;
+  const double* xb = x + base;
+  const double* tb = SOLVE ? th + base : nullptr;
+  double* yb = y + base;
+
+  for (int i = tid; i < np * np; i += blockDim.x) {
+    const int r = i / np, c = i - r * np;
+    double sv = 0.0, xv = 0.0;
+    if (r < n && c < n) {
+      sv = S[r * n + c];
+      xv = xb[r * n + c];
+      if (SOLVE) xv = xv / tb[r * n + c];
+    }
+    Sl[r * ld + c] = sv;
+    Xl[r * ld + c] = xv;
+  }
+  __syncthreads();
+
+  const int nt = np / 16, ngrp = (nt + kFusedGroupTiles - 1) / kFusedGroupTiles;
+  const int per = (nt + ngrp - 1) / ngrp;          // column tiles per group (<= 3)
+  const int strip = wave / ngrp, grp = wave - strip * ngrp;
+  const int ct0 = grp * per, ctn = min(nt, ct0 + per) - ct0;
+  const int row0 = 16 * strip;
+  const int ksteps = (n + 3) / 4;                  // k beyond n is zero in both buffers
+  constexpr int nprod = SOLVE ? 4 : 2;
+
+#pragma unroll 1
+  for (int p = 0; p < nprod; ++p) {
+    d4 acc[kFusedGroupTiles];
+#pragma unroll
+    for (int j = 0; j < kFusedGroupTiles; ++j) acc[j] = d4{0.0, 0.0, 0.0, 0.0};
+    const bool xs = (p & 1) == 0;                  // X S; else S X
+    const double* Am = xs ? Xl : Sl;
+    const double* Bk = xs ? Sl : Xl;
+    for (int ks = 0; ks < ksteps; ++ks) {
+      const int k = 4 * ks + l4;
+      const double a = xs ? Am[(row0 + l15) * ld + k] : Am[k * ld + row0 + l15];
+#pragma unroll
+      for (int j = 0; j < kFusedGroupTiles; ++j)
+        if (j < ctn) acc[j] = mfma_f64(a, Bk[k * ld + 16 * (ct0 + j) + l15], acc[j]);
+    }
+    const bool last = p == nprod - 1;
+    if (!last) __syncthreads();                    // every wave has read Xl
+#pragma unroll
+    for (int j = 0; j < kFusedGroupTiles; ++j)
+      if (j < ctn) {
+        const int col = 16 * (ct0 + j) + l15;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = row0 + l4 + 4 * r;
+          const bool in = row < n && col < n;
+          double v = acc[j][r];
+          if (SOLVE && p == 1) v = in ? v * (h2 / (lam[row] + lam[col])) : 0.0;
+          if (last) {
+            if (in) yb[row * n + col] = v;
+          } else {
+            Xl[row * ld + col] = v;
+          }
+        }
+      }
+    if (!last) __syncthreads();
+  }
+}
+
+static int gemm_launch(bool div, bool scale, const double* A, long long sA, const double* Bm, long long sB, double* C,
+                       long long sC, const double* th, const double* lam, double h2, int n, int B,
+                       hipStream_t stream) {
+  const int t = ceil_div(n, kGT);
+  const dim3 grid(t, t, std::min(B, 65535)), block(256);
+  if (div)
+    hipLaunchKernelGGL((dst_gemm_kernel<true, false>), grid, block, 0, stream, A, sA, Bm, sB, C, sC, th, lam, h2, n, B);
+  else if (scale)
+    hipLaunchKernelGGL((dst_gemm_kernel<false, true>), grid, block, 0, stream, A, sA, Bm, sB, C, sC, th, lam, h2, n, B);
+  else
+    hipLaunchKernelGGL((dst_gemm_kernel<false, false>), grid, block, 0, stream, A, sA, Bm, sB, C, sC, th, lam, h2, n, B);
+  return 0;
+}
+
+}  // namespace srpde
+
+using namespace srpde;
+
+#define DST_FAIL(code, ...)          \
+  do {                               \
+    ::srpde::set_error(__VA_ARGS__); \
+    return code;                     \
+  } while (0)
+
+extern "C" {
+
+size_t srpde_poisson_dst_plan_size(int n) { return (n <= 0 || n > kDstMaxN) ? 0 : dst_plan_bytes(n); }
+
+int srpde_poisson_dst_lds_max_n(void) { return kDstLdsMaxN; }
+
+size_t srpde_poisson_dst_workspace_size(int B, int n) {
+  if (B <= 0 || n <= kDstLdsMaxN || n > kDstMaxN) return 0;
+  return (size_t)B * n * n * sizeof(double);
+}
+
+int srpde_poisson_dst_plan(int n, void* plan, size_t plan_bytes, hipStream_t stream) {
+  SRPDE_CHECK_ARG(plan, "srpde_poisson_dst_plan: null pointer");
+  if (n <= 0 || n > kDstMaxN) DST_FAIL(kErrShape, "srpde_poisson_dst_plan: bad shape n=%d (1 .. %d)", n, kDstMaxN);
+  if (reinterpret_cast<uintptr_t>(plan) & 7u) DST_FAIL(kErrAlign, "srpde_poisson_dst_plan: plan not 8-byte aligned");
+  if (plan_bytes < dst_plan_bytes(n))
+    DST_FAIL(kErrWorkspace, "srpde_poisson_dst_plan: plan buffer too small (%zu bytes, n=%d needs %zu)", plan_bytes, n,
+             dst_plan_bytes(n));
+  double* S = static_cast<double*>(plan);
+  const int blocks = (int)std::min<long long>(((long long)n * n + 255) / 256, 8192);
+  hipLaunchKernelGGL(dst_plan_kernel, dim3(blocks), dim3(256), 0, stream, n, S, S + (size_t)n * n);
+  SRPDE_LAUNCH_CHECK("srpde_poisson_dst_plan");
+  return 0;
+}
+
+// the checks srpde_poisson_dst_batched and srpde_poisson_dst_apply share; a plan is tied to its n by its size
+static int dst_check(const char* name, int B, int n, int nmin, const void* plan, size_t plan_bytes, const void* ws,
+                     size_t ws_bytes) {
+  if (B <= 0 || n < nmin || n > kDstMaxN)
+    DST_FAIL(kErrShape, "%s: bad shape B=%d n=%d (B >= 1, n %d .. %d)", name, B, n, nmin, kDstMaxN);
+  if (reinterpret_cast<uintptr_t>(plan) & 7u) DST_FAIL(kErrAlign, "%s: plan not 8-byte aligned", name);
+  if (plan_bytes != dst_plan_bytes(n))
+    DST_FAIL(kErrWorkspace, "%s: a plan of %zu bytes is not a plan for n=%d (srpde_poisson_dst_plan_size: %zu)", name,
+             plan_bytes, n, dst_plan_bytes(n));
+  if (n > kDstLdsMaxN) {
+    if (!ws) DST_FAIL(kErrArg, "%s: null workspace (n=%d > %d needs one)", name, n, kDstLdsMaxN);
+    if (!aligned16(ws)) DST_FAIL(kErrAlign, "%s: workspace not 16-byte aligned", name);
+    if (ws_bytes < srpde_poisson_dst_workspace_size(B, n))
+      DST_FAIL(kErrWorkspace, "%s: workspace too small (%zu bytes, needs %zu)", name, ws_bytes,
+               srpde_poisson_dst_workspace_size(B, n));
+  }
+  return 0;
+}
+
+int srpde_poisson_dst_batched(const double* f, const double* theta, double* u, int B, int n, const void* plan,
+                              size_t plan_bytes, void* ws, size_t ws_bytes, hipStream_t stream) {
+  const char* name = "srpde_poisson_dst_batched";
+  SRPDE_CHECK_ARG(f && theta && u && plan, "srpde_poisson_dst_batched: null pointer");
+  if (int rc = dst_check(name, B, n, 2, plan, plan_bytes, ws, ws_bytes)) return rc;
+  const double* S = static_cast<const double*>(plan);
+  const double* lam = S + (size_t)n * n;
+  const double h = 1.0 / (double)(n - 1), h2 = h * h;
+  if (n <= kDstLdsMaxN) {
+    hipLaunchKernelGGL(dst_fused_kernel<true>, dim3(B), dim3(64 * dst_fused_waves(n)), dst_fused_lds(n), stream, f,
+                       theta, u, S, lam, h2, n);
+    SRPDE_LAUNCH_CHECK(name);
+    return 0;
+  }
+  const long long nn = (long long)n * n;
+  double* w = static_cast<double*>(ws);
+  gemm_launch(true, false, f, nn, S, 0, w, nn, theta, lam, h2, n, B, stream);     // w = (f / theta) S
+  SRPDE_LAUNCH_CHECK(name);
+  gemm_launch(false, true, S, 0, w, nn, u, nn, nullptr, lam, h2, n, B, stream);   // u = (S w) o h^2 / (lam + lam)
+  SRPDE_LAUNCH_CHECK(name);
+  gemm_launch(false, false, u, nn, S, 0, w, nn, nullptr, lam, h2, n, B, stream);  // w = u S
+  SRPDE_LAUNCH_CHECK(name);
+  gemm_launch(false, false, S, 0, w, nn, u, nn, nullptr, lam, h2, n, B, stream);  // u = S w
+  SRPDE_LAUNCH_CHECK(name);
+  return 0;
+}
+
+int srpde_poisson_dst_apply(const double* x, double* y, int B, int n, const void* plan, size_t plan_bytes, void* ws,
+                            size_t ws_bytes, hipStream_t stream) {
+  const char* name = "srpde_poisson_dst_apply";
+  SRPDE_CHECK_ARG(x && y && plan, "srpde_poisson_dst_apply: null pointer");
+  if (int rc = dst_check(name, B, n, 1, plan, plan_bytes, ws, ws_bytes)) return rc;
+  const double* S = static_cast<const double*>(plan);
+  const double* lam = S + (size_t)n * n;
+  if (n <= kDstLdsMaxN) {
+    hipLaunchKernelGGL(dst_fused_kernel<false>, dim3(B), dim3(64 * dst_fused_waves(n)), dst_fused_lds(n), stream, x,
+                       nullptr, y, S, lam, 0.0, n);
+    SRPDE_LAUNCH_CHECK(name);
+    return 0;
+  }
+  const long long nn = (long long)n * n;
+  double* w = static_cast<double*>(ws);
+  gemm_launch(false, false, x, nn, S, 0, w, nn, nullptr, lam, 0.0, n, B, stream);   // w = x S
+  SRPDE_LAUNCH_CHECK(name);
+  gemm_launch(false, false, S, 0, w, nn, y, nn, nullptr, lam, 0.0, n, B, stream);   // y = S w
+  SRPDE_LAUNCH_CHECK(name);
+  return 0;
+}
+
+}  // extern "C"

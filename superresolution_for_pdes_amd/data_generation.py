@@ -64,10 +64,11 @@ def to_numpy(d: dict) -> dict:
 
 
 class PoissonSolver:
-    def __init__(self, n_coarse: int = 20, n_fine: int = 40, device: str = "cuda"):
+    def __init__(self, n_coarse: int = 20, n_fine: int = 40, device: str = "cuda", solver: str = "cg"):
         self.n_coarse = n_coarse
         self.n_fine = n_fine
         self.device = device
+        self.solver = P.check_solver(solver)   # "cg" or "dst" (poisson.solve_batched's method)
         self.x_coarse = np.linspace(0, 1, n_coarse)
         self.y_coarse = np.linspace(0, 1, n_coarse)
         self.x_fine = np.linspace(0, 1, n_fine)
@@ -108,11 +109,11 @@ class PoissonSolver:
         n = self._n(grid)
         f = np.asarray(f, dtype=np.float64).reshape(n, n)
         theta = np.asarray(theta, dtype=np.float64).reshape(n, n)
-        return P.solve_batched(f, theta, device=self.device)[0].cpu().numpy()
+        return P.solve_batched(f, theta, device=self.device, method=self.solver)[0].cpu().numpy()
 
     def solve_poisson_batched(self, f, theta, grid: str = "fine") -> torch.Tensor:
         """Batched on-device solve: f, theta [B, n, n] (numpy or tensors) -> u [B, n, n] float64 tensor."""
-        return P.solve_batched(f, theta, device=self.device)
+        return P.solve_batched(f, theta, device=self.device, method=self.solver)
 
     def generate_dataset(self, n_samples: int, k_range: Tuple[float, float] = (1, 5), keep_on_device: bool = False,
                          shard=None) -> dict:
@@ -142,8 +143,8 @@ class PoissonSolver:
         th_f = torch.ones(ns, nf, nf, dtype=torch.float64, device=self.device)
         th_c = torch.ones(ns, nc, nc, dtype=torch.float64, device=self.device)
         return {
-            "u_coarse": P.solve_batched(f_coarse, th_c, device=self.device),
-            "u_fine": P.solve_batched(f_fine, th_f, device=self.device),
+            "u_coarse": P.solve_batched(f_coarse, th_c, device=self.device, method=self.solver),
+            "u_fine": P.solve_batched(f_fine, th_f, device=self.device, method=self.solver),
             "f_coarse": f_coarse,
             "f_fine": f_fine,
             "theta_coarse": th_c,

@@ -18,8 +18,9 @@ from .data_generation import PoissonSolver, gather_fields, resolve_shard, shard_
 
 
 class EnhancedPoissonSolver(PoissonSolver):
-    def __init__(self, n_coarse: int = 20, n_fine: int = 40, n_superfine: int = 80, device: str = "cuda"):
-        super().__init__(n_coarse, n_fine, device)
+    def __init__(self, n_coarse: int = 20, n_fine: int = 40, n_superfine: int = 80, device: str = "cuda",
+                 solver: str = "cg"):
+        super().__init__(n_coarse, n_fine, device, solver=solver)
         self.n_superfine = n_superfine
         self.x_superfine = np.linspace(0, 1, n_superfine)
         self.y_superfine = np.linspace(0, 1, n_superfine)
@@ -35,7 +36,7 @@ class EnhancedPoissonSolver(PoissonSolver):
     def solve_poisson_superfine(self, f: np.ndarray, theta: np.ndarray) -> np.ndarray:
         n = self.n_superfine
         return P.solve_batched(np.asarray(f, np.float64).reshape(n, n), np.asarray(theta, np.float64).reshape(n, n),
-                               device=self.device)[0].cpu().numpy()
+                               device=self.device, method=self.solver)[0].cpu().numpy()
 
     def extract_subdomain(self, field, start_x: int, start_y: int, size: int):
         return field[start_y:start_y + size, start_x:start_x + size]
@@ -61,7 +62,7 @@ class EnhancedPoissonSolver(PoissonSolver):
         k, starts, ns = k_all[lo:hi], starts_all[lo:hi], hi - lo
         f_sf = P.forcing_batched(k, nsf, self.device)
         th_sf = torch.ones(ns, nsf, nsf, dtype=torch.float64, device=self.device)
-        u_sf = P.solve_batched(f_sf, th_sf, device=self.device)
+        u_sf = P.solve_batched(f_sf, th_sf, device=self.device, method=self.solver)
         # crop windows by one gather: rows start_y + i, cols start_x + j
         ar = torch.arange(nf, device=self.device)
         sx = torch.as_tensor(starts[:, 0], device=self.device)

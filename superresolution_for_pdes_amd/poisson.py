@@ -10,6 +10,11 @@ reference) as the SPD system (-L) u = -f/theta by matrix-free CG in fp64:
                the device -- stream-ordered, no host sync.
 Both go through the single C entry ``srpde_poisson_cg_batched`` (include/srpde.h), which a
 non-Python caller binds the same way.
+
+``solve_direct(f, theta)`` / ``solve_batched(..., method="dst")`` solve the same system exactly by the
+2-D sine transform (csrc/poisson_dst.hip): L = (T (x) I + I (x) T) / h^2 is diagonalised by the symmetric
+orthogonal sine matrix S, so u = S ((S (f / theta) S) o h^2 / (lam_i + lam_j)) S -- four dense fp64 MFMA
+products per problem, no iteration, any n.  Opt-in: every default stays CG.
 """
 from __future__ import annotations
 
@@ -41,15 +46,99 @@ class GridBarrierAbort(RuntimeError):
     """A cooperative grid-CG launch gave up at a grid barrier (iters = -1): its u is not a solution."""
 
 
+SOLVERS = ("cg", "dst")
+_dst_plans = {}   # (n, device) -> the plan buffer of srpde_poisson_dst_plan (S [n][n], lam [n])
+
+
+def check_solver(solver: str) -> str:
+    if solver not in SOLVERS:
+        raise ValueError(f"unknown Poisson solver {solver!r}: one of {SOLVERS}")
+    return solver
+
+
+def dst_plan(n: int, device="cuda"):
+    """The sine matrix and eigenvalues for n on ``device``, built on first use (one launch) and kept."""
+    dev = torch.device(device)
+    if dev.index is None:
+        dev = torch.device(dev.type, torch.cuda.current_device())
+    key = (int(n), dev)
+    plan = _dst_plans.get(key)
+    if plan is None:
+        nbytes = int(query("srpde_poisson_dst_plan_size", int(n)))
+        if nbytes == 0:
+            raise ValueError(f"no sine-transform plan for n={n}")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"the sine-transform plan for n={n} must exist before stream capture: call "
+                               "poisson.dst_plan(n) first")
+        plan = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        call("srpde_poisson_dst_plan", int(n), plan.data_ptr(), nbytes, stream_ptr(dev))
+        _dst_plans[key] = plan
+    return plan
+
+
+def _dst_ws(B, n, device):
+    ws_bytes = int(query("srpde_poisson_dst_workspace_size", B, n))
+    return torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=device), ws_bytes
+
+
+def solve_direct(f, theta, device="cuda"):
+    """u[B, n, n] (float64, on device) with theta*Lap(u) = f per problem, by the sine transform: exact up to
+    rounding, cost fixed by the shape, stream-ordered with no host sync (capturable once dst_plan(n) exists)."""
+    f = _dev_f64(f, device)
+    theta = _dev_f64(theta, device)
+    if f.dim() == 2:
+        f, theta = f.unsqueeze(0), theta.unsqueeze(0)
+    if theta.shape != f.shape:
+        theta = theta.expand_as(f).contiguous()
+    B, n, n2 = f.shape
+    if n != n2:
+        raise ValueError("square grids only")
+    u = torch.empty_like(f)
+    if B == 0:
+        return u
+    plan = dst_plan(n, f.device)
+    ws, ws_bytes = _dst_ws(B, n, f.device)
+    call("srpde_poisson_dst_batched", f.data_ptr(), theta.data_ptr(), u.data_ptr(), B, n, plan.data_ptr(),
+         plan.numel(), ws.data_ptr(), ws_bytes, stream_ptr(f.device))
+    return u
+
+
+def dst2(x, device="cuda"):
+    """y = S x S per field: the orthonormal 2-D DST-I of x [B, n, n] (or [n, n]); its own inverse."""
+    x = _dev_f64(x, device)
+    single = x.dim() == 2
+    if single:
+        x = x.unsqueeze(0)
+    B, n, n2 = x.shape
+    if n != n2:
+        raise ValueError("square grids only")
+    y = torch.empty_like(x)
+    if B:
+        plan = dst_plan(n, x.device)
+        ws, ws_bytes = _dst_ws(B, n, x.device)
+        call("srpde_poisson_dst_apply", x.data_ptr(), y.data_ptr(), B, n, plan.data_ptr(), plan.numel(),
+             ws.data_ptr(), ws_bytes, stream_ptr(x.device))
+    return y[0] if single else y
+
+
 def solve_batched(f, theta, rtol: float = DEFAULT_RTOL, maxit: int = None, device="cuda",
-                  return_iters: bool = False, check: bool = True, _start_aborted: bool = False):
+                  return_iters: bool = False, check: bool = True, _start_aborted: bool = False,
+                  method: str = "cg"):
     """u[B, n, n] (float64, on device) with theta*Lap(u) = f per problem.
+
+    ``method="dst"`` solves directly (solve_direct): there is nothing to iterate, so ``return_iters`` gives
+    zeros and non-default ``rtol`` / ``maxit`` / ``check`` / ``_start_aborted`` are refused.
 
     For n above the LDS solver's limit the solve runs as cooperative launches whose grid barriers
     abort after ~1 s of waiting (srpde_poisson_cg_batched marks those problems iters = -1 and
     leaves u unconverged).  ``check`` (default) reads the iteration counts back -- one host sync,
     only on that path, not under stream capture -- and raises GridBarrierAbort instead of returning
     such a u (every data-generation caller otherwise consumed it silently)."""
+    if check_solver(method) == "dst":
+        if rtol != DEFAULT_RTOL or maxit is not None or check is not True or _start_aborted:
+            raise ValueError('method="dst" is a direct solve: rtol, maxit, check and _start_aborted do not apply')
+        u = solve_direct(f, theta, device=device)
+        return (u, torch.zeros(u.shape[0], dtype=torch.int32, device=u.device)) if return_iters else u
     f = _dev_f64(f, device)
     theta = _dev_f64(theta, device)
     if f.dim() == 2:

@@ -28,14 +28,17 @@ def _world() -> int:
 
 
 def solve_multi_resolution(n_coarse: int = 40, resolutions: List[int] = (80, 160, 320, 640), device="cuda",
-                           verbose: bool = False, shard_gt: bool = False):
+                           verbose: bool = False, shard_gt: bool = False, solver: str = "cg"):
     """resolution_comparison.py:13-78 with the GT solves on device (returns numpy fields).
+
+    ``solver``: "cg" or "dst" (poisson.solve_batched's method); the row-sharded solve of ``shard_gt`` is CG.
 
     ``shard_gt``: under a process group of world > 1, the finest level's solve runs row-sharded
     over the ranks (poisson.solve_rows_sharded); every rank still returns every
     field.  Off by default: at 640^2 the solve is latency-bound (two collectives per CG
     iteration), and the replicated single-GPU solve is the faster one."""
     resolutions = list(resolutions)
+    P.check_solver(solver)
     k1 = np.random.uniform(10.0, 11.0)
     k2 = np.random.uniform(10.0, 11.0)
     n_finest = max(resolutions)
@@ -51,7 +54,8 @@ def solve_multi_resolution(n_coarse: int = 40, resolutions: List[int] = (80, 160
         if shard_gt and res == n_finest and _world() > 1:
             data["u"][res] = P.solve_rows_sharded(data["f"][res], data["theta"][res], device=device).cpu().numpy()
         else:
-            data["u"][res] = P.solve_batched(data["f"][res], data["theta"][res], device=device)[0].cpu().numpy()
+            data["u"][res] = P.solve_batched(data["f"][res], data["theta"][res], device=device,
+                                             method=solver)[0].cpu().numpy()
         if verbose:
             print(f"u_{res} - min: {data['u'][res].min():.6f}, max: {data['u'][res].max():.6f}")
     return data

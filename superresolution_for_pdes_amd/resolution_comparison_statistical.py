@@ -75,18 +75,20 @@ def _timed(fn, n_examples: int, device):
 
 
 def solve_multi_resolution(n_examples: int = 1, n_coarse: int = 40, resolutions: Sequence[int] = (80, 160, 320, 640),
-                           k_range=(8.0, 12.0), device="cuda") -> dict:
-    """:25-96 for ``n_examples`` fields at once: draw_fields, then ONE batched CG solve per resolution on the
-    [E, res, res] stack.  data['u' | 'f' | 'theta'][res] are [E, res, res] fp64 device tensors, data['k1'], ['k2']
+                           k_range=(8.0, 12.0), device="cuda", solver: str = "cg") -> dict:
+    """:25-96 for ``n_examples`` fields at once: draw_fields, then ONE batched solve per resolution (``solver``: "cg"
+    or "dst", poisson.solve_batched's method) on the [E, res, res] stack.  data['u' | 'f' | 'theta'][res] are [E, res, res] fp64 device tensors, data['k1'], ['k2']
     length-E arrays, data['solve_times'][res] the HIP-event time of the batched solve divided by E."""
     device = torch.device(device)
+    P.check_solver(solver)
     drawn = draw_fields(n_examples, n_coarse, resolutions, k_range)
     data = {"k1": drawn["k1"], "k2": drawn["k2"], "f": {}, "theta": {}, "u": {}, "solve_times": {}}
     for res in [n_coarse] + list(resolutions):
         data["f"][res] = torch.from_numpy(drawn["f"][res]).to(device)
         data["theta"][res] = torch.from_numpy(drawn["theta"][res]).to(device)
         data["u"][res], data["solve_times"][res] = _timed(
-            lambda: P.solve_batched(data["f"][res], data["theta"][res], device=device), n_examples, device)
+            lambda: P.solve_batched(data["f"][res], data["theta"][res], device=device, method=solver), n_examples,
+            device)
     return data
 
 
@@ -145,7 +147,7 @@ def interpolate_batched(u_start: torch.Tensor, target_resolution: int, mode: str
 
 
 def run_examples(model, n_examples: int = 10, resolutions: Sequence[int] = (80, 160, 320, 640), seed=None,
-                 device="cuda") -> List[Dict]:
+                 device="cuda", solver: str = "cg") -> List[Dict]:
     """run_single_example (:98-205) for ``n_examples`` fields side by side: the list of per-example metric dicts with
     the reference's keys (example, k1, k2, resolutions, {ml, bilinear_multi, bilinear_direct}_{mae, rmse},
     {ml, bilinear_multi, bilinear_direct}_times, solve_times) plus cubic_multi_* / cubic_direct_*.  Every time is
@@ -155,7 +157,7 @@ def run_examples(model, n_examples: int = 10, resolutions: Sequence[int] = (80, 
         np.random.seed(seed)
     device = torch.device(device)
     resolutions = list(resolutions)
-    data = solve_multi_resolution(n_examples, 40, resolutions, device=device)
+    data = solve_multi_resolution(n_examples, 40, resolutions, device=device, solver=solver)
     E = n_examples
     start = data["u"][40]
     cols = {f"{k}_{m}": [] for k, _ in METHODS for m in ("mae", "rmse", "times")}
@@ -242,17 +244,23 @@ def write_summary(all_metrics: List[Dict], save_dir) -> Dict:
     return table
 
 
-def main(argv=None):
-    """CLI of the reference (:501-540) plus ``--seed`` and ``--resolutions``: the summary files go into
-    ``resolution_comparison_statistical_<timestamp>/`` next to the checkpoint.  Returns that directory."""
-    from .compare_methods import load_model
+def arg_parser():
     ap = argparse.ArgumentParser(description="Statistical analysis of upscaling methods")
     ap.add_argument("--model_path", type=str, required=True, help="Path to the model file")
     ap.add_argument("--n_examples", type=int, default=10, help="Number of examples to run")
     ap.add_argument("--seed", type=int, default=None, help="np.random seed of the test fields (reference: unseeded)")
     ap.add_argument("--resolutions", type=int, nargs="+", default=[80, 160, 320, 640],
                     help="Target resolutions (reference: 80 160 320 640)")
-    args = ap.parse_args(argv)
+    ap.add_argument("--solver", choices=("cg", "dst"), default="cg",
+                    help="Ground-truth Poisson solver: conjugate gradients (default) or the direct sine transform")
+    return ap
+
+
+def main(argv=None):
+    """CLI of the reference (:501-540) plus ``--seed``, ``--resolutions`` and ``--solver``: the summary files go into
+    ``resolution_comparison_statistical_<timestamp>/`` next to the checkpoint.  Returns that directory."""
+    from .compare_methods import load_model
+    args = arg_parser().parse_args(argv)
     if not os.path.exists(args.model_path):
         raise FileNotFoundError(f"Model not found at path: {args.model_path}")
     model = load_model(args.model_path, "cuda")
@@ -260,7 +268,7 @@ def main(argv=None):
     stamp = datetime.now().strftime("%Y%m%d_%H%M%S")
     results_dir = os.path.join(os.path.dirname(os.path.abspath(args.model_path)),
                                f"resolution_comparison_statistical_{stamp}")
-    all_metrics = run_examples(model, args.n_examples, args.resolutions, seed=args.seed)
+    all_metrics = run_examples(model, args.n_examples, args.resolutions, seed=args.seed, solver=args.solver)
     write_summary(all_metrics, results_dir)
     print(f"\nResults saved in: {results_dir}")
     return results_dir

@@ -253,12 +253,13 @@ def default_config():
     }
 
 
-def generate_on_device(n_standard=1000, n_subdomain=1000, keep_on_device=True, shard=None):
+def generate_on_device(n_standard=1000, n_subdomain=1000, keep_on_device=True, shard=None, solver="cg"):
     """Config #3: the enhanced_data_generation.py __main__ dataset built by the HIP solver.
     The fields stay device tensors from the batched CG to PDEDataset; under
-    torchrun the solves are sharded over the ranks and all-gathered (8(e)), the draws global."""
+    torchrun the solves are sharded over the ranks and all-gathered (8(e)), the draws global.
+    ``solver``: "cg" or "dst" (poisson.solve_batched's method)."""
     from .enhanced_data_generation import EnhancedPoissonSolver
-    s = EnhancedPoissonSolver(20, 40, 80)
+    s = EnhancedPoissonSolver(20, 40, 80, solver=solver)
     d1 = s.generate_dataset(n_samples=n_standard, k_range=(0.5, 5.0), keep_on_device=keep_on_device, shard=shard)
     d2 = s.generate_subdomain_dataset(n_samples=n_subdomain, k_range=(0.5, 12.0), keep_on_device=keep_on_device,
                                       shard=shard)
@@ -279,7 +280,7 @@ def select(data: dict, idx) -> dict:
     return out
 
 
-def main(argv=None):
+def arg_parser():
     ap = argparse.ArgumentParser(description="MI355X U-Net training (reference train_enhanced.main)")
     ap.add_argument("--data", default="data/pde_dataset.npz")
     ap.add_argument("--generate", type=int, nargs=2, metavar=("N_STD", "N_SUB"), default=None,
@@ -288,7 +289,13 @@ def main(argv=None):
     ap.add_argument("--batch-size", type=int, default=None,
                     help="per-rank batch (under torchrun the global batch is world x batch-size, as torch DDP)")
     ap.add_argument("--results", default="results")
-    args = ap.parse_args(argv)
+    ap.add_argument("--solver", choices=("cg", "dst"), default="cg",
+                    help="Poisson solver of --generate: conjugate gradients (default) or the direct sine transform")
+    return ap
+
+
+def main(argv=None):
+    args = arg_parser().parse_args(argv)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world > 1 and not dist.is_initialized():
@@ -315,7 +322,7 @@ def main(argv=None):
     writer = ScalarWriter(str(save_dir / "tensorboard")) if rank == 0 else None
 
     if args.generate is not None:
-        data = generate_on_device(*args.generate)
+        data = generate_on_device(*args.generate, solver=args.solver)
     else:
         data = dict(np.load(args.data))
     train_idx, val_idx = stratified_split(data, config["val_split"], config["stratify_by_subdomain"])

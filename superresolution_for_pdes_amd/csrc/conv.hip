@@ -1066,11 +1066,9 @@ static int launch_fwd_v2(ConvParams p, hipStream_t st, void* ws, size_t ws_bytes
   const size_t lds = (size_t)2 * (BM + BN) * ROW2;
   // workgroups resident at once (occupancy x CUs), queried once per instantiation
   static int slots = [&] {
-    int per_cu = 0, dev = 0, cus = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    int per_cu = 0;
     (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, conv_fwd_v2_kernel<BM, BN, WM, WN, HP>, 256, lds);
-    return std::max(1, per_cu) * std::max(1, cus);
+    return std::max(1, per_cu) * cu_count();
   }();
   // tail split: when the last round of workgroups would be under half full, cut its tiles
   // into F K-pieces so that round runs on ~F x more CUs for 1/F of the time
@@ -1175,14 +1173,8 @@ int srpde_conv_fwd(const float* x0, int c0, int ldx0, const float* x1, int c1, i
   SRPDE_CHECK_ARG(aligned16(x0) && aligned16(wpack) && (c1 == 0 || aligned16(x1)),
                   "srpde_conv_fwd: inputs must be 16-byte aligned");
   SRPDE_CHECK_ARG((long long)n * h * w < (1LL << 31), "srpde_conv_fwd: too many pixels");
-  ConvParams p;
-  p.x0 = x0; p.c0 = c0; p.ldx0 = ldx0;
-  p.x1 = x1; p.c1 = c1; p.ldx1 = ldx1 > 0 ? ldx1 : 4;
-  p.w = wpack; p.bias = bias; p.y = y; p.ldy = ldy;
-  p.stats = reinterpret_cast<float2*>(stats);
-  p.N = n; p.H = h; p.W = w; p.Cout = cout; p.ksize = ksize; p.dil = dil; p.sign = sign; p.accumulate = accumulate;
-  p.P = n * h * w; p.Cin = c0 + c1; p.K = ksize * ksize * p.Cin;
-  p.ntail = 0; p.tsplit = 1; p.part = nullptr;
+  ConvParams p = make_conv_params(x0, c0, ldx0, x1, c1, ldx1, wpack, bias, y, ldy, stats, n, h, w, cout, ksize, dil, sign,
+                                  accumulate);
   SRPDE_CHECK_ARG(ep_mean == nullptr || (ep_invstd && ep_gamma && ep_beta && !accumulate && stats == nullptr &&
                                          cout % 4 == 0 && !v2_ok(p)),
                   "srpde_conv_fwd: the epilogue BN + ReLU needs mean/invstd/gamma/beta, no accumulate / stats, "

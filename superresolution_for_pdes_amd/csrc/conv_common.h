@@ -650,4 +650,42 @@ static void plan_tail(ConvParams& p, int T, int slots, int BM, int BN, void* ws,
   }
 }
 
+// plan_tail for the h3 kernel families, whose K-pieces are whole 32-channel chunks -> the launch's
+// workgroups (whole tiles plus the tail's pieces)
+static int plan_tail_chunks(ConvParams& p, int T, int slots, int BM, int BN, void* ws, size_t ws_bytes) {
+  plan_tail(p, T, slots, BM, BN, ws, ws_bytes);
+  const int nch = p.Cin / BK2;
+  if (p.ntail > 0 && p.tsplit > nch) p.tsplit = nch;
+  if (p.tsplit < 2) { p.ntail = 0; p.tsplit = 1; }
+  return T - p.ntail + p.ntail * p.tsplit;
+}
+
+// CUs of the device (current when first asked), at least 1; static like plan_tail: the library exports no
+// symbol for it
+static int cu_count() {
+  static const int cus = [] {
+    int dev = 0, c = 0;
+    (void)hipGetDevice(&dev);
+    (void)hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev);
+    return std::max(1, c);
+  }();
+  return cus;
+}
+
+// the tensor, shape and sign fields of a conv entry's parameter block; no tail split (plan_tail), no fused
+// BN reduction / epilogue (the struct's defaults)
+static ConvParams make_conv_params(const float* x0, int c0, int ldx0, const float* x1, int c1, int ldx1, const float* w,
+                                   const float* bias, float* y, int ldy, float* stats, int n, int h, int wd, int cout,
+                                   int ksize, int dil, int sign, int accumulate) {
+  ConvParams p;
+  p.x0 = x0; p.c0 = c0; p.ldx0 = ldx0;
+  p.x1 = x1; p.c1 = c1; p.ldx1 = ldx1 > 0 ? ldx1 : 4;
+  p.w = w; p.bias = bias; p.y = y; p.ldy = ldy;
+  p.stats = reinterpret_cast<float2*>(stats);
+  p.N = n; p.H = h; p.W = wd; p.Cout = cout; p.ksize = ksize; p.dil = dil; p.sign = sign; p.accumulate = accumulate;
+  p.P = n * h * wd; p.Cin = c0 + c1; p.K = ksize * ksize * p.Cin;
+  p.ntail = 0; p.tsplit = 1; p.part = nullptr;
+  return p;
+}
+
 }  // namespace srpde

@@ -2079,19 +2079,9 @@ static int launch_fwd_h3(ConvParams p, H3Args h, hipStream_t st, void* ws, size_
   const int T = nbm * nbn;
   const size_t lds = h3_lds(BN, h.arows, TPS, BNB, PRE);
   if ((size_t)h.arows * ROW2 < (size_t)(2 * WM * BN + WM * WN * 512) * 4) h.wide = 0;   // F too small to stage
-  static const int cus = [] {
-    int dev = 0, c = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev);
-    return std::max(1, c);
-  }();
   // resident workgroups: by waves (8 per CU) and by LDS
-  const int slots = cus * std::max(1, std::min(8 / (WM * WN), (int)((160 * 1024) / lds)));
-  plan_tail(p, T, slots, BM, BN, ws, ws_bytes);
-  const int nch = p.Cin / BK2;
-  if (p.ntail > 0 && p.tsplit > nch) p.tsplit = nch;   // pieces are whole channel chunks
-  if (p.tsplit < 2) { p.ntail = 0; p.tsplit = 1; }
-  const int grid = T - p.ntail + p.ntail * p.tsplit;
+  const int slots = cu_count() * std::max(1, std::min(8 / (WM * WN), (int)((160 * 1024) / lds)));
+  const int grid = plan_tail_chunks(p, T, slots, BM, BN, ws, ws_bytes);
   note_kernel("conv_fwd_h3_kernel<%d, %d, %d, %d, %d, %s, %d, %s, %s>", BM, BN, WM, WN, SRB, TWO_LEVEL ? "true" : "false",
               TPS, BNB ? "true" : "false", PRE ? "true" : "false");
   hipLaunchKernelGGL((conv_fwd_h3_kernel<BM, BN, WM, WN, SRB, TWO_LEVEL, TPS, BNB, PRE>), dim3(grid), dim3(NT), lds, st,
@@ -2121,17 +2111,7 @@ static int launch_fwd_h3r(ConvParams p, H3Args h, hipStream_t st, void* ws, size
   const int T = nbm * nbn;
   const size_t lds = h3r_lds(BN, h.arows, TPS);
   if ((size_t)h.arows * 128 < (size_t)(2 * WM * 2 * BN + WM * 512) * 4) h.wide = 0;   // S too small to stage
-  static int slots = [&] {
-    int dev = 0, cus = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    return std::max(1, cus) * 2;   // resident workgroups: two per CU
-  }();
-  plan_tail(p, T, slots, BM, BN, ws, ws_bytes);
-  const int nch = p.Cin / BK2;
-  if (p.ntail > 0 && p.tsplit > nch) p.tsplit = nch;
-  if (p.tsplit < 2) { p.ntail = 0; p.tsplit = 1; }
-  const int grid = T - p.ntail + p.ntail * p.tsplit;
+  const int grid = plan_tail_chunks(p, T, 2 * cu_count(), BM, BN, ws, ws_bytes);   // two workgroups per CU
   note_kernel("conv_fwd_h3r_kernel<%d, %d, %d, %d, %s>", BN, TPS, H3R_NTK, H3R_NB, PRE ? "true" : "false");
   hipLaunchKernelGGL((conv_fwd_h3r_kernel<BN, TPS, H3R_NTK, H3R_NB, PRE>), dim3(grid), dim3(256), lds, st, p, h);
   SRPDE_LAUNCH_CHECK("srpde_conv_fwd_h3(h3r)");
@@ -2189,7 +2169,7 @@ static bool h3g_ok(int cout, int K, int cin, int w, int dil) {
 void h3p_split(int P, int cout, int K, int w, int* chunk, int* splits) {
   int bm, bn;
   h3p_tiles(cout, K, &bm, &bn);
-  const bool g = h3g_ok(cout, K, K / 9, w, 1);
+  const bool g = h3g_ok(cout, K, K / 9, w, 1);   // dil hard-wired to 1: ADVICE.md (left for a fix)
   if (g) { bm = 128; bn = 288; }
   const long long tiles = (long long)ceil_div(cout, bm) * ceil_div(K, bn);
   // one workgroup per CU (LDS): ~2 rounds of 256 CUs, chunks a multiple of the 32-pixel stage.
@@ -2256,6 +2236,81 @@ static int launch_h3p(const WgradParams& p, const H3P& q, hipStream_t st) {
   return 0;
 }
 
+// the 8-wave kernel of a column tile (cfg: h3_cfg) and taps per stage: exactly the instantiations that are built
+// (BNB: one tap per stage and no 128-column tile, see srpde_conv_dgrad_h3_bnb)
+template <int BN, bool BNB, bool PRE>
+static int launch_h3_tps(int tps, const ConvParams& p, const H3Args& a, hipStream_t st, void* ws, size_t ws_bytes) {
+  if constexpr (!BNB)
+    if (tps == 2) return launch_fwd_h3<256, BN, 8, 1, H3_SRB, true, 2, BNB, PRE>(p, a, st, ws, ws_bytes);
+  return launch_fwd_h3<256, BN, 8, 1, H3_SRB, true, 1, BNB, PRE>(p, a, st, ws, ws_bytes);
+}
+template <bool BNB, bool PRE>
+static int launch_h3_tile(int cfg, int tps, const ConvParams& p, const H3Args& a, hipStream_t st, void* ws,
+                          size_t ws_bytes) {
+  if constexpr (!BNB)
+    if (cfg == 1) return launch_h3_tps<128, BNB, PRE>(tps, p, a, st, ws, ws_bytes);
+  return cfg == 2 ? launch_h3_tps<64, BNB, PRE>(tps, p, a, st, ws, ws_bytes)
+                  : launch_h3_tps<32, BNB, PRE>(tps, p, a, st, ws, ws_bytes);
+}
+template <bool PRE>
+static int launch_h3r_tile(int cfg, const ConvParams& p, const H3Args& a, hipStream_t st, void* ws, size_t ws_bytes) {
+  return cfg == 2 ? launch_fwd_h3r<64, 1, PRE>(p, a, st, ws, ws_bytes) : launch_fwd_h3r<32, 1, PRE>(p, a, st, ws, ws_bytes);
+}
+
+// the fused BN-backward reduction over an entry's output (ConvParams::bn_*) and its per-tile max|out| slots
+static int set_bn_reduction(ConvParams& p, const float* bn_y, int bn_ldy, const float* mean, const float* invstd,
+                            const float* gamma, const float* beta, void* bn_part, float* out_max, const char* entry) {
+  SRPDE_CHECK_ARG(bn_part == nullptr || (bn_y && mean && invstd && gamma && beta && !p.accumulate && bn_ldy % 4 == 0 &&
+                                          p.Cout % 4 == 0),
+                  "%s: the fused BN reduction needs bn_y/mean/invstd/gamma/beta, bn_ldy and the output channels "
+                  "multiples of 4, and no accumulate", entry);
+  p.bn_y = bn_y; p.bn_ldy = bn_ldy; p.bn_mean = mean; p.bn_invstd = invstd;
+  p.bn_gamma = gamma; p.bn_beta = beta; p.bn_part = static_cast<float2*>(bn_part);
+  p.out_max = out_max;
+  return 0;
+}
+
+// the kernel arguments every h3 entry sets the same way (y: the output view); the optional ones stay null
+static H3Args make_h3_args(const void* wsplit, const int* wexp, const unsigned* amax0, const unsigned* amax1, int w,
+                           int dil, const float* y, int ldy) {
+  H3Args a{};
+  a.wsp = static_cast<const _Float16*>(wsplit);
+  a.wexp = wexp;
+  a.amax0 = amax0;
+  a.amax1 = amax1;
+  a.halo = (w + 1) * dil;
+  a.arows = h3_arows(w, dil);
+  a.relax = 1;   // a stage waits only for its weight DMA; the halo slices land later
+  a.wide = ldy % 4 == 0 && aligned16(y);
+  return a;
+}
+
+// the parameter block of the split-reading weight gradients (srpde_conv_wgrad_h3p / _h3x): no fp32 dy -- its
+// planes hold cout rounded up to the 32-channel chunk (srpde_bn_bwd_apply_split's padding; the padded rows are
+// zero-filled by the DMA range check, their products never stored) --, x0 / x1 the fp32 input rows (h3x) or
+// null with the planes' row stride (h3p)
+static WgradParams make_h3p_params(const float* x0, int c0, int ldx0, const float* x1, int c1, int ldx1, int n, int h,
+                                   int w, int cout, int ksize, int dil) {
+  WgradParams p;
+  p.dy = nullptr; p.lddy = (cout + 31) / 32 * 32; p.x0 = x0; p.c0 = c0; p.ldx0 = ldx0; p.x1 = x1; p.c1 = c1;
+  p.ldx1 = ldx1;
+  p.N = n; p.H = h; p.W = w; p.Cout = cout; p.ksize = ksize; p.dil = dil;
+  p.P = n * h * w; p.Cin = c0 + c1; p.K = ksize * ksize * p.Cin;
+  return p;
+}
+
+// the split-K plan and its slabs in the caller's workspace
+static int set_h3p_split(WgradParams& p, void* workspace, size_t ws_bytes, const char* entry) {
+  h3p_split(p.P, p.Cout, p.K, p.W, &p.chunk, &p.splits);
+  const size_t need = (size_t)p.splits * p.Cout * p.K * sizeof(float);
+  if (ws_bytes < need) {
+    set_error("%s: workspace %zu < %zu bytes", entry, ws_bytes, need);
+    return kErrWorkspace;
+  }
+  p.part = static_cast<float*>(workspace);
+  return 0;
+}
+
 }  // namespace srpde
 
 using namespace srpde;
@@ -2276,22 +2331,10 @@ int srpde_conv_wgrad_h3p(const void* dyp, const unsigned* amax_dy, const void* x
   SRPDE_CHECK_ARG(cout % 16 == 0 && (c0 + c1) % 8 == 0 && ksize == 3 && cin_real <= c0 + c1,
                   "srpde_conv_wgrad_h3p: needs cout %% 16 == 0, cin %% 8 == 0, ksize 3 (cout=%d cin=%d)", cout, c0 + c1);
   SRPDE_CHECK_ARG(aligned16(dyp) && aligned16(xp), "srpde_conv_wgrad_h3p: planes must be 16-byte aligned");
-  WgradParams p;
-  // dyp planes hold cout rounded up to the 32-channel chunk (srpde_bn_bwd_apply_split's padding); rows of
-  // dw: cout (the padded rows are zero-filled by the DMA range check, their products never stored)
-  p.dy = nullptr; p.lddy = (cout + 31) / 32 * 32; p.x0 = nullptr; p.c0 = c0; p.ldx0 = c0 + c1; p.x1 = nullptr; p.c1 = c1;
-  p.ldx1 = c0 + c1;
-  p.N = n; p.H = h; p.W = w; p.Cout = cout; p.ksize = ksize; p.dil = dil;
-  p.P = n * h * w; p.Cin = c0 + c1; p.K = ksize * ksize * p.Cin;
+  WgradParams p = make_h3p_params(nullptr, c0, c0 + c1, nullptr, c1, c0 + c1, n, h, w, cout, ksize, dil);
   // the dy planes' row stride is cout rounded up to 32 (p.lddy): the bound is on that width
   SRPDE_CHECK_ARG(2LL * p.P * std::max(p.lddy, p.Cin) * 2 < (1LL << 31), "srpde_conv_wgrad_h3p: tensor too large");
-  h3p_split(p.P, cout, p.K, w, &p.chunk, &p.splits);
-  const size_t need = (size_t)p.splits * cout * p.K * sizeof(float);
-  if (ws_bytes < need) {
-    set_error("srpde_conv_wgrad_h3p: workspace %zu < %zu bytes", ws_bytes, need);
-    return kErrWorkspace;
-  }
-  p.part = static_cast<float*>(workspace);
+  if (const int rc = set_h3p_split(p, workspace, ws_bytes, "srpde_conv_wgrad_h3p")) return rc;
   const H3P q{static_cast<const _Float16*>(dyp), static_cast<const _Float16*>(xp), amax_dy, amax0, c1 ? amax1 : amax0};
   int rc;
   if (h3g_ok(cout, p.K, p.Cin, w, dil)) rc = launch_h3g<20, 1>(p, q, stream);
@@ -2331,20 +2374,10 @@ int srpde_conv_wgrad_h3x(const void* dyp, const unsigned* amax_dy, const float* 
                       (in_scale == nullptr || (aligned16(in_scale) && aligned16(in_shift))) &&
                       (x1_ca == nullptr || aligned16(x1_ca)),
                   "srpde_conv_wgrad_h3x: 16-byte aligned operands, row strides multiples of 4");
-  WgradParams p;
-  p.dy = nullptr; p.lddy = (cout + 31) / 32 * 32; p.x0 = x0; p.c0 = c0; p.ldx0 = ldx0; p.x1 = x1; p.c1 = c1;
-  p.ldx1 = ldx1;
-  p.N = n; p.H = h; p.W = w; p.Cout = cout; p.ksize = ksize; p.dil = dil;
-  p.P = n * h * w; p.Cin = c0 + c1; p.K = ksize * ksize * p.Cin;
+  WgradParams p = make_h3p_params(x0, c0, ldx0, x1, c1, ldx1, n, h, w, cout, ksize, dil);
   SRPDE_CHECK_ARG(2LL * p.P * p.lddy * 2 < (1LL << 31) && (long long)p.P * std::max(ldx0, ldx1) < (1LL << 31),
                   "srpde_conv_wgrad_h3x: tensor too large");
-  h3p_split(p.P, cout, p.K, w, &p.chunk, &p.splits);
-  const size_t need = (size_t)p.splits * cout * p.K * sizeof(float);
-  if (ws_bytes < need) {
-    set_error("srpde_conv_wgrad_h3x: workspace %zu < %zu bytes", ws_bytes, need);
-    return kErrWorkspace;
-  }
-  p.part = static_cast<float*>(workspace);
+  if (const int rc = set_h3p_split(p, workspace, ws_bytes, "srpde_conv_wgrad_h3x")) return rc;
   const H3P q{static_cast<const _Float16*>(dyp), nullptr, amax_dy, amax0, c1 ? amax1 : amax0, in_scale, in_shift,
               x1_ca, x1_sa};
   int rc;
@@ -2353,15 +2386,6 @@ int srpde_conv_wgrad_h3x(const void* dyp, const unsigned* amax_dy, const float* 
   if (rc) return rc;
   return wgrad_reduce(p.part, dw, p.splits, cout, p.Cin, cin_real, ksize * ksize, accumulate, stream);
 }
-
-}  // extern "C"
-
-namespace srpde {
-}  // namespace srpde
-
-using namespace srpde;
-
-extern "C" {
 
 int srpde_conv_h3_stats_rows(void) { return H3_SRB; }
 
@@ -2434,25 +2458,12 @@ int srpde_conv_fwd_h3(const float* x0, int c0, int ldx0, const float* x1, int c1
   SRPDE_CHECK_ARG(ldx0 % 4 == 0 && (c1 == 0 || ldx1 % 4 == 0), "srpde_conv_fwd_h3: strides must be multiples of 4");
   SRPDE_CHECK_ARG(aligned16(x0) && aligned16(wsplit) && (c1 == 0 || aligned16(x1)),
                   "srpde_conv_fwd_h3: inputs must be 16-byte aligned");
-  ConvParams p;
-  p.x0 = x0; p.c0 = c0; p.ldx0 = ldx0;
-  p.x1 = x1; p.c1 = c1; p.ldx1 = ldx1 > 0 ? ldx1 : 4;
-  p.w = nullptr; p.bias = bias; p.y = y; p.ldy = ldy;
-  p.stats = reinterpret_cast<float2*>(stats);
-  p.N = n; p.H = h; p.W = w; p.Cout = cout; p.ksize = ksize; p.dil = dil; p.sign = sign; p.accumulate = accumulate;
-  p.P = n * h * w; p.Cin = c0 + c1; p.K = ksize * ksize * p.Cin;
-  p.ntail = 0; p.tsplit = 1; p.part = nullptr;
+  ConvParams p = make_conv_params(x0, c0, ldx0, x1, c1, ldx1, nullptr, bias, y, ldy, stats, n, h, w, cout, ksize, dil,
+                                  sign, accumulate);
   const long long maxld = std::max(ldx0, c1 ? ldx1 : 0);
   SRPDE_CHECK_ARG((long long)p.P * maxld * 4 < (1LL << 31) && 2LL * cout * p.K * 2 < (1LL << 31),
                   "srpde_conv_fwd_h3: tensor too large");
-  H3Args a{};
-  a.wsp = static_cast<const _Float16*>(wsplit);
-  a.wexp = wexp;
-  a.amax0 = amax0;
-  a.amax1 = c1 ? amax1 : nullptr;
-  a.halo = (w + 1) * dil;
-  a.arows = h3_arows(w, dil);
-  a.relax = 1;   // a stage waits only for its weight DMA; the halo slices land later
+  H3Args a = make_h3_args(wsplit, wexp, amax0, c1 ? amax1 : nullptr, w, dil, y, ldy);
   a.xsplit = static_cast<_Float16*>(xsplit_out);
   SRPDE_CHECK_ARG((in_scale == nullptr) == (in_shift == nullptr) && (in_scale == nullptr || c1 == 0),
                   "srpde_conv_fwd_h3: in_scale / in_shift go together and need c1 == 0");
@@ -2462,13 +2473,9 @@ int srpde_conv_fwd_h3(const float* x0, int c0, int ldx0, const float* x1, int c1
   a.x1_sa = x1_sa;
   a.up_src = x0_up;
   a.up_ld = up_ld; a.up_h = up_h; a.up_w = up_w;
-  a.wide = ldy % 4 == 0 && aligned16(y);
-  SRPDE_CHECK_ARG(bn_part == nullptr || (bn_y && bn_mean && bn_invstd && bn_gamma && bn_beta && !accumulate &&
-                                          bn_ldy % 4 == 0 && cout % 4 == 0),
-                  "srpde_conv_fwd_h3: the fused BN reduction needs bn_y/mean/invstd/gamma/beta and no accumulate");
-  p.bn_y = bn_y; p.bn_ldy = bn_ldy; p.bn_mean = bn_mean; p.bn_invstd = bn_invstd;
-  p.bn_gamma = bn_gamma; p.bn_beta = bn_beta; p.bn_part = static_cast<float2*>(bn_part);
-  p.out_max = out_max;
+  if (const int rc = set_bn_reduction(p, bn_y, bn_ldy, bn_mean, bn_invstd, bn_gamma, bn_beta, bn_part, out_max,
+                                      "srpde_conv_fwd_h3"))
+    return rc;
   SRPDE_CHECK_ARG(xsplit_out == nullptr || aligned16(xsplit_out), "srpde_conv_fwd_h3: xsplit_out must be 16-byte aligned");
   SRPDE_CHECK_ARG(ep_mean == nullptr || (ep_invstd && ep_gamma && ep_beta && !accumulate && stats == nullptr &&
                                          bn_part == nullptr && cout % 4 == 0),
@@ -2497,20 +2504,9 @@ int srpde_conv_fwd_h3(const float* x0, int c0, int ldx0, const float* x1, int c1
                   "blocks would not be the srpde_conv_h3_stats_rows_for ones", cout);
   if (x0_up != nullptr || (h4ok && h4_supported(w, dil, cout, false)))
     return launch_fwd_h4(p, a, false, stream, workspace, ws_bytes);
-  if (h3r_fits(h3_bn(h3_cfg(cout)), a.arows, fam)) {
-    if (h3_cfg(cout) == 2) return launch_fwd_h3r<64, 1>(p, a, stream, workspace, ws_bytes);
-    return launch_fwd_h3r<32, 1>(p, a, stream, workspace, ws_bytes);
-  }
-  const int tps = h3_tps(h3_bn(h3_cfg(cout)), a.arows);
-#define H3_LAUNCH(BN_)                                                                        \
-  (tps == 2 ? launch_fwd_h3<256, BN_, 8, 1, H3_SRB, true, 2>(p, a, stream, workspace, ws_bytes) \
-            : launch_fwd_h3<256, BN_, 8, 1, H3_SRB, true, 1>(p, a, stream, workspace, ws_bytes))
-  switch (h3_cfg(cout)) {
-    case 1: return H3_LAUNCH(128);
-    case 2: return H3_LAUNCH(64);
-    default: return H3_LAUNCH(32);
-  }
-#undef H3_LAUNCH
+  const int cfg = h3_cfg(cout), bn = h3_bn(cfg);
+  if (h3r_fits(bn, a.arows, fam)) return launch_h3r_tile<false>(cfg, p, a, stream, workspace, ws_bytes);
+  return launch_h3_tile<false, false>(cfg, h3_tps(bn, a.arows), p, a, stream, workspace, ws_bytes);
 }
 
 // srpde_conv_fwd_h3 on an input that arrives as its h3 split (planes [2][P][c] fp16 hi / lo of
@@ -2531,52 +2527,22 @@ int srpde_conv_fwd_h3_presplit(const void* xsplit, int c, const unsigned* amax, 
   SRPDE_CHECK_ARG(srpde_conv_h3_supported(c, 0, cout, w, dil, ksize),
                   "srpde_conv_fwd_h3_presplit: unsupported shape (c=%d cout=%d w=%d dil=%d)", c, cout, w, dil);
   SRPDE_CHECK_ARG(aligned16(xsplit) && aligned16(wsplit), "srpde_conv_fwd_h3_presplit: 16-byte alignment");
-  ConvParams p;
-  p.x0 = static_cast<const float*>(xsplit); p.c0 = c; p.ldx0 = c;   // [2][P][c] fp16 == P * c floats of bytes
-  p.x1 = nullptr; p.c1 = 0; p.ldx1 = 4;
-  p.w = nullptr; p.bias = bias; p.y = y; p.ldy = ldy;
-  p.stats = reinterpret_cast<float2*>(stats);
-  p.N = n; p.H = h; p.W = w; p.Cout = cout; p.ksize = ksize; p.dil = dil; p.sign = sign; p.accumulate = accumulate;
-  p.P = n * h * w; p.Cin = c; p.K = ksize * ksize * c;
-  p.ntail = 0; p.tsplit = 1; p.part = nullptr;
+  // the planes as the x0 view: [2][P][c] fp16 == P * c floats of bytes
+  ConvParams p = make_conv_params(static_cast<const float*>(xsplit), c, c, nullptr, 0, 0, nullptr, bias, y, ldy, stats, n,
+                                  h, w, cout, ksize, dil, sign, accumulate);
   SRPDE_CHECK_ARG((long long)p.P * c * 4 < (1LL << 31) && 2LL * cout * p.K * 2 < (1LL << 31),
                   "srpde_conv_fwd_h3_presplit: tensor too large");
-  SRPDE_CHECK_ARG(bn_part == nullptr || (bn_y && bn_mean && bn_invstd && bn_gamma && bn_beta && !accumulate &&
-                                          bn_ldy % 4 == 0 && cout % 4 == 0),
-                  "srpde_conv_fwd_h3_presplit: the fused BN reduction needs bn_y/mean/invstd/gamma/beta, no accumulate");
-  p.bn_y = bn_y; p.bn_ldy = bn_ldy; p.bn_mean = bn_mean; p.bn_invstd = bn_invstd;
-  p.bn_gamma = bn_gamma; p.bn_beta = bn_beta; p.bn_part = static_cast<float2*>(bn_part);
-  p.out_max = out_max;
-  H3Args a{};
-  a.wsp = static_cast<const _Float16*>(wsplit);
-  a.wexp = wexp;
-  a.amax0 = amax;
-  a.amax1 = nullptr;
-  a.halo = (w + 1) * dil;
-  a.arows = h3_arows(w, dil);
-  a.relax = 1;
-  a.xsplit = nullptr;
-  a.in_scale = nullptr; a.in_shift = nullptr;
-  a.wide = ldy % 4 == 0 && aligned16(y);
+  if (const int rc = set_bn_reduction(p, bn_y, bn_ldy, bn_mean, bn_invstd, bn_gamma, bn_beta, bn_part, out_max,
+                                      "srpde_conv_fwd_h3_presplit"))
+    return rc;
+  const H3Args a = make_h3_args(wsplit, wexp, amax, nullptr, w, dil, y, ldy);
   if (!(fam & FAM_NO_H4) && h4_supported(w, dil, cout, false))
     return launch_fwd_h4(p, a, true, stream, workspace, ws_bytes);
-  if (h3r_fits(h3_bn(h3_cfg(cout)), a.arows, fam)) {
-    if (h3_cfg(cout) == 2) return launch_fwd_h3r<64, 1, true>(p, a, stream, workspace, ws_bytes);
-    return launch_fwd_h3r<32, 1, true>(p, a, stream, workspace, ws_bytes);
-  }
-  const int bn = h3_bn(h3_cfg(cout));
+  const int cfg = h3_cfg(cout), bn = h3_bn(cfg);
+  if (h3r_fits(bn, a.arows, fam)) return launch_h3r_tile<true>(cfg, p, a, stream, workspace, ws_bytes);
   SRPDE_CHECK_ARG(h3_lds(bn, a.arows, 1, false, true) <= 160 * 1024, "srpde_conv_fwd_h3_presplit: LDS (w=%d dil=%d)", w,
                   dil);
-  const int tps = h3_tps(bn, a.arows, true);
-#define H3P_LAUNCH(BN_)                                                                                   \
-  (tps == 2 ? launch_fwd_h3<256, BN_, 8, 1, H3_SRB, true, 2, false, true>(p, a, stream, workspace, ws_bytes) \
-            : launch_fwd_h3<256, BN_, 8, 1, H3_SRB, true, 1, false, true>(p, a, stream, workspace, ws_bytes))
-  switch (h3_cfg(cout)) {
-    case 1: return H3P_LAUNCH(128);
-    case 2: return H3P_LAUNCH(64);
-    default: return H3P_LAUNCH(32);
-  }
-#undef H3P_LAUNCH
+  return launch_h3_tile<false, true>(cfg, h3_tps(bn, a.arows, true), p, a, stream, workspace, ws_bytes);
 }
 
 // dgrad with the BatchNorm (+ReLU) backward apply fused into the operand transform (BNB kernels):
@@ -2599,44 +2565,26 @@ int srpde_conv_dgrad_h3_bnb(const float* da, int ldda, const unsigned* dy_amax, 
                   dil);
   SRPDE_CHECK_ARG(ldda % 4 == 0 && bn_ldy_in % 4 == 0 && aligned16(da) && aligned16(bn_y_in) && aligned16(wsplit) &&
                   aligned16(dysplit_out), "srpde_conv_dgrad_h3_bnb: 16-byte alignment / ld % 4");
-  ConvParams p;
-  p.x0 = da; p.c0 = cout_dy; p.ldx0 = ldda;
-  p.x1 = nullptr; p.c1 = 0; p.ldx1 = 4;
-  p.w = nullptr; p.bias = nullptr; p.y = dx; p.ldy = lddx;
-  p.stats = nullptr;
-  p.N = n; p.H = h; p.W = w; p.Cout = cin_dx; p.ksize = 3; p.dil = dil; p.sign = -1; p.accumulate = 0;
-  p.P = n * h * w; p.Cin = cout_dy; p.K = 9 * p.Cin;
-  p.ntail = 0; p.tsplit = 1; p.part = nullptr;
+  ConvParams p = make_conv_params(da, cout_dy, ldda, nullptr, 0, 0, nullptr, nullptr, dx, lddx, nullptr, n, h, w, cin_dx,
+                                  3, dil, -1, 0);
   SRPDE_CHECK_ARG((long long)p.P * std::max(ldda, bn_ldy_in) * 4 < (1LL << 31) && 2LL * cin_dx * p.K * 2 < (1LL << 31),
                   "srpde_conv_dgrad_h3_bnb: tensor too large");
-  SRPDE_CHECK_ARG(bn_part == nullptr || (bn_y && bn_mean && bn_invstd && bn_gamma && bn_beta && bn_ldy % 4 == 0 &&
-                                          cin_dx % 4 == 0), "srpde_conv_dgrad_h3_bnb: bad fused-reduction arguments");
-  p.bn_y = bn_y; p.bn_ldy = bn_ldy; p.bn_mean = bn_mean; p.bn_invstd = bn_invstd;
-  p.bn_gamma = bn_gamma; p.bn_beta = bn_beta; p.bn_part = static_cast<float2*>(bn_part);
-  p.out_max = dx_max;
-  H3Args a{};
-  a.wsp = static_cast<const _Float16*>(wsplit);
-  a.wexp = wexp;
-  a.amax0 = dy_amax;
-  a.amax1 = nullptr;
-  a.halo = (w + 1) * dil;
-  a.arows = h3_arows(w, dil);
-  a.relax = 1;
+  if (const int rc = set_bn_reduction(p, bn_y, bn_ldy, bn_mean, bn_invstd, bn_gamma, bn_beta, bn_part, dx_max,
+                                      "srpde_conv_dgrad_h3_bnb"))
+    return rc;
+  H3Args a = make_h3_args(wsplit, wexp, dy_amax, nullptr, w, dil, dx, lddx);
   a.xsplit = static_cast<_Float16*>(dysplit_out);
-  a.in_scale = nullptr; a.in_shift = nullptr;
-  a.wide = lddx % 4 == 0 && aligned16(dx);
   a.bnb_y = bn_y_in; a.bnb_ldy = bn_ldy_in;
   a.bnb_mean = mean; a.bnb_invstd = invstd; a.bnb_gamma = gamma; a.bnb_beta = beta;
   a.bnb_m1 = m1; a.bnb_m2 = m2;
   a.bnb_relu = flags & 1;
-  const int bn = h3_bn(h3_cfg(cin_dx));
-  SRPDE_CHECK_ARG(h3_lds(bn, a.arows, 1, true) <= 160 * 1024, "srpde_conv_dgrad_h3_bnb: LDS (w=%d dil=%d)", w, dil);
-  SRPDE_CHECK_ARG(h3_cfg(cin_dx) != 1, "srpde_conv_dgrad_h3_bnb: 128-column tiles not provided (cin_dx=%d)", cin_dx);
+  const int cfg = h3_cfg(cin_dx);
+  SRPDE_CHECK_ARG(h3_lds(h3_bn(cfg), a.arows, 1, true) <= 160 * 1024, "srpde_conv_dgrad_h3_bnb: LDS (w=%d dil=%d)", w, dil);
+  SRPDE_CHECK_ARG(cfg != 1, "srpde_conv_dgrad_h3_bnb: 128-column tiles not provided (cin_dx=%d)", cin_dx);
   // one tap per stage: the second fp32 halo tile takes the second weight stage's LDS.  (The
   // 128-column tile does not fit its registers with the fused transform -- 46 VGPRs of scratch --
   // so outputs with a multiple of 128 channels keep srpde_bn_relu_bwd + srpde_conv_fwd_h3.)
-  if (h3_cfg(cin_dx) == 2) return launch_fwd_h3<256, 64, 8, 1, H3_SRB, true, 1, true>(p, a, stream, workspace, ws_bytes);
-  return launch_fwd_h3<256, 32, 8, 1, H3_SRB, true, 1, true>(p, a, stream, workspace, ws_bytes);
+  return launch_h3_tile<true, false>(cfg, 1, p, a, stream, workspace, ws_bytes);
 }
 
 // Number of output tiles (= out_max slots) srpde_conv_fwd_h3 uses for this shape; 0 if unsupported.

@@ -667,19 +667,10 @@ static int launch_h4_cfg(ConvParams p, H3Args h, hipStream_t st, void* ws, size_
   using G = H4Geom<W, DIL, BN_>;
   constexpr int BM = G::BM, BN = G::BN;
   const int T = ceil_div(p.P, BM) * (p.Cout / BN);
-  static const int cus = [] {
-    int dev = 0, c = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev);
-    return std::max(1, c);
-  }();
-  plan_tail(p, T, cus, BM, BN, ws, ws_bytes);   // one workgroup per CU (LDS)
-  const int nch = p.Cin / BK2;
-  if (p.ntail > 0 && p.tsplit > nch) p.tsplit = nch;
-  if (p.tsplit < 2) { p.ntail = 0; p.tsplit = 1; }
+  const int cus = cu_count();
+  const int nitems = plan_tail_chunks(p, T, cus, BM, BN, ws, ws_bytes);   // one workgroup per CU (LDS)
   // persistent: one workgroup per CU (LDS), each running items b, b + grid, ... (whole tiles, then the
   // K-pieces of the split tail)
-  const int nitems = T - p.ntail + p.ntail * p.tsplit;
   const int grid = G::PERSIST ? std::min(nitems, cus) : nitems;
   note_kernel("conv_fwd_h4_kernel<%d, %d, %d, %d, %s, %s>", W, DIL, BN, SIGN, PRE ? "true" : "false", UP ? "true" : "false");
   hipLaunchKernelGGL((conv_fwd_h4_kernel<W, DIL, BN, SIGN, PRE, UP>), dim3(grid), dim3(512), G::template lds<PRE>(), st,

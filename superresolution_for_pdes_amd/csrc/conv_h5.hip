@@ -697,14 +697,8 @@ static int launch_h5_ncb(const ConvParams& p, const H3Args& h, int grid, hipStre
 }
 
 int launch_fwd_h5(const ConvParams& p, const H3Args& h, hipStream_t st) {
-  static const int cus = [] {
-    int dev = 0, c = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev);
-    return std::max(1, c);
-  }();
   const int ntiles = p.N * (p.H / kTR);
-  const int grid = std::min(ntiles, cus);
+  const int grid = std::min(ntiles, cu_count());
   const int rc = p.Cout == 64 ? launch_h5_ncb<2>(p, h, grid, st) : launch_h5_ncb<1>(p, h, grid, st);
   if (rc != 0) return rc;
   SRPDE_LAUNCH_CHECK("srpde_conv_fwd_h3(h5)");

@@ -27,6 +27,11 @@ def _p(t):
     return 0 if t is None else t.data_ptr()
 
 
+def _pl_opt(t):
+    """(pointer, ld, channels) of an optional second input (a virtual concat's x1); zeros when absent."""
+    return (0, 0, 0) if t is None else (*_pl(t), t.shape[1])
+
+
 def empty(*shape, device):
     return torch.empty(*shape, dtype=F32, device=device)
 
@@ -65,6 +70,28 @@ def _conv_call(name, flop, *args):
 
 def conv_math() -> str:
     return _CONV_MATH
+
+
+def _conv_flop(cout, cin, ksize, n, h, w):
+    """algorithmic FLOP of a convolution, its input gradient or its weight gradient (LAUNCH_TAP)"""
+    return 2.0 * cout * cin * ksize * ksize * n * h * w
+
+
+def _check_rows(buf, rows, what):
+    """A statistics / partials buffer (None: nothing to check) must hold blocks of ``rows`` rows (None: the h3
+    kernels' srpde_conv_h3_stats_rows)."""
+    if buf is None:
+        return
+    if rows is None:
+        rows = int(query("srpde_conv_h3_stats_rows"))
+    if getattr(buf, "_srpde_rows", None) != rows:
+        raise ValueError(f"statistics buffer not laid out for {what}")
+
+
+def _wgrad_workspace(query_name, n, h, w, cout, cin, ksize, device):
+    """The split-K slabs of a weight gradient -> (uint8 buffer, the byte count its entry is told)."""
+    ws_bytes = int(query(query_name, n, h, w, cout, cin, ksize))
+    return torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=device), ws_bytes
 
 
 def split_weights_h3(wpack, rows):
@@ -235,30 +262,26 @@ def conv_fwd(x0, x1, wpack, bias, y, n, h, w, cout, ksize=3, dil=1, sign=1, accu
         x0 = up.materialize()
         up = None
     p0, ld0 = _pl(x0.x if up is not None else x0)
-    if x1 is not None:
-        p1, ld1 = _pl(x1)
-        c1 = x1.shape[1]
-    else:
-        p1, ld1, c1 = 0, 0, 0
+    p1, ld1, c1 = _pl_opt(x1)
     py, ldy = _pl(y)
+    flop = _conv_flop(cout, x0.shape[1] + c1, ksize, n, h, w)
     ws = _scratch(int(query("srpde_conv_fwd_workspace_size", cout)), y.device)
     if _CONV_MATH == "h3" and query("srpde_conv_h3_supported", x0.shape[1], c1, cout, w, dil, ksize):
         planes, wexp = getattr(wpack, "h3", None) or split_weights_h3(wpack, cout)
-        rows_fwd = (int(query("srpde_conv_h3_stats_rows_for", x0.shape[1], c1, cout, h, w, dil, _FAMILY)) if sign == 1
-                    else int(query("srpde_conv_h3_stats_rows")))
-        for buf, rows in ((stats, rows_fwd), (bn_bwd[5] if bn_bwd is not None else None,
-                                              int(query("srpde_conv_h3_stats_rows")))):
-            if buf is not None and getattr(buf, "_srpde_rows", None) != rows:
-                raise ValueError("statistics buffer not laid out for the h3 kernel (use conv_stats_buffer "
-                                 "with the input channels / bn_bwd_partials)")
+        what = "the h3 kernel (use conv_stats_buffer with the input channels / bn_bwd_partials)"
+        if stats is not None:
+            _check_rows(stats, int(query("srpde_conv_h3_stats_rows_for", x0.shape[1], c1, cout, h, w, dil, _FAMILY))
+                        if sign == 1 else None, what)
+        _check_rows(bn_bwd[5] if bn_bwd is not None else None, None, what)
         a0 = amax_of(x0)
         a1 = amax_of(x1) if x1 is not None else None
-        _conv_call("srpde_conv_fwd_h3", 2.0 * cout * (x0.shape[1] + c1) * ksize * ksize * n * h * w, p0, x0.shape[1], ld0, p1, c1, ld1, a0.data_ptr(), _p(a1), planes.data_ptr(),
-             wexp.data_ptr(), _p(bias), py, ldy, n, h, w, cout, ksize, dil, sign, int(accumulate) | _FAMILY, _p(stats),
-             _p(planes_out), _p(in_affine[0] if in_affine else None), _p(in_affine[1] if in_affine else None),
-             *_bn_bwd_args(bn_bwd), _p(out_max), *_ep_args(ep_bn), _p(x1_gate[0] if x1_gate else None),
-             _p(x1_gate[1] if x1_gate else None), p0 if up is not None else 0, ld0 if up is not None else 0,
-             up.h if up is not None else 0, up.w if up is not None else 0, ws.data_ptr(), ws.numel(), stream_ptr())
+        _conv_call("srpde_conv_fwd_h3", flop, p0, x0.shape[1], ld0, p1, c1, ld1, a0.data_ptr(), _p(a1),
+                   planes.data_ptr(), wexp.data_ptr(), _p(bias), py, ldy, n, h, w, cout, ksize, dil, sign,
+                   int(accumulate) | _FAMILY, _p(stats), _p(planes_out), _p(in_affine[0] if in_affine else None),
+                   _p(in_affine[1] if in_affine else None), *_bn_bwd_args(bn_bwd), _p(out_max), *_ep_args(ep_bn),
+                   _p(x1_gate[0] if x1_gate else None), _p(x1_gate[1] if x1_gate else None),
+                   p0 if up is not None else 0, ld0 if up is not None else 0, up.h if up is not None else 0,
+                   up.w if up is not None else 0, ws.data_ptr(), ws.numel(), stream_ptr())
         if ep_bn is not None:
             tag_amax(y, ep_bn[4])
         if planes_out is not None:
@@ -267,11 +290,12 @@ def conv_fwd(x0, x1, wpack, bias, y, n, h, w, cout, ksize=3, dil=1, sign=1, accu
         return
     assert (planes_out is None and in_affine is None and bn_bwd is None and out_max is None
             and x1_gate is None), "planes_out / in_affine / bn_bwd / out_max / x1_gate need the h3 kernels"
-    if stats is not None and getattr(stats, "_srpde_rows", None) != int(query("srpde_conv_stats_rows_per_block", cout)):
-        raise ValueError("statistics buffer not laid out for this conv family (use conv_stats_buffer)")
-    _conv_call("srpde_conv_fwd", 2.0 * cout * (x0.shape[1] + c1) * ksize * ksize * n * h * w, p0, x0.shape[1], ld0, p1, c1, ld1, wpack.data_ptr(), _p(bias), py, ldy,
-         n, h, w, cout, ksize, dil, sign, int(accumulate), _p(stats), *_ep_args(ep_bn), ws.data_ptr(), ws.numel(),
-         stream_ptr())
+    if stats is not None:
+        _check_rows(stats, int(query("srpde_conv_stats_rows_per_block", cout)),
+                    "this conv family (use conv_stats_buffer)")
+    _conv_call("srpde_conv_fwd", flop, p0, x0.shape[1], ld0, p1, c1, ld1, wpack.data_ptr(), _p(bias), py, ldy, n, h, w,
+               cout, ksize, dil, sign, int(accumulate), _p(stats), *_ep_args(ep_bn), ws.data_ptr(), ws.numel(),
+               stream_ptr())
     if ep_bn is not None:
         tag_amax(y, ep_bn[4])
 
@@ -284,12 +308,12 @@ def conv_fwd_presplit(xp, wpack, bias, y, n, h, w, cout, ksize=3, dil=1, sign=1,
     planes, wexp = wpack.h3
     py, ldy = _pl(y)
     for buf in (stats, bn_bwd[5] if bn_bwd is not None else None):
-        if buf is not None and getattr(buf, "_srpde_rows", None) != int(query("srpde_conv_h3_stats_rows")):
-            raise ValueError("statistics buffer not laid out for the h3 kernel")
+        _check_rows(buf, None, "the h3 kernel")
     ws = _scratch(int(query("srpde_conv_fwd_workspace_size", cout)), y.device)
-    _conv_call("srpde_conv_fwd_h3_presplit", 2.0 * cout * c * ksize * ksize * n * h * w, xp.data_ptr(), c, xp._srpde_amax.data_ptr(), planes.data_ptr(), wexp.data_ptr(),
-         _p(bias), py, ldy, n, h, w, cout, ksize, dil, sign, int(accumulate) | _FAMILY, _p(stats), *_bn_bwd_args(bn_bwd),
-         _p(out_max), ws.data_ptr(), ws.numel(), stream_ptr())
+    _conv_call("srpde_conv_fwd_h3_presplit", _conv_flop(cout, c, ksize, n, h, w), xp.data_ptr(), c,
+               xp._srpde_amax.data_ptr(), planes.data_ptr(), wexp.data_ptr(), _p(bias), py, ldy, n, h, w, cout, ksize,
+               dil, sign, int(accumulate) | _FAMILY, _p(stats), *_bn_bwd_args(bn_bwd), _p(out_max), ws.data_ptr(),
+               ws.numel(), stream_ptr())
 
 
 def bn_bwd_apply_split(y, da, mean, invstd, gamma, beta, m1, m2, dy_amax, out=None, relu=True):
@@ -385,14 +409,13 @@ def conv_dgrad_bnb(da, y, mean, invstd, gamma, beta, m1, m2, dy_amax, wpack, dx,
     pda, ldda = _pl(da)
     py, ldy = _pl(y)
     pdx, lddx = _pl(dx)
-    for buf in (bn_bwd[5] if bn_bwd is not None else None,):
-        if buf is not None and getattr(buf, "_srpde_rows", None) != int(query("srpde_conv_h3_stats_rows")):
-            raise ValueError("statistics buffer not laid out for the h3 kernel (bn_bwd_partials)")
+    _check_rows(bn_bwd[5] if bn_bwd is not None else None, None, "the h3 kernel (bn_bwd_partials)")
     ws = _scratch(int(query("srpde_conv_fwd_workspace_size", cin_dx)), dx.device)
-    _conv_call("srpde_conv_dgrad_h3_bnb", 2.0 * cin_dx * cout_dy * 9 * n * h * w, pda, ldda, dy_amax.data_ptr(), py, ldy, mean.data_ptr(), invstd.data_ptr(),
-         gamma.data_ptr(), beta.data_ptr(), m1.data_ptr(), m2.data_ptr(), BN_RELU if relu else 0, planes.data_ptr(),
-         wexp.data_ptr(), pdx, lddx, n, h, w, cout_dy, cin_dx, dil, dysplit.data_ptr(), *_bn_bwd_args(bn_bwd),
-         _p(dx_max), ws.data_ptr(), ws.numel(), stream_ptr())
+    _conv_call("srpde_conv_dgrad_h3_bnb", _conv_flop(cin_dx, cout_dy, 3, n, h, w), pda, ldda, dy_amax.data_ptr(), py,
+               ldy, mean.data_ptr(), invstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(), m1.data_ptr(),
+               m2.data_ptr(), BN_RELU if relu else 0, planes.data_ptr(), wexp.data_ptr(), pdx, lddx, n, h, w, cout_dy,
+               cin_dx, dil, dysplit.data_ptr(), *_bn_bwd_args(bn_bwd), _p(dx_max), ws.data_ptr(), ws.numel(),
+               stream_ptr())
     dysplit._srpde_amax = dy_amax
 
 
@@ -462,9 +485,8 @@ def conv_wgrad_bnb(da, y, mean, invstd, gamma, beta, m1, m2, x0, dw, n, h, w, ks
     p0, ld0 = _pl(x0)
     cin = x0.shape[1]
     cin_real = dw.shape[1]
-    ws_bytes = int(query("srpde_conv_wgrad_workspace_size", n, h, w, cout, cin, ksize))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=da.device)
-    _conv_call("srpde_conv_wgrad_bnb", 2.0 * cout * cin_real * ksize * ksize * n * h * w, pda, ldda, py, ldy,
+    ws, ws_bytes = _wgrad_workspace("srpde_conv_wgrad_workspace_size", n, h, w, cout, cin, ksize, da.device)
+    _conv_call("srpde_conv_wgrad_bnb", _conv_flop(cout, cin_real, ksize, n, h, w), pda, ldda, py, ldy,
                mean.data_ptr(), invstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(), m1.data_ptr(), m2.data_ptr(),
                BN_RELU if relu else 0, p0, cin, ld0, dw.data_ptr(), cin_real, 0, n, h, w, cout, ksize, dil,
                ws.data_ptr(), ws_bytes, stream_ptr())
@@ -474,23 +496,19 @@ def conv_wgrad(dy, x0, x1, dw, n, h, w, ksize=3, dil=1, accumulate=False):
     cout = dy.shape[1]
     pdy, lddy = _pl(dy)
     p0, ld0 = _pl(x0)
-    if x1 is not None:
-        p1, ld1 = _pl(x1)
-        c1 = x1.shape[1]
-    else:
-        p1, ld1, c1 = 0, 0, 0
+    p1, ld1, c1 = _pl_opt(x1)
     cin = x0.shape[1] + c1
     cin_real = dw.shape[1]
-    ws_bytes = int(query("srpde_conv_wgrad_workspace_size", n, h, w, cout, cin, ksize))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dy.device)
+    flop = _conv_flop(cout, cin_real, ksize, n, h, w)
+    ws, ws_bytes = _wgrad_workspace("srpde_conv_wgrad_workspace_size", n, h, w, cout, cin, ksize, dy.device)
     if _CONV_MATH == "h3" and x0.shape[1] % 32 == 0 and c1 % 32 == 0 and cout % 16 == 0 and ksize == 3:
         a1 = amax_of(x1) if x1 is not None else None
-        _conv_call("srpde_conv_wgrad_h3", 2.0 * cout * cin_real * ksize * ksize * n * h * w, pdy, lddy, amax_of(dy).data_ptr(), p0, x0.shape[1], ld0, amax_of(x0).data_ptr(),
-             p1, c1, ld1, _p(a1), dw.data_ptr(), cin_real, int(accumulate), n, h, w, cout, ksize, dil, ws.data_ptr(),
-             ws_bytes, stream_ptr())
+        _conv_call("srpde_conv_wgrad_h3", flop, pdy, lddy, amax_of(dy).data_ptr(), p0, x0.shape[1], ld0,
+                   amax_of(x0).data_ptr(), p1, c1, ld1, _p(a1), dw.data_ptr(), cin_real, int(accumulate), n, h, w, cout,
+                   ksize, dil, ws.data_ptr(), ws_bytes, stream_ptr())
         return
-    _conv_call("srpde_conv_wgrad", 2.0 * cout * cin_real * ksize * ksize * n * h * w, pdy, lddy, p0, x0.shape[1], ld0, p1, c1, ld1, dw.data_ptr(), cin_real,
-         int(accumulate), n, h, w, cout, ksize, dil, ws.data_ptr(), ws_bytes, stream_ptr())
+    _conv_call("srpde_conv_wgrad", flop, pdy, lddy, p0, x0.shape[1], ld0, p1, c1, ld1, dw.data_ptr(), cin_real,
+               int(accumulate), n, h, w, cout, ksize, dil, ws.data_ptr(), ws_bytes, stream_ptr())
 
 
 def split_planes_buffer(P, c, device):
@@ -538,24 +556,22 @@ def conv_wgrad_h3p(dyp, xp, dw, n, h, w, ksize=3, dil=1, accumulate=False):
     a0, a1 = (ax, None) if not isinstance(ax, tuple) else ax
     c1 = 0 if a1 is None else cin - xp._srpde_c0
     c0 = cin - c1
-    ws_bytes = int(query("srpde_conv_wgrad_h3p_workspace_size", n, h, w, cout, cin, ksize))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dyp.device)
-    _conv_call("srpde_conv_wgrad_h3p", 2.0 * cout * dw.shape[1] * ksize * ksize * n * h * w, dyp.data_ptr(), dyp._srpde_amax.data_ptr(), xp.data_ptr(), c0, a0.data_ptr(), c1,
-         _p(a1), dw.data_ptr(), dw.shape[1], int(accumulate), n, h, w, cout, ksize, dil, ws.data_ptr(), ws_bytes,
-         stream_ptr())
+    ws, ws_bytes = _wgrad_workspace("srpde_conv_wgrad_h3p_workspace_size", n, h, w, cout, cin, ksize, dyp.device)
+    _conv_call("srpde_conv_wgrad_h3p", _conv_flop(cout, dw.shape[1], ksize, n, h, w), dyp.data_ptr(),
+               dyp._srpde_amax.data_ptr(), xp.data_ptr(), c0, a0.data_ptr(), c1, _p(a1), dw.data_ptr(), dw.shape[1],
+               int(accumulate), n, h, w, cout, ksize, dil, ws.data_ptr(), ws_bytes, stream_ptr())
 
 
 def _conv_wgrad_h3x(dyp, xs, dw, n, h, w, ksize, dil, accumulate):
     cout = dw.shape[0]
     assert dyp.shape[2] == cpad32(cout), "dy planes must hold cout rounded up to 32 channels"
     x0, x1 = xs.x0, xs.x1
-    c0, c1 = x0.shape[1], (x1.shape[1] if x1 is not None else 0)
+    c0 = x0.shape[1]
     p0, ld0 = _pl(x0)
-    p1, ld1 = _pl(x1) if x1 is not None else (0, 0)
+    p1, ld1, c1 = _pl_opt(x1)
     aff, gate = xs.in_affine, xs.x1_gate
-    ws_bytes = int(query("srpde_conv_wgrad_h3p_workspace_size", n, h, w, cout, c0 + c1, ksize))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dyp.device)
-    _conv_call("srpde_conv_wgrad_h3x", 2.0 * cout * dw.shape[1] * ksize * ksize * n * h * w, dyp.data_ptr(),
+    ws, ws_bytes = _wgrad_workspace("srpde_conv_wgrad_h3p_workspace_size", n, h, w, cout, c0 + c1, ksize, dyp.device)
+    _conv_call("srpde_conv_wgrad_h3x", _conv_flop(cout, dw.shape[1], ksize, n, h, w), dyp.data_ptr(),
                dyp._srpde_amax.data_ptr(), p0, ld0, c0, xs.a0.data_ptr(), _p(aff[0] if aff else None),
                _p(aff[1] if aff else None), p1, ld1, c1, _p(xs.a1), _p(gate[0] if gate else None),
                _p(gate[1] if gate else None), dw.data_ptr(), dw.shape[1], int(accumulate), n, h, w, cout, ksize, dil,

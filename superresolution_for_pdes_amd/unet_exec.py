@@ -497,6 +497,54 @@ def _xkeep(xp):
     return tuple(xp.tensors()) if isinstance(xp, H.XSource) else ()
 
 
+def _bwd_path(saved, dx, dx_accumulate, cin, w, dil):
+    """Which kernels run a conv + BN + ReLU layer's backward (_cbr_bwd), first match wins:
+    "bnb": the BN backward inside the dgrad's operand transform (srpde_conv_dgrad_h3_bnb);
+    "presplit": the BN backward apply writes dy's h3 split, read by the dgrad and the weight gradient;
+    "wgrad_bnb": enc1.conv1 (no dgrad: the input image), the BN backward inside the fp32 weight gradient's dY loads;
+    "plain": bn_relu_bwd writes fp32 dy for whichever dgrad / weight gradient kernels take the shape."""
+    x0, x1, y, _, _, xp, train = saved
+    cout = y.shape[1]
+    if (_FUSE_BN_APPLY and train and dx is not None and xp is not None and not dx_accumulate
+            and cin <= _BNB_MAX_CIN and cout >= _BNB_MIN_COUT and H.bnb_capable(cout, cin, w, dil)):
+        return "bnb"
+    if (_PRESPLIT_BWD and train and dx is not None and xp is not None
+            and H.h3_capable(H.cpad32(cout), 0, cin, w, dil)):
+        return "presplit"
+    if (_FUSE_WGRAD_BN and train and dx is None and xp is None and x0 is not None and x1 is None
+            and x0.shape[1] % 32 != 0):
+        return "wgrad_bnb"
+    return "plain"
+
+
+def _bn_prepare(conv, bn, saved, da, grads, part):
+    """srpde_bn_bwd_prepare of the layer's BN: its parameter gradients, -> (m1, m2, dy's max|.| word)"""
+    _, _, y, mean, invstd, _, _ = saved
+    part_t, da_max = part if part is not None else (None, None)
+    return H.bn_bwd_prepare(y, da, mean, invstd, bn.weight, bn.bias, grads[bn.weight], grads[bn.bias],
+                            grads[conv.bias], part=part_t, da_max=da_max)
+
+
+def _below_reduction(below, n, h, w, cin, dev, max_slots):
+    """What a dgrad into a fresh ``dx`` takes to also reduce for the BN below (``below = (bn, saved)``, None:
+    not fused) -> (bn_bwd, dx_max, out_part).  ``max_slots``: makes the max|dx| slots that dgrad kernel writes
+    (None: it writes none)."""
+    if below is None:
+        return None, None, None
+    bnb, sb = below
+    out_part = H.bn_bwd_partials(n, h, w, cin, dev)
+    bn_bwd = (sb[2], sb[3], sb[4], bnb.weight, bnb.bias, out_part)
+    return bn_bwd, (max_slots() if max_slots is not None else None), out_part
+
+
+def _submit(wq, fn, keep):
+    """Run a weight-gradient launch in line, or on ``wq``'s side stream keeping ``keep`` alive there."""
+    if wq is None:
+        fn()
+    else:
+        wq.submit(fn, keep)
+
+
 def _cbr_bwd(conv, bn, saved, da, n, h, w, dil, grads, slots, dx=None, dx_accumulate=False, part=None,
              below=None, wq=None):
     """dgrad first: its h3 kernel stores dy's split, which the weight gradient then reads together
@@ -517,92 +565,58 @@ def _cbr_bwd(conv, bn, saved, da, n, h, w, dil, grads, slots, dx=None, dx_accumu
     +45 us) the separate elementwise pass is cheaper, so those keep it."""
     x0, x1, y, mean, invstd, xp, train = saved
     P, cout = y.shape
-    part_t, da_max = part if part is not None else (None, None)
+    dev = y.device
     cin = conv.in_channels if x0 is None else x0.shape[1] + (x1.shape[1] if x1 is not None else 0)
-    dyp = None
-    out_part = None
-    if (_FUSE_BN_APPLY and train and dx is not None and xp is not None and not dx_accumulate
-            and cin <= _BNB_MAX_CIN and cout >= _BNB_MIN_COUT and H.bnb_capable(cout, cin, w, dil)):
-        m1, m2, dyw = H.bn_bwd_prepare(y, da, mean, invstd, bn.weight, bn.bias, grads[bn.weight], grads[bn.bias],
-                                       grads[conv.bias], part=part_t, da_max=da_max)
-        wd = _dgrad_weights(conv, cin, w, dil)
-        dyp = H.split_planes_buffer(P, cout, y.device)
-        bn_bwd, dx_max = None, None
-        if below is not None and _FUSE_BN_BWD:
-            bnb, sb = below
-            out_part = H.bn_bwd_partials(n, h, w, cin, y.device)
-            bn_bwd = (sb[2], sb[3], sb[4], bnb.weight, bnb.bias, out_part)
-            dx_max = H.dx_max_slots(n, h, w, cin, y.device)
-        H.conv_dgrad_bnb(da, y, mean, invstd, bn.weight, bn.bias, m1, m2, dyw, wd, dx, n, h, w, cout, cin, dil, dyp,
-                         bn_bwd=bn_bwd, dx_max=dx_max)
-        _tap_dgrad(conv, dyp, dx, dx_max, out_part)
-        fn, keep = (lambda: H.conv_wgrad_h3p(dyp, xp, grads[conv.weight], n, h, w, 3, dil)), (dyp, dyw) + _xkeep(xp)
-        if wq is None:
-            fn()
+    path = _bwd_path(saved, dx, dx_accumulate, cin, w, dil)
+    if path in ("bnb", "presplit"):
+        m1, m2, dyw = _bn_prepare(conv, bn, saved, da, grads, part)
+        if path == "bnb":
+            wd = _dgrad_weights(conv, cin, w, dil)
+            dyp = H.split_planes_buffer(P, cout, dev)
+            bn_bwd, dx_max, out_part = _below_reduction(below if _FUSE_BN_BWD else None, n, h, w, cin, dev,
+                                                        lambda: H.dx_max_slots(n, h, w, cin, dev))
+            H.conv_dgrad_bnb(da, y, mean, invstd, bn.weight, bn.bias, m1, m2, dyw, wd, dx, n, h, w, cout, cin, dil,
+                             dyp, bn_bwd=bn_bwd, dx_max=dx_max)
         else:
-            wq.submit(fn, keep)
-        return None if out_part is None else (out_part, dx_max)
-    if (_PRESPLIT_BWD and train and dx is not None and xp is not None
-            and H.h3_capable(H.cpad32(cout), 0, cin, w, dil)):
-        # the BN backward apply writes dy as its h3 split (scale from bn_bwd_prepare's rigorous bound);
-        # the dgrad reads the fp16 pieces straight into its operand tiles and the weight gradient
-        # reads the same planes: no fp32 dy, no split work or split store in the dgrad
-        m1, m2, dyw = H.bn_bwd_prepare(y, da, mean, invstd, bn.weight, bn.bias, grads[bn.weight], grads[bn.bias],
-                                       grads[conv.bias], part=part_t, da_max=da_max)
-        dyp = H.bn_bwd_apply_split(y, da, mean, invstd, bn.weight, bn.bias, m1, m2, dyw)
-        if DEBUG_TAPS is not None:
+            # the BN backward apply writes dy as its h3 split (scale from bn_bwd_prepare's rigorous bound);
+            # the dgrad reads the fp16 pieces straight into its operand tiles and the weight gradient
+            # reads the same planes: no fp32 dy, no split work or split store in the dgrad
+            dyp = H.bn_bwd_apply_split(y, da, mean, invstd, bn.weight, bn.bias, m1, m2, dyw)
             _tap("dyp:" + getattr(conv, "_srpde_name", "?"), dyp)
-        wd = _dgrad_weights(conv, cin, w, dil, cdy=H.cpad32(cout))
-        bn_bwd, dx_max = None, None
-        if below is not None and not dx_accumulate and _FUSE_BN_BWD:
-            bnb, sb = below
-            out_part = H.bn_bwd_partials(n, h, w, cin, y.device)
-            bn_bwd = (sb[2], sb[3], sb[4], bnb.weight, bnb.bias, out_part)
-            if _FUSE_BN_APPLY:   # max|dx| slots for the layer below's BN backward bound
-                dx_max = H.out_max_slots(n, h, w, H.cpad32(cout), cin, dil, y.device)
-        H.conv_fwd_presplit(dyp, wd, None, dx, n, h, w, cin, 3, dil, -1, dx_accumulate, None, bn_bwd=bn_bwd,
-                            out_max=dx_max)
+            wd = _dgrad_weights(conv, cin, w, dil, cdy=H.cpad32(cout))
+            # max|dx| slots (for the layer below's BN backward bound) only when that layer can fuse its apply
+            bn_bwd, dx_max, out_part = _below_reduction(
+                below if _FUSE_BN_BWD and not dx_accumulate else None, n, h, w, cin, dev,
+                (lambda: H.out_max_slots(n, h, w, H.cpad32(cout), cin, dil, dev)) if _FUSE_BN_APPLY else None)
+            H.conv_fwd_presplit(dyp, wd, None, dx, n, h, w, cin, 3, dil, -1, dx_accumulate, None, bn_bwd=bn_bwd,
+                                out_max=dx_max)
         _tap_dgrad(conv, dyp, dx, dx_max, out_part)
-        fn, keep = (lambda: H.conv_wgrad_h3p(dyp, xp, grads[conv.weight], n, h, w, 3, dil)), (dyp, dyw) + _xkeep(xp)
-        if wq is None:
-            fn()
-        else:
-            wq.submit(fn, keep)
+        _submit(wq, lambda: H.conv_wgrad_h3p(dyp, xp, grads[conv.weight], n, h, w, 3, dil), (dyp, dyw) + _xkeep(xp))
         return None if out_part is None else (out_part, dx_max)
-    if (_FUSE_WGRAD_BN and train and dx is None and xp is None and x0 is not None and x1 is None
-            and x0.shape[1] % 32 != 0 and DEBUG_TAPS is None):
-        # enc1.conv1 (no dgrad: the input image): the fp32 weight gradient applies the BN backward to its dY loads
-        m1, m2, _ = H.bn_bwd_prepare(y, da, mean, invstd, bn.weight, bn.bias, grads[bn.weight], grads[bn.bias],
-                                     grads[conv.bias], part=part_t, da_max=da_max)
-        dw = grads[conv.weight]
-        fn = lambda: H.conv_wgrad_bnb(da, y, mean, invstd, bn.weight, bn.bias, m1, m2, x0, dw, n, h, w, 3, dil)
-        if wq is None:
-            fn()
-        else:
-            wq.submit(fn, (da, y, m1, m2))
+    dw = grads[conv.weight]
+    if path == "wgrad_bnb":
+        m1, m2, _ = _bn_prepare(conv, bn, saved, da, grads, part)
+        _submit(wq, lambda: H.conv_wgrad_bnb(da, y, mean, invstd, bn.weight, bn.bias, m1, m2, x0, dw, n, h, w, 3, dil),
+                (da, y, m1, m2))
         return None
-    dy = H.empty(P, cout, device=y.device)
+    dy = H.empty(P, cout, device=dev)
     # eval mode: the forward normalised with the running statistics (constants), so the BN
     # backward drops the batch-statistic terms (aten native_batch_norm_backward, training=False)
     H.bn_relu_bwd(y, da, mean, invstd, bn.weight, bn.bias, dy, grads[bn.weight], grads[bn.bias], grads[conv.bias],
-                  amax=slots.take(), part=part_t, eval_mode=not train)
-    if DEBUG_TAPS is not None:
-        _tap("dy:" + getattr(conv, "_srpde_name", "?"), dy)
+                  amax=slots.take(), part=part[0] if part is not None else None, eval_mode=not train)
+    _tap("dy:" + getattr(conv, "_srpde_name", "?"), dy)
+    dyp, out_part, dx_max = None, None, None
     if dx is not None:
         wd = _dgrad_weights(conv, cin, w, dil)
         if xp is not None:
-            dyp = H.split_planes_buffer(P, cout, y.device)
-        bn_bwd, dx_max = None, None
-        if below is not None and not dx_accumulate and _FUSE_BN_BWD and H.h3_capable(cout, 0, cin, w, dil):
-            bnb, sb = below
-            out_part = H.bn_bwd_partials(n, h, w, cin, y.device)
-            bn_bwd = (sb[2], sb[3], sb[4], bnb.weight, bnb.bias, out_part)
-            if _FUSE_BN_APPLY:   # max|dx| slots for a fused BN apply in the layer below
-                dx_max = H.out_max_slots(n, h, w, cout, cin, dil, y.device)
+            dyp = H.split_planes_buffer(P, cout, dev)
+        fused = below is not None and _FUSE_BN_BWD and not dx_accumulate and H.h3_capable(cout, 0, cin, w, dil)
+        bn_bwd, dx_max, out_part = _below_reduction(
+            below if fused else None, n, h, w, cin, dev,
+            (lambda: H.out_max_slots(n, h, w, cout, cin, dil, dev)) if _FUSE_BN_APPLY else None)
         H.conv_fwd(dy, None, wd, None, dx, n, h, w, cin, 3, dil, -1, dx_accumulate, None, dyp, bn_bwd=bn_bwd,
                    out_max=dx_max)
         _tap_dgrad(conv, dyp, dx, dx_max, out_part)
-    dw = grads[conv.weight]
     if xp is not None and dyp is not None:
         fn, keep = (lambda: H.conv_wgrad_h3p(dyp, xp, dw, n, h, w, 3, dil)), (dyp, dyp._srpde_amax) + _xkeep(xp)
     else:
@@ -610,10 +624,7 @@ def _cbr_bwd(conv, bn, saved, da, n, h, w, dil, grads, slots, dx=None, dx_accumu
         if isinstance(x1, GatedInput):
             x1 = x1.materialize()
         fn, keep = (lambda: H.conv_wgrad(dy, x0, x1, dw, n, h, w, 3, dil)), (dy, getattr(dy, "_srpde_amax", None))
-    if wq is None:
-        fn()
-    else:
-        wq.submit(fn, keep)
+    _submit(wq, fn, keep)
     return None if out_part is None else (out_part, dx_max)
 
 

@@ -11,12 +11,26 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda"
 
 
+# the conv launches of the last _step: hipops.LAUNCH_TAP's records, and the name of the entry behind each
+LAST_LAUNCHES, LAST_ENTRIES = [], []
+
+
 def _step(model, x, t, fuse, attr="_FUSE_ENC_OUT", keep=("e1", "e2")):
+    from superresolution_for_pdes_amd import hipops as H
     from superresolution_for_pdes_amd import unet_exec as X
     from superresolution_for_pdes_amd.functional import mse_loss
     prev = getattr(X, attr)
     setattr(X, attr, fuse)
     X.DEBUG_TAPS = {}
+    conv_call = H._conv_call
+    LAST_LAUNCHES.clear()
+    LAST_ENTRIES.clear()
+
+    def recording_conv_call(name, *args):
+        LAST_ENTRIES.append(name)
+        return conv_call(name, *args)
+
+    H.LAUNCH_TAP, H._conv_call = LAST_LAUNCHES, recording_conv_call
     try:
         for p in model.parameters():
             p.grad = None
@@ -25,6 +39,7 @@ def _step(model, x, t, fuse, attr="_FUSE_ENC_OUT", keep=("e1", "e2")):
         torch.cuda.synchronize()
         taps = X.DEBUG_TAPS
     finally:
+        H.LAUNCH_TAP, H._conv_call = None, conv_call
         X.DEBUG_TAPS = None
         setattr(X, attr, prev)
     return {k: v for k, v in taps.items() if k in keep}, {n: p.grad.clone() for n, p in model.named_parameters()}
@@ -223,8 +238,13 @@ def test_enc1_conv1_weight_gradient_with_fused_bn_backward(n):
     x = torch.randn(n, 3, 40, 40, device=DEV, generator=g)
     x[:, 1] = 1.0
     t = torch.randn(n, 1, 40, 40, device=DEV, generator=g)
+    # srpde_conv_wgrad_bnb's fp32 kernel does not report its name to srpde_last_kernel (its LAUNCH_TAP record
+    # carries the launch before it), so the launch is identified by its entry: one call on the fused run, whose
+    # record the tap holds, and none on the unfused run
     _, grads_f = _step(model, x, t, True, "_FUSE_WGRAD_BN", ())
+    assert LAST_ENTRIES.count("srpde_conv_wgrad_bnb") == 1 and len(LAST_LAUNCHES) == len(LAST_ENTRIES)
     _, grads_u = _step(model, x, t, False, "_FUSE_WGRAD_BN", ())
+    assert "srpde_conv_wgrad_bnb" not in LAST_ENTRIES and len(LAST_LAUNCHES) == len(LAST_ENTRIES)
     for name, gu in grads_u.items():
         if name == "enc1.conv1.bias":
             rel = float((grads_f[name] - gu).double().norm() / max(float(grads_u["enc1.conv1.weight"].norm()), 1e-30))

@@ -9,7 +9,7 @@
 // (conv.hip) merged here with Chan's parallel formula in fp64, in a fixed tree order
 // (deterministic).  The backward recomputes x_hat and the ReLU mask from the conv
 // output y instead of storing them.
-#include "common.h"
+#include "bn_reduce.h"
 
 namespace srpde {
 
@@ -256,6 +256,13 @@ __device__ __forceinline__ void block_amax(float v, unsigned* amax) {
   }
 }
 
+// (v - mean) * invstd * gamma + beta
+__device__ __forceinline__ float4 bn_affine4(const float4& v, const float4& mu, const float4& is, const float4& g,
+                                             const float4& b) {
+  return make_float4((v.x - mu.x) * is.x * g.x + b.x, (v.y - mu.y) * is.y * g.y + b.y,
+                     (v.z - mu.z) * is.z * g.z + b.z, (v.w - mu.w) * is.w * g.w + b.w);
+}
+
 // out = relu((y - mean) * invstd * gamma + beta)
 __global__ __launch_bounds__(256) void bn_relu_fwd_kernel(const float* __restrict__ y, int ldy,
                                                           const float* __restrict__ mean,
@@ -270,21 +277,15 @@ __global__ __launch_bounds__(256) void bn_relu_fwd_kernel(const float* __restric
        e += (long long)gridDim.x * blockDim.x) {
     const long long p = e / C4;
     const int c = (int)(e - p * C4) * 4;
-    const float4 v = *reinterpret_cast<const float4*>(y + p * ldy + c);
-    const float4 mu = *reinterpret_cast<const float4*>(mean + c);
-    const float4 is = *reinterpret_cast<const float4*>(invstd + c);
-    const float4 g = *reinterpret_cast<const float4*>(gamma + c);
-    const float4 b = *reinterpret_cast<const float4*>(beta + c);
-    float4 o;
-    o.x = (v.x - mu.x) * is.x * g.x + b.x;
-    o.y = (v.y - mu.y) * is.y * g.y + b.y;
-    o.z = (v.z - mu.z) * is.z * g.z + b.z;
-    o.w = (v.w - mu.w) * is.w * g.w + b.w;
-    if (relu) {
-      o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f);
-    }
-    *reinterpret_cast<float4*>(out + p * ldo + c) = o;
-    mx = fmaxf(mx, fmaxf(fmaxf(fabsf(o.x), fabsf(o.y)), fmaxf(fabsf(o.z), fabsf(o.w))));
+    const float4 v = ld4(y + p * ldy + c);
+    const float4 mu = ld4(mean + c);
+    const float4 is = ld4(invstd + c);
+    const float4 g = ld4(gamma + c);
+    const float4 b = ld4(beta + c);
+    float4 o = bn_affine4(v, mu, is, g, b);
+    if (relu) o = relu4(o);
+    st4(out + p * ldo + c, o);
+    mx = fmaxf(mx, absmax4(o));
   }
   if (amax) block_amax(mx, amax);
 }
@@ -312,15 +313,15 @@ __device__ __forceinline__ void bn_rows(long long p0, long long pe, int rs, cons
     float4 vv[BN_U], dd[BN_U];
 #pragma unroll
     for (int u = 0; u < BN_U; ++u) {
-      vv[u] = *reinterpret_cast<const float4*>(y + (p0 + u * rs) * ldy + c);
-      dd[u] = *reinterpret_cast<const float4*>(da + (p0 + u * rs) * ldda + c);
+      vv[u] = ld4(y + (p0 + u * rs) * ldy + c);
+      dd[u] = ld4(da + (p0 + u * rs) * ldda + c);
     }
     __builtin_amdgcn_sched_barrier(0);   // (the scheduler would sink each load to its row)
 #pragma unroll
     for (int u = 0; u < BN_U; ++u) row(p0 + u * rs, vv[u], dd[u]);
   }
   for (; p0 < pe; p0 += rs)
-    row(p0, *reinterpret_cast<const float4*>(y + p0 * ldy + c), *reinterpret_cast<const float4*>(da + p0 * ldda + c));
+    row(p0, ld4(y + p0 * ldy + c), ld4(da + p0 * ldda + c));
 }
 
 // partial sums of dz and dz*xhat per (block, channel); dz = da * [bn_out > 0]
@@ -338,51 +339,20 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const float* __restr
   thread_rc(C, &c4, &r0, &rs);
   const int active = (C >> 2) * rs;
   const int c = c4 * 4;
-  float4 s1 = make_float4(0.f, 0.f, 0.f, 0.f), s2 = s1;
-  float dmax = 0.f;
+  BnBwdAcc acc;
   if ((int)threadIdx.x < active) {
-    const float4 mu = *reinterpret_cast<const float4*>(mean + c);
-    const float4 is = *reinterpret_cast<const float4*>(invstd + c);
-    const float4 g = *reinterpret_cast<const float4*>(gamma + c);
-    const float4 b = *reinterpret_cast<const float4*>(beta + c);
+    acc.load(mean, invstd, gamma, beta, c);
     const long long pb = (long long)blockIdx.x * rows_per_blk;
     const long long pe = min(P, pb + rows_per_blk);
     auto row = [&](long long, const float4& v, const float4& d) {
-      dmax = fmaxf(dmax, fmaxf(fmaxf(fabsf(d.x), fabsf(d.y)), fmaxf(fabsf(d.z), fabsf(d.w))));
-      float xh, dz;
-#define BN_ACC(X)                                              \
-  xh = (v.X - mu.X) * is.X;                                    \
-  dz = (!(relu & 1) || xh * g.X + b.X > 0.f) ? d.X : 0.f;      \
-  s1.X += dz;                                                  \
-  s2.X += dz * xh;
-      BN_ACC(x) BN_ACC(y) BN_ACC(z) BN_ACC(w)
-#undef BN_ACC
+      acc.amax(d);
+      acc.add(v, d, relu);
     };
     bn_rows(pb + r0, pe, rs, y, ldy, da, ldda, c, row);
   }
-  red4[threadIdx.x] = s1;
-  red4[256 + threadIdx.x] = s2;
-  __syncthreads();
-  if ((int)threadIdx.x < (C >> 2)) {
-    float4 t1 = make_float4(0.f, 0.f, 0.f, 0.f), t2 = t1;
-    for (int r = 0; r < rs; ++r) {
-      const float4 a = red4[r * (C >> 2) + threadIdx.x], b2 = red4[256 + r * (C >> 2) + threadIdx.x];
-      t1.x += a.x; t1.y += a.y; t1.z += a.z; t1.w += a.w;
-      t2.x += b2.x; t2.y += b2.y; t2.z += b2.z; t2.w += b2.w;
-    }
-    float2* o = part + (size_t)blockIdx.x * C + c;
-    o[0] = make_float2(t1.x, t2.x); o[1] = make_float2(t1.y, t2.y);
-    o[2] = make_float2(t1.z, t2.z); o[3] = make_float2(t1.w, t2.w);
-  }
-  if (da_max != nullptr) {   // this block's max|da| -> its slot (block-uniform branch)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) dmax = fmaxf(dmax, __shfl_xor(dmax, o, 64));
-    __syncthreads();
-    float* wmx = reinterpret_cast<float*>(red4);
-    if ((threadIdx.x & 63) == 0) wmx[threadIdx.x >> 6] = dmax;
-    __syncthreads();
-    if (threadIdx.x == 0) da_max[blockIdx.x] = fmaxf(fmaxf(wmx[0], wmx[1]), fmaxf(wmx[2], wmx[3]));
-  }
+  // this block's max|da| -> its slot (block-uniform branch)
+  bn_bwd_block_combine(red4, threadIdx.x, (int)threadIdx.x < (C >> 2), threadIdx.x, C >> 2, rs, acc,
+                       part + (size_t)blockIdx.x * C + c, da_max != nullptr, da_max + blockIdx.x);
 }
 
 // The attention gate's gating gradient accumulated into dg (pointwise.hip att_bwd_gating_kernel's
@@ -403,54 +373,22 @@ __global__ __launch_bounds__(256) void gating_bn_reduce_kernel(const float* __re
   thread_rc(C, &c4, &r0, &rs);
   const int active = (C >> 2) * rs;
   const int c = c4 * 4;
-  float4 s1 = make_float4(0.f, 0.f, 0.f, 0.f), s2 = s1;
-  float dmax = 0.f;
+  BnBwdAcc acc;
   if ((int)threadIdx.x < active) {
-    const float4 mu = *reinterpret_cast<const float4*>(mean + c);
-    const float4 is = *reinterpret_cast<const float4*>(invstd + c);
-    const float4 g = *reinterpret_cast<const float4*>(gamma + c);
-    const float4 b = *reinterpret_cast<const float4*>(beta + c);
-    const float4 w = *reinterpret_cast<const float4*>(wg + c);
+    acc.load(mean, invstd, gamma, beta, c);
+    const float4 w = ld4(wg + c);
     const long long pb = (long long)blockIdx.x * rows_per_blk;
     const long long pe = min(P, pb + rows_per_blk);
     auto row = [&](long long p, const float4& v, const float4& old) {
-      const float sp = dsa[p];
-      float4 d = make_float4(sp * w.x, sp * w.y, sp * w.z, sp * w.w);
-      d.x += old.x; d.y += old.y; d.z += old.z; d.w += old.w;
-      *reinterpret_cast<float4*>(dg + p * lddg + c) = d;
-      dmax = fmaxf(dmax, fmaxf(fmaxf(fabsf(d.x), fabsf(d.y)), fmaxf(fabsf(d.z), fabsf(d.w))));
-      float xh, dz;
-#define GBN_ACC(X)                                             \
-  xh = (v.X - mu.X) * is.X;                                    \
-  dz = (!(relu & 1) || xh * g.X + b.X > 0.f) ? d.X : 0.f;      \
-  s1.X += dz;                                                  \
-  s2.X += dz * xh;
-      GBN_ACC(x) GBN_ACC(y) GBN_ACC(z) GBN_ACC(w)
-#undef GBN_ACC
+      const float4 d = add4(scale4(dsa[p], w), old);
+      st4(dg + p * lddg + c, d);
+      acc.amax(d);
+      acc.add(v, d, relu);
     };
     bn_rows(pb + r0, pe, rs, y, ldy, dg, lddg, c, row);
   }
-  red4[threadIdx.x] = s1;
-  red4[256 + threadIdx.x] = s2;
-  __syncthreads();
-  if ((int)threadIdx.x < (C >> 2)) {
-    float4 t1 = make_float4(0.f, 0.f, 0.f, 0.f), t2 = t1;
-    for (int r = 0; r < rs; ++r) {
-      const float4 a = red4[r * (C >> 2) + threadIdx.x], b2 = red4[256 + r * (C >> 2) + threadIdx.x];
-      t1.x += a.x; t1.y += a.y; t1.z += a.z; t1.w += a.w;
-      t2.x += b2.x; t2.y += b2.y; t2.z += b2.z; t2.w += b2.w;
-    }
-    float2* o = part + (size_t)blockIdx.x * C + c;
-    o[0] = make_float2(t1.x, t2.x); o[1] = make_float2(t1.y, t2.y);
-    o[2] = make_float2(t1.z, t2.z); o[3] = make_float2(t1.w, t2.w);
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) dmax = fmaxf(dmax, __shfl_xor(dmax, o, 64));
-  __syncthreads();
-  float* wmx = reinterpret_cast<float*>(red4);
-  if ((threadIdx.x & 63) == 0) wmx[threadIdx.x >> 6] = dmax;
-  __syncthreads();
-  if (threadIdx.x == 0) da_max[blockIdx.x] = fmaxf(fmaxf(wmx[0], wmx[1]), fmaxf(wmx[2], wmx[3]));
+  bn_bwd_block_combine(red4, threadIdx.x, (int)threadIdx.x < (C >> 2), threadIdx.x, C >> 2, rs, acc,
+                       part + (size_t)blockIdx.x * C + c, true, da_max + blockIdx.x);
 }
 
 // fp64 column sums of [nblk][C] float2 partials -> out0[C], out1[C]; one block per channel
@@ -477,6 +415,23 @@ __global__ __launch_bounds__(256) void colsum2_kernel(const float2* __restrict__
   }
 }
 
+// dy = (dz - m1 - xhat * m2) * k for a channel quad: m1 = sum(dz)/P, m2 = sum(dz*xhat)/P (0 in eval mode), k = gamma*invstd
+struct BnBwdDy {
+  float4 mu, is, g, b, m1, m2, k;
+  __device__ __forceinline__ float dy1(float v, float mu1, float is1, float g1, float b1, float d, int relu, float a1,
+                                       float a2, float k1) const {
+    float xh;
+    const float dz = bn_relu_mask(v, mu1, is1, g1, b1, d, relu, &xh);
+    return (dz - a1 - xh * a2) * k1;
+  }
+  __device__ __forceinline__ float4 dy4(const float4& v, const float4& d, int relu) const {
+    return make_float4(dy1(v.x, mu.x, is.x, g.x, b.x, d.x, relu, m1.x, m2.x, k.x),
+                       dy1(v.y, mu.y, is.y, g.y, b.y, d.y, relu, m1.y, m2.y, k.y),
+                       dy1(v.z, mu.z, is.z, g.z, b.z, d.z, relu, m1.z, m2.z, k.z),
+                       dy1(v.w, mu.w, is.w, g.w, b.w, d.w, relu, m1.w, m2.w, k.w));
+  }
+};
+
 // train mode: dy = gamma*invstd*(dz - sum(dz)/P - xhat*sum(dz*xhat)/P); eval mode (flags bit 1: the
 // normalisation used the running statistics, constants w.r.t. the input): dy = gamma*invstd*dz.
 // Partial column sums of dy (conv bias grad).  flags bit 0: ReLU after the BN.
@@ -496,12 +451,12 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
   thread_rc(C, &c4, &r0, &rs);
   const int active = (C >> 2) * rs;
   const int c = c4 * 4;
-  float4 sb = make_float4(0.f, 0.f, 0.f, 0.f);
+  float4 sb = zero4();
   if ((int)threadIdx.x < active) {
-    const float4 mu = *reinterpret_cast<const float4*>(mean + c);
-    const float4 is = *reinterpret_cast<const float4*>(invstd + c);
-    const float4 g = *reinterpret_cast<const float4*>(gamma + c);
-    const float4 b = *reinterpret_cast<const float4*>(beta + c);
+    const float4 mu = ld4(mean + c);
+    const float4 is = ld4(invstd + c);
+    const float4 g = ld4(gamma + c);
+    const float4 b = ld4(beta + c);
     const double invP = (relu & 2) ? 0.0 : 1.0 / (double)P;
     float4 m1, m2, k;
     m1.x = (float)(sdz[c] * invP); m1.y = (float)(sdz[c + 1] * invP);
@@ -511,18 +466,12 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
     k.x = g.x * is.x; k.y = g.y * is.y; k.z = g.z * is.z; k.w = g.w * is.w;
     const long long pb = (long long)blockIdx.x * rows_per_blk;
     const long long pe = min(P, pb + rows_per_blk);
+    const BnBwdDy f{mu, is, g, b, m1, m2, k};
     auto row = [&](long long p, const float4& v, const float4& d) {
-      float4 o;
-      float xh, dz;
-#define BN_APPLY(X)                                            \
-  xh = (v.X - mu.X) * is.X;                                    \
-  dz = (!(relu & 1) || xh * g.X + b.X > 0.f) ? d.X : 0.f;      \
-  o.X = (dz - m1.X - xh * m2.X) * k.X;                         \
-  sb.X += o.X;
-      BN_APPLY(x) BN_APPLY(y) BN_APPLY(z) BN_APPLY(w)
-#undef BN_APPLY
-      *reinterpret_cast<float4*>(dy + p * lddy + c) = o;
-      mx = fmaxf(mx, fmaxf(fmaxf(fabsf(o.x), fabsf(o.y)), fmaxf(fabsf(o.z), fabsf(o.w))));
+      const float4 o = f.dy4(v, d, relu);
+      sb = add4(sb, o);
+      st4(dy + p * lddy + c, o);
+      mx = fmaxf(mx, absmax4(o));
     };
     bn_rows(pb + r0, pe, rs, y, ldy, da, ldda, c, row);
   }
@@ -531,14 +480,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
   red4[threadIdx.x] = sb;
   __syncthreads();
   if ((int)threadIdx.x < (C >> 2)) {
-    float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int r = 0; r < rs; ++r) {
-      const float4 a = red4[r * (C >> 2) + threadIdx.x];
-      t.x += a.x; t.y += a.y; t.z += a.z; t.w += a.w;
-    }
-    float2* o = bias_part + (size_t)blockIdx.x * C + c;
-    o[0] = make_float2(t.x, 0.f); o[1] = make_float2(t.y, 0.f);
-    o[2] = make_float2(t.z, 0.f); o[3] = make_float2(t.w, 0.f);
+    store_part4(bias_part + (size_t)blockIdx.x * C + c, rowsum4(red4, C >> 2, rs, threadIdx.x), zero4());
   }
 }
 
@@ -576,23 +518,18 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_split_kernel(const float* __
     }
     return;
   }
-  const float4 mu = *reinterpret_cast<const float4*>(mean + c);
-  const float4 is = *reinterpret_cast<const float4*>(invstd + c);
-  const float4 g = *reinterpret_cast<const float4*>(gamma + c);
-  const float4 b = *reinterpret_cast<const float4*>(beta + c);
-  const float4 m1 = *reinterpret_cast<const float4*>(m1v + c);
-  const float4 m2 = *reinterpret_cast<const float4*>(m2v + c);
+  const float4 mu = ld4(mean + c);
+  const float4 is = ld4(invstd + c);
+  const float4 g = ld4(gamma + c);
+  const float4 b = ld4(beta + c);
+  const float4 m1 = ld4(m1v + c);
+  const float4 m2 = ld4(m2v + c);
   const float4 k = make_float4(g.x * is.x, g.y * is.y, g.z * is.z, g.w * is.w);
   const float s = exp2i(h3_exp(*dy_amax));
+  const BnBwdDy f{mu, is, g, b, m1, m2, k};
   auto row = [&](long long p, const float4& v, const float4& d) {
-    float o[4];
-    float xh, dz;
-#define BN_APPLY_S(I, X)                                       \
-  xh = (v.X - mu.X) * is.X;                                    \
-  dz = (!(relu & 1) || xh * g.X + b.X > 0.f) ? d.X : 0.f;      \
-  o[I] = (dz - m1.X - xh * m2.X) * k.X;
-    BN_APPLY_S(0, x) BN_APPLY_S(1, y) BN_APPLY_S(2, z) BN_APPLY_S(3, w)
-#undef BN_APPLY_S
+    const float4 dy = f.dy4(v, d, relu);
+    const float o[4] = {dy.x, dy.y, dy.z, dy.w};
     half4 hi, lo;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {   // conv_h3.hip split2h: hi = fp16(x s), lo = fp16(x s - hi)
@@ -675,31 +612,21 @@ __global__ __launch_bounds__(256) void bn_relu_pool_fwd_kernel(const float* __re
     const long long nb = t / Ho;
     const long long p00 = (nb * H + 2 * oy) * W + 2 * ox;
     const long long pp[4] = {p00, p00 + 1, p00 + W, p00 + W + 1};
-    const float4 mu = *reinterpret_cast<const float4*>(mean + c);
-    const float4 is = *reinterpret_cast<const float4*>(invstd + c);
-    const float4 g = *reinterpret_cast<const float4*>(gamma + c);
-    const float4 b = *reinterpret_cast<const float4*>(beta + c);
+    const float4 mu = ld4(mean + c);
+    const float4 is = ld4(invstd + c);
+    const float4 g = ld4(gamma + c);
+    const float4 b = ld4(beta + c);
     float4 o[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      const float4 v = *reinterpret_cast<const float4*>(y + pp[k] * ldy + c);
-      float4 r;
-      r.x = (v.x - mu.x) * is.x * g.x + b.x;
-      r.y = (v.y - mu.y) * is.y * g.y + b.y;
-      r.z = (v.z - mu.z) * is.z * g.z + b.z;
-      r.w = (v.w - mu.w) * is.w * g.w + b.w;
-      if (relu) {
-        r.x = fmaxf(r.x, 0.f); r.y = fmaxf(r.y, 0.f); r.z = fmaxf(r.z, 0.f); r.w = fmaxf(r.w, 0.f);
-      }
-      *reinterpret_cast<float4*>(out + pp[k] * ldo + c) = r;
-      mx = fmaxf(mx, fmaxf(fmaxf(fabsf(r.x), fabsf(r.y)), fmaxf(fabsf(r.z), fabsf(r.w))));
+      const float4 v = ld4(y + pp[k] * ldy + c);
+      float4 r = bn_affine4(v, mu, is, g, b);
+      if (relu) r = relu4(r);
+      st4(out + pp[k] * ldo + c, r);
+      mx = fmaxf(mx, absmax4(r));
       o[k] = r;
     }
-    float4 m;
-#define MX(X) { float v = o[0].X; if (o[1].X > v) v = o[1].X; if (o[2].X > v) v = o[2].X; if (o[3].X > v) v = o[3].X; m.X = v; }
-    MX(x) MX(y) MX(z) MX(w)
-#undef MX
-    *reinterpret_cast<float4*>(pool + q * ldp + c) = m;
+    st4(pool + q * ldp + c, max2x2_first(o[0], o[1], o[2], o[3]));
   }
   if (amax) block_amax(mx, amax);
 }
@@ -719,12 +646,12 @@ __global__ __launch_bounds__(256) void bn_relu_pool_att_fwd_kernel(
   __shared__ float ms[256], hs[32];
   const int nb = blockIdx.x, C4 = C >> 2, Wo = W >> 1, Ho = H >> 1, Cr = C >> 3;
   const int c4 = threadIdx.x % C4, rs = 256 / C4, c = 4 * c4;
-  const float4 mu = *reinterpret_cast<const float4*>(mean + c);
-  const float4 is = *reinterpret_cast<const float4*>(invstd + c);
-  const float4 g = *reinterpret_cast<const float4*>(gamma + c);
-  const float4 b = *reinterpret_cast<const float4*>(beta + c);
+  const float4 mu = ld4(mean + c);
+  const float4 is = ld4(invstd + c);
+  const float4 g = ld4(gamma + c);
+  const float4 b = ld4(beta + c);
   float mx = 0.f;
-  float4 sum = make_float4(0.f, 0.f, 0.f, 0.f);
+  float4 sum = zero4();
   const long long pbase = (long long)nb * H * W;
   constexpr int NPX = POOL ? 4 : 1;   // pixels per work item: a pooling window, or one pixel
   for (int q = threadIdx.x / C4; q < (POOL ? Ho * Wo : H * W); q += rs) {
@@ -739,34 +666,20 @@ __global__ __launch_bounds__(256) void bn_relu_pool_att_fwd_kernel(
     float4 o[4];
 #pragma unroll
     for (int k = 0; k < NPX; ++k) {
-      const float4 v = *reinterpret_cast<const float4*>(y + pp[k] * ldy + c);
-      float4 r;
-      r.x = fmaxf((v.x - mu.x) * is.x * g.x + b.x, 0.f);
-      r.y = fmaxf((v.y - mu.y) * is.y * g.y + b.y, 0.f);
-      r.z = fmaxf((v.z - mu.z) * is.z * g.z + b.z, 0.f);
-      r.w = fmaxf((v.w - mu.w) * is.w * g.w + b.w, 0.f);
-      if (out) *reinterpret_cast<float4*>(out + pp[k] * ldo + c) = r;
-      mx = fmaxf(mx, fmaxf(fmaxf(r.x, r.y), fmaxf(r.z, r.w)));
-      sum.x += r.x; sum.y += r.y; sum.z += r.z; sum.w += r.w;
+      const float4 v = ld4(y + pp[k] * ldy + c);
+      const float4 r = relu4(bn_affine4(v, mu, is, g, b));
+      if (out) st4(out + pp[k] * ldo + c, r);
+      mx = fmaxf(mx, max4(r));
+      sum = add4(sum, r);
       o[k] = r;
     }
-    if (POOL) {
-      float4 m;
-#define MX(X) { float v = o[0].X; if (o[1].X > v) v = o[1].X; if (o[2].X > v) v = o[2].X; if (o[3].X > v) v = o[3].X; m.X = v; }
-      MX(x) MX(y) MX(z) MX(w)
-#undef MX
-      *reinterpret_cast<float4*>(pool + ((long long)nb * Ho * Wo + q) * ldp + c) = m;
-    }
+    if (POOL) st4(pool + ((long long)nb * Ho * Wo + q) * ldp + c, max2x2_first(o[0], o[1], o[2], o[3]));
   }
   if (amax) block_amax(mx, amax);
   red4[threadIdx.x] = sum;
   __syncthreads();
   if ((int)threadIdx.x < C4) {
-    float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int r = 0; r < rs; ++r) {
-      const float4 a = red4[r * C4 + threadIdx.x];
-      t.x += a.x; t.y += a.y; t.z += a.z; t.w += a.w;
-    }
+    const float4 t = rowsum4(red4, C4, rs, threadIdx.x);
     const float inv = 1.f / (float)(H * W);
     const int cc = threadIdx.x * 4;
     ms[cc] = t.x * inv; ms[cc + 1] = t.y * inv; ms[cc + 2] = t.z * inv; ms[cc + 3] = t.w * inv;
@@ -803,26 +716,22 @@ __global__ __launch_bounds__(256) void bn_relu_gate_fwd_kernel(const float* __re
   __shared__ float wred[4];
   const int C4 = C >> 2, ppb = 256 / C4, wpp = C4 >> 6;
   const int c = 4 * (threadIdx.x % C4), pl = threadIdx.x / C4, wave = threadIdx.x >> 6;
-  const float4 mu = *reinterpret_cast<const float4*>(mean + c);
-  const float4 is = *reinterpret_cast<const float4*>(invstd + c);
-  const float4 g = *reinterpret_cast<const float4*>(gamma + c);
-  const float4 b = *reinterpret_cast<const float4*>(beta + c);
-  const float4 wv = *reinterpret_cast<const float4*>(wg + c);
+  const float4 mu = ld4(mean + c);
+  const float4 is = ld4(invstd + c);
+  const float4 g = ld4(gamma + c);
+  const float4 b = ld4(beta + c);
+  const float4 wv = ld4(wg + c);
   const float bias = bg[0];
   float mx = 0.f;
   for (long long p0 = (long long)blockIdx.x * ppb; p0 < P; p0 += (long long)gridDim.x * ppb) {
     const long long p = p0 + pl;
     float dot = 0.f;
     if (p < P) {
-      const float4 v = *reinterpret_cast<const float4*>(y + p * ldy + c);
-      float4 r;
-      r.x = fmaxf((v.x - mu.x) * is.x * g.x + b.x, 0.f);
-      r.y = fmaxf((v.y - mu.y) * is.y * g.y + b.y, 0.f);
-      r.z = fmaxf((v.z - mu.z) * is.z * g.z + b.z, 0.f);
-      r.w = fmaxf((v.w - mu.w) * is.w * g.w + b.w, 0.f);
-      if (out) *reinterpret_cast<float4*>(out + p * ldo + c) = r;
-      mx = fmaxf(mx, fmaxf(fmaxf(r.x, r.y), fmaxf(r.z, r.w)));
-      dot = r.x * wv.x + r.y * wv.y + r.z * wv.z + r.w * wv.w;
+      const float4 v = ld4(y + p * ldy + c);
+      const float4 r = relu4(bn_affine4(v, mu, is, g, b));
+      if (out) st4(out + p * ldo + c, r);
+      mx = fmaxf(mx, max4(r));
+      dot = dot4(r, wv);
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) dot += __shfl_xor(dot, o, 64);
@@ -855,12 +764,8 @@ __global__ __launch_bounds__(256) void att_pool_bn_bwd_kernel(
   extern __shared__ float4 red4[];   // [2][256]
   const int C4 = blockDim.x, C = 4 * C4, c = threadIdx.x * 4;
   const unsigned Wo = W >> 1, Ho = H >> 1, HW = (unsigned)(H * W);
-  const float4 mu = *reinterpret_cast<const float4*>(mean + c);
-  const float4 is = *reinterpret_cast<const float4*>(invstd + c);
-  const float4 g = *reinterpret_cast<const float4*>(gamma + c);
-  const float4 b = *reinterpret_cast<const float4*>(beta + c);
-  float4 s1 = make_float4(0.f, 0.f, 0.f, 0.f), s2 = s1;
-  float dmax = 0.f;
+  BnBwdAcc acc;
+  acc.load(mean, invstd, gamma, beta, c);
   for (unsigned q = blockIdx.x * blockDim.y + threadIdx.y; q < npool; q += gridDim.x * blockDim.y) {
     const unsigned ox = q % Wo, t = q / Wo, oy = t % Ho, n = t / Ho;
     const size_t p0 = ((size_t)n * H + 2 * oy) * W + 2 * ox;
@@ -869,72 +774,29 @@ __global__ __launch_bounds__(256) void att_pool_bn_bwd_kernel(
     float sv[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      v[k] = *reinterpret_cast<const float4*>(a + p[k] * lda + c);
-      d[k] = *reinterpret_cast<const float4*>(dout + p[k] * lddo + c);
-      yv[k] = *reinterpret_cast<const float4*>(y + p[k] * ldy + c);
+      v[k] = ld4(a + p[k] * lda + c);
+      d[k] = ld4(dout + p[k] * lddo + c);
+      yv[k] = ld4(y + p[k] * ldy + c);
       sv[k] = sa[p[k]];
     }
-    const float4 gp = *reinterpret_cast<const float4*>(dp + (size_t)q * lddp + c);
-    const float4 cav = *reinterpret_cast<const float4*>(ca + (size_t)n * C + c);
-    const float4 dmv = *reinterpret_cast<const float4*>(dm + (size_t)n * C + c);
+    const float4 gp = ld4(dp + (size_t)q * lddp + c);
+    const float4 cav = ld4(ca + (size_t)n * C + c);
+    const float4 dmv = ld4(dm + (size_t)n * C + c);
     (void)HW;
     float4 o[4];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const float s = sv[k];
-      o[k].x = (d[k].x * s) * cav.x + dmv.x; o[k].y = (d[k].y * s) * cav.y + dmv.y;
-      o[k].z = (d[k].z * s) * cav.z + dmv.z; o[k].w = (d[k].w * s) * cav.w + dmv.w;
-    }
-    // (the routed add by selects, not o[am]: a dynamic index put o in scratch)
-#define ARG(X)                                                     \
-  {                                                                \
-    int am = 0; float mv = v[0].X;                                 \
-    if (v[1].X > mv) { mv = v[1].X; am = 1; }                      \
-    if (v[2].X > mv) { mv = v[2].X; am = 2; }                      \
-    if (v[3].X > mv) { mv = v[3].X; am = 3; }                      \
-    o[0].X = am == 0 ? o[0].X + gp.X : o[0].X;                     \
-    o[1].X = am == 1 ? o[1].X + gp.X : o[1].X;                     \
-    o[2].X = am == 2 ? o[2].X + gp.X : o[2].X;                     \
-    o[3].X = am == 3 ? o[3].X + gp.X : o[3].X;                     \
-  }
-    ARG(x) ARG(y) ARG(z) ARG(w)
-#undef ARG
+    for (int k = 0; k < 4; ++k) o[k] = gate_dx4(d[k], sv[k], cav, dmv);
+    route_argmax_select(v, gp, o);   // (not route_argmax: its dynamic index put o in scratch)
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      *reinterpret_cast<float4*>(de + p[k] * ldde + c) = o[k];
-      dmax = fmaxf(dmax, fmaxf(fmaxf(fabsf(o[k].x), fabsf(o[k].y)), fmaxf(fabsf(o[k].z), fabsf(o[k].w))));
-      float xh, dz;
-#define BN_ACC(X)                                              \
-  xh = (yv[k].X - mu.X) * is.X;                                \
-  dz = (xh * g.X + b.X > 0.f) ? o[k].X : 0.f;                  \
-  s1.X += dz;                                                  \
-  s2.X += dz * xh;
-      BN_ACC(x) BN_ACC(y) BN_ACC(z) BN_ACC(w)
-#undef BN_ACC
+      st4(de + p[k] * ldde + c, o[k]);
+      acc.amax(o[k]);
+      acc.add<true>(yv[k], o[k]);
     }
   }
   const int tid = threadIdx.y * C4 + threadIdx.x;
-  red4[tid] = s1;
-  red4[256 + tid] = s2;
-  __syncthreads();
-  if (threadIdx.y == 0) {
-    float4 t1 = make_float4(0.f, 0.f, 0.f, 0.f), t2 = t1;
-    for (int r = 0; r < (int)blockDim.y; ++r) {
-      const float4 u1 = red4[r * C4 + threadIdx.x], u2 = red4[256 + r * C4 + threadIdx.x];
-      t1.x += u1.x; t1.y += u1.y; t1.z += u1.z; t1.w += u1.w;
-      t2.x += u2.x; t2.y += u2.y; t2.z += u2.z; t2.w += u2.w;
-    }
-    float2* o2 = part + (size_t)blockIdx.x * C + c;
-    o2[0] = make_float2(t1.x, t2.x); o2[1] = make_float2(t1.y, t2.y);
-    o2[2] = make_float2(t1.z, t2.z); o2[3] = make_float2(t1.w, t2.w);
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) dmax = fmaxf(dmax, __shfl_xor(dmax, o, 64));
-  __syncthreads();
-  float* wmx = reinterpret_cast<float*>(red4);
-  if ((tid & 63) == 0) wmx[tid >> 6] = dmax;
-  __syncthreads();
-  if (tid == 0) da_max[blockIdx.x] = fmaxf(fmaxf(wmx[0], wmx[1]), fmaxf(wmx[2], wmx[3]));
+  bn_bwd_block_combine(red4, tid, threadIdx.y == 0, threadIdx.x, C4, (int)blockDim.y, acc,
+                       part + (size_t)blockIdx.x * C + c, true, da_max + blockIdx.x);
 }
 
 static int att_pool_blocks(int n, int h, int w, int c) {

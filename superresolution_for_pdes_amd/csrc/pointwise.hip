@@ -4,8 +4,7 @@
 //
 // Reference anchors (src/models.py): pool :69,:79-80; up :70,:89-93; AttentionGate
 // :103-130; final 1x1 + residual :61,:74,:98,:101; nn.MSELoss src/train_enhanced.py:307.
-#include "common.h"
-#include "resample.h"
+#include "bn_reduce.h"
 
 namespace srpde {
 
@@ -49,8 +48,44 @@ __global__ void axpy_channel_kernel(float* __restrict__ y, const float* __restri
   }
 }
 
+// Each vector op below has a grid-stride kernel (any C % 4 == 0: a 64-bit element index divided per float4) and a
+// pixel-blocked one (C / 4 a power of two <= 256, further down); a pair shares one body, templated on the type I
+// its pixel indices multiply in: long long, or the pixel-blocked kernels' size_t over 32-bit products.
+template <typename I>
+__device__ __forceinline__ I tap_index(int i, int W, int j) {   // pixel (i, j) of a W-wide sample
+  if constexpr (sizeof(I) == sizeof(size_t) && !std::is_signed<I>::value) return (I)(i * W + j);
+  else return (I)i * W + j;
+}
+
 // --------------------------------- max pool ------------------------------------
 // nn.MaxPool2d(2): first maximum in (0,0),(0,1),(1,0),(1,1) order wins (strict >), as aten.
+// window q with top-left pixel p00, channel quad c
+template <typename I>
+__device__ __forceinline__ void maxpool2_fwd_body(const float* __restrict__ x, int ldx, float* __restrict__ out,
+                                                  int ldo, I p00, I q, int W, int c) {
+  const float4 a = ld4(x + p00 * ldx + c);
+  const float4 b = ld4(x + (p00 + 1) * ldx + c);
+  const float4 d = ld4(x + (p00 + W) * ldx + c);
+  const float4 f = ld4(x + (p00 + W + 1) * ldx + c);
+  st4(out + q * ldo + c, max2x2_first(a, b, d, f));
+}
+
+template <typename I>
+__device__ __forceinline__ void maxpool2_bwd_body(const float* __restrict__ x, int ldx, const float* __restrict__ dout,
+                                                  int lddo, float* __restrict__ dx, int lddx, I p0, I q, int W, int c,
+                                                  int accumulate) {
+  const I p[4] = {p0, p0 + 1, p0 + W, p0 + W + 1};
+  float4 v[4], o[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) v[k] = ld4(x + p[k] * ldx + c);
+  const float4 g = ld4(dout + q * lddo + c);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) o[k] = accumulate ? ld4(dx + p[k] * lddx + c) : zero4();
+  route_argmax(v, g, o);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) st4(dx + p[k] * lddx + c, o[k]);
+}
+
 __global__ void maxpool2_fwd_kernel(const float* __restrict__ x, int ldx, float* __restrict__ out, int ldo, int N,
                                     int H, int W, int C) {
   const int Ho = H >> 1, Wo = W >> 1, C4 = C >> 2;
@@ -63,16 +98,7 @@ __global__ void maxpool2_fwd_kernel(const float* __restrict__ x, int ldx, float*
     const long long t = q / Wo;
     const int oy = (int)(t % Ho);
     const long long n = t / Ho;
-    const long long p00 = (n * H + 2 * oy) * W + 2 * ox;
-    const float4 a = *reinterpret_cast<const float4*>(x + p00 * ldx + c);
-    const float4 b = *reinterpret_cast<const float4*>(x + (p00 + 1) * ldx + c);
-    const float4 d = *reinterpret_cast<const float4*>(x + (p00 + W) * ldx + c);
-    const float4 f = *reinterpret_cast<const float4*>(x + (p00 + W + 1) * ldx + c);
-    float4 m;
-#define MX(X) { float v = a.X; if (b.X > v) v = b.X; if (d.X > v) v = d.X; if (f.X > v) v = f.X; m.X = v; }
-    MX(x) MX(y) MX(z) MX(w)
-#undef MX
-    *reinterpret_cast<float4*>(out + q * ldo + c) = m;
+    maxpool2_fwd_body<long long>(x, ldx, out, ldo, (n * H + 2 * oy) * W + 2 * ox, q, W, c);
   }
 }
 
@@ -88,34 +114,23 @@ __global__ void maxpool2_bwd_kernel(const float* __restrict__ x, int ldx, const 
     const long long t = q / Wo;
     const int oy = (int)(t % Ho);
     const long long n = t / Ho;
-    const long long p[4] = {(n * H + 2 * oy) * W + 2 * ox, (n * H + 2 * oy) * W + 2 * ox + 1,
-                            (n * H + 2 * oy + 1) * W + 2 * ox, (n * H + 2 * oy + 1) * W + 2 * ox + 1};
-    float4 v[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = *reinterpret_cast<const float4*>(x + p[k] * ldx + c);
-    const float4 g = *reinterpret_cast<const float4*>(dout + q * lddo + c);
-    float4 o[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      if (accumulate) o[k] = *reinterpret_cast<const float4*>(dx + p[k] * lddx + c);
-      else o[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-#define ARG(X)                                                     \
-  {                                                                \
-    int am = 0; float mv = v[0].X;                                 \
-    if (v[1].X > mv) { mv = v[1].X; am = 1; }                      \
-    if (v[2].X > mv) { mv = v[2].X; am = 2; }                      \
-    if (v[3].X > mv) { mv = v[3].X; am = 3; }                      \
-    o[am].X += g.X;                                                \
-  }
-    ARG(x) ARG(y) ARG(z) ARG(w)
-#undef ARG
-#pragma unroll
-    for (int k = 0; k < 4; ++k) *reinterpret_cast<float4*>(dx + p[k] * lddx + c) = o[k];
+    maxpool2_bwd_body<long long>(x, ldx, dout, lddo, dx, lddx, (n * H + 2 * oy) * W + 2 * ox, q, W, c, accumulate);
   }
 }
 
 // ----------------------------- bilinear upsample x2 ------------------------------
+// output pixel (oy, ox) -> o; base: the sample's first pixel at the thread's channel quad
+template <typename I>
+__device__ __forceinline__ void upsample_fwd_body(const float* __restrict__ base, int ldx, float* __restrict__ o, int oy,
+                                                  int ox, int H, int W, int Ho, int Wo) {
+  const Lerp ly = lerp_index(oy, H, Ho), lx = lerp_index(ox, W, Wo);
+  const float4 a = ld4(base + tap_index<I>(ly.i0, W, lx.i0) * ldx);
+  const float4 b = ld4(base + tap_index<I>(ly.i0, W, lx.i1) * ldx);
+  const float4 d = ld4(base + tap_index<I>(ly.i1, W, lx.i0) * ldx);
+  const float4 f = ld4(base + tap_index<I>(ly.i1, W, lx.i1) * ldx);
+  st4(o, bilerp4(ly, lx, a, b, d, f));
+}
+
 __global__ void upsample_fwd_kernel(const float* __restrict__ x, int ldx, float* __restrict__ out, int ldo, int N,
                                     int H, int W, int Ho, int Wo, int C) {
   const int C4 = C >> 2;
@@ -128,17 +143,7 @@ __global__ void upsample_fwd_kernel(const float* __restrict__ x, int ldx, float*
     const long long t = q / Wo;
     const int oy = (int)(t % Ho);
     const long long n = t / Ho;
-    const Lerp ly = lerp_index(oy, H, Ho), lx = lerp_index(ox, W, Wo);
-    const float* base = x + n * H * W * (long long)ldx;
-    const float4 a = *reinterpret_cast<const float4*>(base + ((long long)ly.i0 * W + lx.i0) * ldx + c);
-    const float4 b = *reinterpret_cast<const float4*>(base + ((long long)ly.i0 * W + lx.i1) * ldx + c);
-    const float4 d = *reinterpret_cast<const float4*>(base + ((long long)ly.i1 * W + lx.i0) * ldx + c);
-    const float4 f = *reinterpret_cast<const float4*>(base + ((long long)ly.i1 * W + lx.i1) * ldx + c);
-    float4 o;
-#define UP(X) o.X = ly.l0 * (lx.l0 * a.X + lx.l1 * b.X) + ly.l1 * (lx.l0 * d.X + lx.l1 * f.X);
-    UP(x) UP(y) UP(z) UP(w)
-#undef UP
-    *reinterpret_cast<float4*>(out + q * ldo + c) = o;
+    upsample_fwd_body<long long>(x + n * H * W * (long long)ldx + c, ldx, out + q * ldo + c, oy, ox, H, W, Ho, Wo);
   }
 }
 
@@ -211,6 +216,30 @@ __device__ __forceinline__ int gather_weights(int i, int in, int out, int* idx, 
   return cnt;
 }
 
+// input pixel (iy, ix) -> o.  base: the sample's first output pixel at the thread's channel quad; sbase / wv: the
+// sample's dsa and the quad's wg when the attention gating gradient dsa[q] * wg[c] joins dout (else null)
+template <typename I>
+__device__ __forceinline__ void upsample_bwd_body(const float* __restrict__ base, int lddo, float* __restrict__ o, int iy,
+                                                  int ix, int H, int W, int Ho, int Wo, int accumulate,
+                                                  const float* __restrict__ sbase, const float4& wv) {
+  int oyi[8], oxi[8];
+  float wy[8], wx[8];
+  const int ny = gather_weights(iy, H, Ho, oyi, wy);
+  const int nx = gather_weights(ix, W, Wo, oxi, wx);
+  float4 s = zero4();
+  for (int a = 0; a < ny; ++a) {
+    float4 r = zero4();
+    for (int b = 0; b < nx; ++b) {
+      float4 g = ld4(base + tap_index<I>(oyi[a], Wo, oxi[b]) * lddo);
+      if (sbase != nullptr) g = scale_add4(sbase[oyi[a] * Wo + oxi[b]], wv, g);
+      r = fma4(r, wx[b], g);
+    }
+    s = fma4(s, wy[a], r);
+  }
+  if (accumulate) s = add4(s, ld4(o));
+  st4(o, s);
+}
+
 __global__ void upsample_bwd_kernel(const float* __restrict__ dout, int lddo, float* __restrict__ dx, int lddx,
                                     int N, int H, int W, int Ho, int Wo, int C, int accumulate) {
   const int C4 = C >> 2;
@@ -223,26 +252,8 @@ __global__ void upsample_bwd_kernel(const float* __restrict__ dout, int lddo, fl
     const long long t = q / W;
     const int iy = (int)(t % H);
     const long long n = t / H;
-    int oyi[8], oxi[8];
-    float wy[8], wx[8];
-    const int ny = gather_weights(iy, H, Ho, oyi, wy);
-    const int nx = gather_weights(ix, W, Wo, oxi, wx);
-    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-    const float* base = dout + n * Ho * Wo * (long long)lddo;
-    for (int a = 0; a < ny; ++a) {
-      float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
-      for (int b = 0; b < nx; ++b) {
-        const float4 g = *reinterpret_cast<const float4*>(base + ((long long)oyi[a] * Wo + oxi[b]) * lddo + c);
-        r.x += wx[b] * g.x; r.y += wx[b] * g.y; r.z += wx[b] * g.z; r.w += wx[b] * g.w;
-      }
-      s.x += wy[a] * r.x; s.y += wy[a] * r.y; s.z += wy[a] * r.z; s.w += wy[a] * r.w;
-    }
-    float* o = dx + q * lddx + c;
-    if (accumulate) {
-      const float4 old = *reinterpret_cast<const float4*>(o);
-      s.x += old.x; s.y += old.y; s.z += old.z; s.w += old.w;
-    }
-    *reinterpret_cast<float4*>(o) = s;
+    upsample_bwd_body<long long>(dout + n * Ho * Wo * (long long)lddo + c, lddo, dx + q * lddx + c, iy, ix, H, W, Ho,
+                                 Wo, accumulate, nullptr, zero4());
   }
 }
 
@@ -258,17 +269,7 @@ __global__ __launch_bounds__(256) void maxpool2_fwd_px_kernel(const float* __res
   if (q >= npix) return;
   const unsigned Wo = W >> 1, Ho = H >> 1;
   const unsigned ox = q % Wo, t = q / Wo, oy = t % Ho, n = t / Ho;
-  const int c = threadIdx.x * 4;
-  const size_t p00 = ((size_t)n * H + 2 * oy) * W + 2 * ox;
-  const float4 a = *reinterpret_cast<const float4*>(x + p00 * ldx + c);
-  const float4 b = *reinterpret_cast<const float4*>(x + (p00 + 1) * ldx + c);
-  const float4 d = *reinterpret_cast<const float4*>(x + (p00 + W) * ldx + c);
-  const float4 f = *reinterpret_cast<const float4*>(x + (p00 + W + 1) * ldx + c);
-  float4 m;
-#define MX(X) { float v = a.X; if (b.X > v) v = b.X; if (d.X > v) v = d.X; if (f.X > v) v = f.X; m.X = v; }
-  MX(x) MX(y) MX(z) MX(w)
-#undef MX
-  *reinterpret_cast<float4*>(out + (size_t)q * ldo + c) = m;
+  maxpool2_fwd_body<size_t>(x, ldx, out, ldo, ((size_t)n * H + 2 * oy) * W + 2 * ox, q, W, threadIdx.x * 4);
 }
 
 __global__ __launch_bounds__(256) void maxpool2_bwd_px_kernel(const float* __restrict__ x, int ldx,
@@ -279,28 +280,8 @@ __global__ __launch_bounds__(256) void maxpool2_bwd_px_kernel(const float* __res
   if (q >= npix) return;
   const unsigned Wo = W >> 1, Ho = H >> 1;
   const unsigned ox = q % Wo, t = q / Wo, oy = t % Ho, n = t / Ho;
-  const int c = threadIdx.x * 4;
-  const size_t p0 = ((size_t)n * H + 2 * oy) * W + 2 * ox;
-  const size_t p[4] = {p0, p0 + 1, p0 + W, p0 + W + 1};
-  float4 v[4], o[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) v[k] = *reinterpret_cast<const float4*>(x + p[k] * ldx + c);
-  const float4 g = *reinterpret_cast<const float4*>(dout + (size_t)q * lddo + c);
-#pragma unroll
-  for (int k = 0; k < 4; ++k)
-    o[k] = accumulate ? *reinterpret_cast<const float4*>(dx + p[k] * lddx + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-#define ARG(X)                                                     \
-  {                                                                \
-    int am = 0; float mv = v[0].X;                                 \
-    if (v[1].X > mv) { mv = v[1].X; am = 1; }                      \
-    if (v[2].X > mv) { mv = v[2].X; am = 2; }                      \
-    if (v[3].X > mv) { mv = v[3].X; am = 3; }                      \
-    o[am].X += g.X;                                                \
-  }
-  ARG(x) ARG(y) ARG(z) ARG(w)
-#undef ARG
-#pragma unroll
-  for (int k = 0; k < 4; ++k) *reinterpret_cast<float4*>(dx + p[k] * lddx + c) = o[k];
+  maxpool2_bwd_body<size_t>(x, ldx, dout, lddo, dx, lddx, ((size_t)n * H + 2 * oy) * W + 2 * ox, q, W, threadIdx.x * 4,
+                            accumulate);
 }
 
 __global__ __launch_bounds__(256) void upsample_fwd_px_kernel(const float* __restrict__ x, int ldx, float* __restrict__ out,
@@ -309,19 +290,8 @@ __global__ __launch_bounds__(256) void upsample_fwd_px_kernel(const float* __res
   if (q >= npix) return;
   const unsigned ox = q % (unsigned)Wo, t = q / (unsigned)Wo, oy = t % (unsigned)Ho, n = t / (unsigned)Ho;
   const int c = threadIdx.x * 4;
-  const Lerp ly = lerp_index(oy, H, Ho), lx = lerp_index(ox, W, Wo);
-  const float* base = x + (size_t)n * H * W * ldx + c;
-  const float4 a = *reinterpret_cast<const float4*>(base + (size_t)(ly.i0 * W + lx.i0) * ldx);
-  const float4 b = *reinterpret_cast<const float4*>(base + (size_t)(ly.i0 * W + lx.i1) * ldx);
-  const float4 d = *reinterpret_cast<const float4*>(base + (size_t)(ly.i1 * W + lx.i0) * ldx);
-  const float4 f = *reinterpret_cast<const float4*>(base + (size_t)(ly.i1 * W + lx.i1) * ldx);
-  float4 o;
-#define UP(X) o.X = ly.l0 * (lx.l0 * a.X + lx.l1 * b.X) + ly.l1 * (lx.l0 * d.X + lx.l1 * f.X);
-  UP(x) UP(y) UP(z) UP(w)
-#undef UP
-  *reinterpret_cast<float4*>(out + (size_t)q * ldo + c) = o;
+  upsample_fwd_body<size_t>(x + (size_t)n * H * W * ldx + c, ldx, out + (size_t)q * ldo + c, oy, ox, H, W, Ho, Wo);
 }
-
 
 // upsample_fwd_px_kernel plus the spatial attention of the gate that reads the upsampled tensor
 // (models.py:124-125: sa = sigmoid(conv1x1(g)) with g = up(d), models.py:89,92): the block's x
@@ -338,7 +308,7 @@ __global__ __launch_bounds__(256) void upsample_gate_fwd_px_kernel(const float* 
                                                                    const float* __restrict__ bg,
                                                                    float* __restrict__ sa) {
   const int c = threadIdx.x * 4;
-  const float4 wv = *reinterpret_cast<const float4*>(wg + c);
+  const float4 wv = ld4(wg + c);
   const float bias = bg[0];
   float4 a[UPX], b[UPX], d[UPX], f[UPX];
   Lerp ly[UPX], lx[UPX];
@@ -350,21 +320,18 @@ __global__ __launch_bounds__(256) void upsample_gate_fwd_px_kernel(const float* 
     ly[u] = lerp_index(oy, H, Ho);
     lx[u] = lerp_index(ox, W, Wo);
     const float* base = x + (size_t)n * H * W * ldx + c;
-    a[u] = *reinterpret_cast<const float4*>(base + (size_t)(ly[u].i0 * W + lx[u].i0) * ldx);
-    b[u] = *reinterpret_cast<const float4*>(base + (size_t)(ly[u].i0 * W + lx[u].i1) * ldx);
-    d[u] = *reinterpret_cast<const float4*>(base + (size_t)(ly[u].i1 * W + lx[u].i0) * ldx);
-    f[u] = *reinterpret_cast<const float4*>(base + (size_t)(ly[u].i1 * W + lx[u].i1) * ldx);
+    a[u] = ld4(base + (size_t)(ly[u].i0 * W + lx[u].i0) * ldx);
+    b[u] = ld4(base + (size_t)(ly[u].i0 * W + lx[u].i1) * ldx);
+    d[u] = ld4(base + (size_t)(ly[u].i1 * W + lx[u].i0) * ldx);
+    f[u] = ld4(base + (size_t)(ly[u].i1 * W + lx[u].i1) * ldx);
   }
 #pragma unroll
   for (int u = 0; u < UPX; ++u) {
     const unsigned q = (blockIdx.x * UPX + u) * blockDim.y + threadIdx.y;
     const bool on = q < npix;
-    float4 o;
-#define UP(X) o.X = ly[u].l0 * (lx[u].l0 * a[u].X + lx[u].l1 * b[u].X) + ly[u].l1 * (lx[u].l0 * d[u].X + lx[u].l1 * f[u].X);
-    UP(x) UP(y) UP(z) UP(w)
-#undef UP
-    if (on) *reinterpret_cast<float4*>(out + (size_t)q * ldo + c) = o;
-    float acc = o.x * wv.x + o.y * wv.y + o.z * wv.z + o.w * wv.w;
+    const float4 o = bilerp4(ly[u], lx[u], a[u], b[u], d[u], f[u]);
+    if (on) st4(out + (size_t)q * ldo + c, o);
+    float acc = dot4(o, wv);
     for (int off = 1; off < (int)blockDim.x; off <<= 1) acc += __shfl_xor(acc, off, 64);
     if (on && threadIdx.x == 0) sa[q] = 1.f / (1.f + expf(-(acc + bias)));
   }
@@ -379,9 +346,9 @@ __global__ __launch_bounds__(256) void gate_dot_px_kernel(const float* __restric
   const unsigned q = px_index();
   const bool on = q < npix;
   const int c = threadIdx.x * 4;
-  const float4 wv = *reinterpret_cast<const float4*>(wg + c);
-  const float4 o = on ? *reinterpret_cast<const float4*>(x + (size_t)q * ldx + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-  float acc = o.x * wv.x + o.y * wv.y + o.z * wv.z + o.w * wv.w;
+  const float4 wv = ld4(wg + c);
+  const float4 o = on ? ld4(x + (size_t)q * ldx + c) : zero4();
+  float acc = dot4(o, wv);
   for (int off = 1; off < (int)blockDim.x; off <<= 1) acc += __shfl_xor(acc, off, 64);
   if (on && threadIdx.x == 0) t[q] = acc;
 }
@@ -410,32 +377,10 @@ __global__ __launch_bounds__(256) void upsample_bwd_px_kernel(const float* __res
   if (q >= npix) return;
   const unsigned ix = q % (unsigned)W, t = q / (unsigned)W, iy = t % (unsigned)H, n = t / (unsigned)H;
   const int c = threadIdx.x * 4;
-  int oyi[8], oxi[8];
-  float wy[8], wx[8];
-  const int ny = gather_weights(iy, H, Ho, oyi, wy);
-  const int nx = gather_weights(ix, W, Wo, oxi, wx);
-  float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-  const float* base = dout + (size_t)n * Ho * Wo * lddo + c;
-  const float4 wv = gw != nullptr ? *reinterpret_cast<const float4*>(gw + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+  const float4 wv = gw != nullptr ? ld4(gw + c) : zero4();
   const float* sbase = gsa != nullptr ? gsa + (size_t)n * Ho * Wo : nullptr;
-  for (int a = 0; a < ny; ++a) {
-    float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int b = 0; b < nx; ++b) {
-      float4 g = *reinterpret_cast<const float4*>(base + (size_t)(oyi[a] * Wo + oxi[b]) * lddo);
-      if (sbase != nullptr) {
-        const float sv = sbase[oyi[a] * Wo + oxi[b]];
-        g.x = sv * wv.x + g.x; g.y = sv * wv.y + g.y; g.z = sv * wv.z + g.z; g.w = sv * wv.w + g.w;
-      }
-      r.x += wx[b] * g.x; r.y += wx[b] * g.y; r.z += wx[b] * g.z; r.w += wx[b] * g.w;
-    }
-    s.x += wy[a] * r.x; s.y += wy[a] * r.y; s.z += wy[a] * r.z; s.w += wy[a] * r.w;
-  }
-  float* o = dx + (size_t)q * lddx + c;
-  if (accumulate) {
-    const float4 old = *reinterpret_cast<const float4*>(o);
-    s.x += old.x; s.y += old.y; s.z += old.z; s.w += old.w;
-  }
-  *reinterpret_cast<float4*>(o) = s;
+  upsample_bwd_body<size_t>(dout + (size_t)n * Ho * Wo * lddo + c, lddo, dx + (size_t)q * lddx + c, iy, ix, H, W, Ho, Wo,
+                            accumulate, sbase, wv);
 }
 
 // Row-blocked upsample backward: one workgroup per (sample, input row iy), all channels.  Phase 1
@@ -484,7 +429,7 @@ __device__ __forceinline__ void upsample_rows_phase1(const float* __restrict__ d
     const float w = oy0 + a <= hi ? cand_weight(oy0 + a, iy, H, Ho, &hit) : 0.f;
     wy[a] = hit ? w : 0.f;
   }
-  const float4 wv = GATED ? *reinterpret_cast<const float4*>(gw + cq * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+  const float4 wv = GATED ? ld4(gw + cq * 4) : zero4();
   const float* base = dout + (size_t)n * Ho * Wo * lddo + cq * 4;
   const float* sb = GATED ? gsa + (size_t)n * Ho * Wo : nullptr;
   for (int ox = lx0; ox < Wo; ox += nlx) {
@@ -493,17 +438,15 @@ __device__ __forceinline__ void upsample_rows_phase1(const float* __restrict__ d
 #pragma unroll
     for (int a = 0; a < NSL; ++a) {
       const int o = (oy0 + a <= hi ? oy0 + a : oy0) * Wo + ox;
-      g[a] = *reinterpret_cast<const float4*>(base + (size_t)o * lddo);
+      g[a] = ld4(base + (size_t)o * lddo);
       if constexpr (GATED) sv[a] = sb[o];
     }
-    float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 r = zero4();
 #pragma unroll
     for (int a = 0; a < NSL; ++a) {   // zero-weight slots add nothing (0 * finite)
       float4 gg = g[a];
-      if constexpr (GATED) {
-        gg.x = sv[a] * wv.x + gg.x; gg.y = sv[a] * wv.y + gg.y; gg.z = sv[a] * wv.z + gg.z; gg.w = sv[a] * wv.w + gg.w;
-      }
-      r.x += wy[a] * gg.x; r.y += wy[a] * gg.y; r.z += wy[a] * gg.z; r.w += wy[a] * gg.w;
+      if constexpr (GATED) gg = scale_add4(sv[a], wv, gg);
+      r = fma4(r, wy[a], gg);
     }
     rrow[ox * C4 + cq] = r;
   }
@@ -558,69 +501,41 @@ __global__ __launch_bounds__(256) void upsample_bwd_rows_kernel(const float* __r
   else if (nrow == 5) upsample_rows_phase1<GATED, 5>(dout, lddo, Ho, Wo, C4, n, iy, H, oy0, hi, gsa, gw, rrow);
   else upsample_rows_phase1<GATED, ROWS_NS>(dout, lddo, Ho, Wo, C4, n, iy, H, oy0, hi, gsa, gw, rrow);
   __syncthreads();
-  float4 mu, is, g, b, s1 = make_float4(0.f, 0.f, 0.f, 0.f), s2 = s1;
-  float dmax = 0.f;
-  if constexpr (BN) {
-    mu = *reinterpret_cast<const float4*>(bn.mean + cq * 4);
-    is = *reinterpret_cast<const float4*>(bn.invstd + cq * 4);
-    g = *reinterpret_cast<const float4*>(bn.gamma + cq * 4);
-    b = *reinterpret_cast<const float4*>(bn.beta + cq * 4);
-  }
+  BnBwdAcc acc;
+  if constexpr (BN) acc.load(bn.mean, bn.invstd, bn.gamma, bn.beta, cq * 4);
   for (int ix = lx0; ix < W; ix += nlx) {
     int xlo, xhi;
     cand_range(ix, W, Wo, &xlo, &xhi);
-    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 s = zero4();
     for (int o = xlo; o <= xhi; ++o) {
       bool hit;
       const float w = cand_weight(o, ix, W, Wo, &hit);
-      if (hit) {
-        const float4 r = rrow[o * C4 + cq];
-        s.x += w * r.x; s.y += w * r.y; s.z += w * r.z; s.w += w * r.w;
-      }
+      if (hit) s = fma4(s, w, rrow[o * C4 + cq]);
     }
     float* o = dx + ((size_t)blk * W + ix) * lddx + cq * 4;
-    if (accumulate) {
-      const float4 old = *reinterpret_cast<const float4*>(o);
-      s.x += old.x; s.y += old.y; s.z += old.z; s.w += old.w;
-    }
-    *reinterpret_cast<float4*>(o) = s;
+    if (accumulate) s = add4(s, ld4(o));
+    st4(o, s);
     if constexpr (BN) {
-      const float4 v = *reinterpret_cast<const float4*>(bn.y + ((size_t)blk * W + ix) * bn.ldy + cq * 4);
-      dmax = fmaxf(dmax, fmaxf(fmaxf(fabsf(s.x), fabsf(s.y)), fmaxf(fabsf(s.z), fabsf(s.w))));
-      float xh, dz;
-#define UPBN_ACC(X)                                            \
-  xh = (v.X - mu.X) * is.X;                                    \
-  dz = (!(bn.relu & 1) || xh * g.X + b.X > 0.f) ? s.X : 0.f;   \
-  s1.X += dz;                                                  \
-  s2.X += dz * xh;
-      UPBN_ACC(x) UPBN_ACC(y) UPBN_ACC(z) UPBN_ACC(w)
-#undef UPBN_ACC
+      const float4 v = ld4(bn.y + ((size_t)blk * W + ix) * bn.ldy + cq * 4);
+      acc.amax(s);
+      acc.add(v, s, bn.relu);
     }
   }
   if constexpr (BN) {
+    // bn_bwd_block_combine's steps around this kernel's own LDS use: the sums go where the row was (only the
+    // threads that own a slot write), the waves' maxima behind them, so one barrier serves both
     __syncthreads();   // every thread is past its rrow reads
     const int t = threadIdx.x;
     if (lx0 < nlx) {
-      rrow[t] = s1;
-      rrow[256 + t] = s2;
+      rrow[t] = acc.s1;
+      rrow[256 + t] = acc.s2;
     }
-#pragma unroll
-    for (int k = 32; k > 0; k >>= 1) dmax = fmaxf(dmax, __shfl_xor(dmax, k, 64));
+    const float dmax = wave_max(acc.dmax);
     float* wmx = reinterpret_cast<float*>(rrow + 512);
     if ((t & 63) == 0) wmx[t >> 6] = dmax;
     __syncthreads();
-    if (t < C4) {
-      float4 t1 = make_float4(0.f, 0.f, 0.f, 0.f), t2 = t1;
-      for (int r = 0; r < nlx; ++r) {
-        const float4 a = rrow[r * C4 + t], a2 = rrow[256 + r * C4 + t];
-        t1.x += a.x; t1.y += a.y; t1.z += a.z; t1.w += a.w;
-        t2.x += a2.x; t2.y += a2.y; t2.z += a2.z; t2.w += a2.w;
-      }
-      float2* op = bn.part + (size_t)blk * C + t * 4;
-      op[0] = make_float2(t1.x, t2.x); op[1] = make_float2(t1.y, t2.y);
-      op[2] = make_float2(t1.z, t2.z); op[3] = make_float2(t1.w, t2.w);
-    }
-    if (t == 0) bn.da_max[blk] = fmaxf(fmaxf(wmx[0], wmx[1]), fmaxf(wmx[2], wmx[3]));
+    if (t < C4) bn_bwd_store_part(rrow, C4, nlx, t, bn.part + (size_t)blk * C + t * 4);
+    if (t == 0) bn.da_max[blk] = max4slots(wmx);
   }
 }
 
@@ -653,6 +568,12 @@ static void launch_upsample_bwd_rows(const float* dout, int lddo, float* dx, int
                      UpBnArgs{});
 }
 
+static int grid_for(long long total, int cap = 8192) {
+  long long b = (total + 255) / 256;
+  if (b < 1) b = 1;
+  return (int)std::min<long long>(b, cap);
+}
+
 // launch geometry of the pixel-blocked kernels, or false when C/4 is not a power of two <= 256
 static bool px_geometry(long long npix, int c, dim3* grid, dim3* block) {
   const int c4 = c / 4;
@@ -661,6 +582,15 @@ static bool px_geometry(long long npix, int c, dim3* grid, dim3* block) {
   *block = dim3(c4, py);
   *grid = dim3((unsigned)((npix + py - 1) / py));
   return true;
+}
+
+// the pixel-blocked kernel of a pair where px_geometry takes the shape (px(grid, block, npix)), else the
+// grid-stride kernel over the npix * c / 4 quads (gs(grid))
+template <typename PX, typename GS>
+static void launch_px_or_grid_stride(long long npix, int c, PX&& px, GS&& gs) {
+  dim3 g, b;
+  if (px_geometry(npix, c, &g, &b)) px(g, b, (unsigned)npix);
+  else gs(dim3(grid_for(npix * (c / 4))));
 }
 
 // ------------------------------- attention gate ----------------------------------
@@ -676,12 +606,12 @@ __global__ __launch_bounds__(256) void att_channel_fwd_kernel(const float* __res
   const int n = blockIdx.x, C4 = C >> 2;
   const int c4 = threadIdx.x % C4, r0 = threadIdx.x / C4, rs = blockDim.x / C4;
   const int active = C4 * rs;
-  float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+  float4 s = zero4();
   if ((int)threadIdx.x < active) {
     const float* base = x + (long long)n * HW * ldx + c4 * 4;
     for (int p = r0; p < HW; p += rs) {
-      const float4 v = *reinterpret_cast<const float4*>(base + (long long)p * ldx);
-      s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+      const float4 v = ld4(base + (long long)p * ldx);
+      s = add4(s, v);
     }
   }
   float4* red = reinterpret_cast<float4*>(sh);
@@ -690,11 +620,7 @@ __global__ __launch_bounds__(256) void att_channel_fwd_kernel(const float* __res
   float* ms = sh + 4 * 256;
   float* hs = ms + C;
   if ((int)threadIdx.x < C4) {
-    float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int r = 0; r < rs; ++r) {
-      const float4 a = red[r * C4 + threadIdx.x];
-      t.x += a.x; t.y += a.y; t.z += a.z; t.w += a.w;
-    }
+    const float4 t = rowsum4(red, C4, rs, threadIdx.x);
     const float inv = 1.f / (float)HW;
     const int c = threadIdx.x * 4;
     ms[c] = t.x * inv; ms[c + 1] = t.y * inv; ms[c + 2] = t.z * inv; ms[c + 3] = t.w * inv;
@@ -726,9 +652,9 @@ __global__ __launch_bounds__(256) void att_spatial_fwd_kernel(const float* __res
     float acc = 0.f;
     const float* row = g + p * ldg;
     for (int c = sub * 4; c < G; c += 32) {
-      const float4 v = *reinterpret_cast<const float4*>(row + c);
-      const float4 w = *reinterpret_cast<const float4*>(wg + c);
-      acc += v.x * w.x + v.y * w.y + v.z * w.z + v.w * w.w;
+      const float4 v = ld4(row + c);
+      const float4 w = ld4(wg + c);
+      acc += dot4(v, w);
     }
     acc += __shfl_xor(acc, 1, 64);
     acc += __shfl_xor(acc, 2, 64);
@@ -748,8 +674,8 @@ __global__ void att_apply_kernel(const float* __restrict__ x, int ldx, const flo
     const long long p = e / C4;
     const int c = (int)(e - p * C4) * 4;
     const long long n = p / HW;
-    const float4 v = *reinterpret_cast<const float4*>(x + p * ldx + c);
-    const float4 a = *reinterpret_cast<const float4*>(ca + n * C + c);
+    const float4 v = ld4(x + p * ldx + c);
+    const float4 a = ld4(ca + n * C + c);
     const float s = sa[p];
     float4 o;
     o.x = (v.x * a.x) * s; o.y = (v.y * a.y) * s; o.z = (v.z * a.z) * s; o.w = (v.w * a.w) * s;
@@ -769,9 +695,9 @@ __global__ __launch_bounds__(256) void att_bwd_pixel_kernel(const float* __restr
     const long long n = p / HW;
     float acc = 0.f;
     for (int c = sub * 4; c < C; c += 32) {
-      const float4 d = *reinterpret_cast<const float4*>(dout + p * lddo + c);
-      const float4 v = *reinterpret_cast<const float4*>(x + p * ldx + c);
-      const float4 a = *reinterpret_cast<const float4*>(ca + n * C + c);
+      const float4 d = ld4(dout + p * lddo + c);
+      const float4 v = ld4(x + p * ldx + c);
+      const float4 a = ld4(ca + n * C + c);
       acc += d.x * (v.x * a.x) + d.y * (v.y * a.y) + d.z * (v.z * a.z) + d.w * (v.w * a.w);
     }
     acc += __shfl_xor(acc, 1, 64);
@@ -796,12 +722,12 @@ __global__ __launch_bounds__(256) void att_bwd_channel_kernel(
   const int n = blockIdx.x, C4 = C >> 2;
   const int c4 = threadIdx.x % C4, r0 = threadIdx.x / C4, rs = blockDim.x / C4;
   const int active = C4 * rs;
-  float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+  float4 s = zero4();
   if ((int)threadIdx.x < active) {
     const long long pb = (long long)n * HW;
     for (int p = r0; p < HW; p += rs) {
-      const float4 d = *reinterpret_cast<const float4*>(dout + (pb + p) * lddo + c4 * 4);
-      const float4 v = *reinterpret_cast<const float4*>(x + (pb + p) * ldx + c4 * 4);
+      const float4 d = ld4(dout + (pb + p) * lddo + c4 * 4);
+      const float4 v = ld4(x + (pb + p) * ldx + c4 * 4);
       const float q = sa[pb + p];
       s.x += (d.x * q) * v.x; s.y += (d.y * q) * v.y; s.z += (d.z * q) * v.z; s.w += (d.w * q) * v.w;
     }
@@ -812,11 +738,7 @@ __global__ __launch_bounds__(256) void att_bwd_channel_kernel(
   float* dpre = sh + 4 * 256;  // [C] grad of pre-sigmoid channel logits
   float* dh = dpre + C;        // [Cr]
   if ((int)threadIdx.x < C4) {
-    float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int r = 0; r < rs; ++r) {
-      const float4 a = red[r * C4 + threadIdx.x];
-      t.x += a.x; t.y += a.y; t.z += a.z; t.w += a.w;
-    }
+    const float4 t = rowsum4(red, C4, rs, threadIdx.x);
     const int c = threadIdx.x * 4;
     const float tv[4] = {t.x, t.y, t.z, t.w};
 #pragma unroll
@@ -855,13 +777,13 @@ __global__ __launch_bounds__(256) void att_bwd_sample_kernel(
   extern __shared__ float sh[];
   const int n = blockIdx.x, C4 = C >> 2;
   const int c4 = threadIdx.x % C4, r0 = threadIdx.x / C4, rs = blockDim.x / C4;
-  float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+  float4 s = zero4();
   {
-    const float4 a = *reinterpret_cast<const float4*>(ca + (long long)n * C + c4 * 4);
+    const float4 a = ld4(ca + (long long)n * C + c4 * 4);
     const long long pb = (long long)n * HW;
     for (int p = r0; p < HW; p += rs) {   // every lane of a pixel's C / 4 group takes the same trips
-      const float4 d = *reinterpret_cast<const float4*>(dout + (pb + p) * lddo + c4 * 4);
-      const float4 v = *reinterpret_cast<const float4*>(x + (pb + p) * ldx + c4 * 4);
+      const float4 d = ld4(dout + (pb + p) * lddo + c4 * 4);
+      const float4 v = ld4(x + (pb + p) * ldx + c4 * 4);
       const float q = sa[pb + p];
       s.x += (d.x * q) * v.x; s.y += (d.y * q) * v.y; s.z += (d.z * q) * v.z; s.w += (d.w * q) * v.w;
       float dot = d.x * (v.x * a.x) + d.y * (v.y * a.y) + d.z * (v.z * a.z) + d.w * (v.w * a.w);
@@ -875,11 +797,7 @@ __global__ __launch_bounds__(256) void att_bwd_sample_kernel(
   float* dpre = sh + 4 * 256;  // [C] grad of pre-sigmoid channel logits
   float* dh = dpre + C;        // [Cr]
   if ((int)threadIdx.x < C4) {
-    float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int r = 0; r < rs; ++r) {
-      const float4 a = red[r * C4 + threadIdx.x];
-      t.x += a.x; t.y += a.y; t.z += a.z; t.w += a.w;
-    }
+    const float4 t = rowsum4(red, C4, rs, threadIdx.x);
     const int c = threadIdx.x * 4;
     const float tv[4] = {t.x, t.y, t.z, t.w};
 #pragma unroll
@@ -917,19 +835,14 @@ __global__ void att_bwd_dx_kernel(const float* __restrict__ dout, int lddo, cons
     const long long p = e / C4;
     const int c = (int)(e - p * C4) * 4;
     const long long n = p / HW;
-    const float4 d = *reinterpret_cast<const float4*>(dout + p * lddo + c);
-    const float4 a = *reinterpret_cast<const float4*>(ca + n * C + c);
-    const float4 g = *reinterpret_cast<const float4*>(dm + n * C + c);
+    const float4 d = ld4(dout + p * lddo + c);
+    const float4 a = ld4(ca + n * C + c);
+    const float4 g = ld4(dm + n * C + c);
     const float s = sa[p];
-    float4 o;
-    o.x = (d.x * s) * a.x + g.x; o.y = (d.y * s) * a.y + g.y;
-    o.z = (d.z * s) * a.z + g.z; o.w = (d.w * s) * a.w + g.w;
+    float4 o = gate_dx4(d, s, a, g);
     float* dst = dx + p * lddx + c;
-    if (accumulate) {
-      const float4 old = *reinterpret_cast<const float4*>(dst);
-      o.x += old.x; o.y += old.y; o.z += old.z; o.w += old.w;
-    }
-    *reinterpret_cast<float4*>(dst) = o;
+    if (accumulate) o = add4(o, ld4(dst));
+    st4(dst, o);
   }
 }
 
@@ -943,14 +856,11 @@ __global__ void att_bwd_gating_kernel(const float* __restrict__ dsa_pre, const f
     const long long p = e / G4;
     const int c = (int)(e - p * G4) * 4;
     const float s = dsa_pre[p];
-    const float4 w = *reinterpret_cast<const float4*>(wg + c);
-    float4 o = make_float4(s * w.x, s * w.y, s * w.z, s * w.w);
+    const float4 w = ld4(wg + c);
+    float4 o = scale4(s, w);
     float* dst = dg + p * lddg + c;
-    if (accumulate) {
-      const float4 old = *reinterpret_cast<const float4*>(dst);
-      o.x += old.x; o.y += old.y; o.z += old.z; o.w += old.w;
-    }
-    *reinterpret_cast<float4*>(dst) = o;
+    if (accumulate) o = add4(o, ld4(dst));
+    st4(dst, o);
   }
 }
 
@@ -963,7 +873,7 @@ __global__ __launch_bounds__(256) void weighted_colsum_kernel(const float* __res
   const int C4 = C >> 2;
   const int c4 = threadIdx.x % C4, r0 = threadIdx.x / C4, rs = blockDim.x / C4;
   const int active = C4 * rs;
-  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+  float4 acc = zero4();
   float sacc = 0.f;
   const long long pb = (long long)blockIdx.x * rows_per_blk;
   const long long pe = min(P, pb + rows_per_blk);
@@ -978,19 +888,19 @@ __global__ __launch_bounds__(256) void weighted_colsum_kernel(const float* __res
       float w[4];
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
-        a[u] = *reinterpret_cast<const float4*>(v + (p + u * rs) * ldv + c4 * 4);
+        a[u] = ld4(v + (p + u * rs) * ldv + c4 * 4);
         w[u] = s[p + u * rs];
       }
 #pragma unroll
       for (int u = 0; u < 4; ++u) row(a[u], w[u]);
     }
-    for (; p < pe; p += rs) row(*reinterpret_cast<const float4*>(v + p * ldv + c4 * 4), s[p]);
+    for (; p < pe; p += rs) row(ld4(v + p * ldv + c4 * 4), s[p]);
   }
   red4[threadIdx.x] = acc;
   red4[256 + threadIdx.x] = make_float4(sacc, 0.f, 0.f, 0.f);
   __syncthreads();
   if ((int)threadIdx.x < C4) {
-    float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 t = zero4();
     float ts = 0.f;
     for (int r = 0; r < rs; ++r) {
       const float4 a = red4[r * C4 + threadIdx.x];
@@ -1075,7 +985,7 @@ __global__ void head_fwd_kernel(const float* __restrict__ z, int ldz, int C, con
   for (long long p = blockIdx.x * (long long)blockDim.x + threadIdx.x; p < P; p += (long long)gridDim.x * blockDim.x) {
     float acc = 0.f;
     for (int c = 0; c < C; c += 4) {
-      const float4 v = *reinterpret_cast<const float4*>(z + p * ldz + c);
+      const float4 v = ld4(z + p * ldz + c);
       acc += v.x * wf[c] + v.y * wf[c + 1] + v.z * wf[c + 2] + v.w * wf[c + 3];
     }
     const long long n = p / HW;
@@ -1138,12 +1048,6 @@ __global__ void mse_bwd_kernel(const float* __restrict__ y, const float* __restr
     dy[i] = norm * (y[i] - t[i]) * g;
 }
 
-static int grid_for(long long total, int cap = 8192) {
-  long long b = (total + 255) / 256;
-  if (b < 1) b = 1;
-  return (int)std::min<long long>(b, cap);
-}
-
 static int colsum_blocks(long long P, int C, int* rpb) {
   const int rs = 256 / (C >> 2);
   long long r = (P + 1023) / 1024;
@@ -1186,14 +1090,12 @@ int srpde_axpy_channel(float* y, const float* x, int n, int c, int hw, int ch, f
 int srpde_maxpool2x2_fwd(const float* x, int ldx, float* out, int ldo, int n, int h, int w, int c,
                          hipStream_t stream) {
   SRPDE_CHECK_ARG(x && out && c % 4 == 0 && h % 2 == 0 && w % 2 == 0, "srpde_maxpool2x2_fwd: bad args");
-  dim3 g, b;
-  if (px_geometry((long long)n * (h / 2) * (w / 2), c, &g, &b)) {
-    hipLaunchKernelGGL(maxpool2_fwd_px_kernel, g, b, 0, stream, x, ldx, out, ldo, (unsigned)(n * (h / 2) * (w / 2)), h, w);
-    SRPDE_LAUNCH_CHECK("srpde_maxpool2x2_fwd");
-    return 0;
-  }
-  hipLaunchKernelGGL(maxpool2_fwd_kernel, dim3(grid_for((long long)n * (h / 2) * (w / 2) * (c / 4))), dim3(256), 0,
-                     stream, x, ldx, out, ldo, n, h, w, c);
+  launch_px_or_grid_stride(
+      (long long)n * (h / 2) * (w / 2), c,
+      [&](dim3 g, dim3 b, unsigned npix) {
+        hipLaunchKernelGGL(maxpool2_fwd_px_kernel, g, b, 0, stream, x, ldx, out, ldo, npix, h, w);
+      },
+      [&](dim3 g) { hipLaunchKernelGGL(maxpool2_fwd_kernel, g, dim3(256), 0, stream, x, ldx, out, ldo, n, h, w, c); });
   SRPDE_LAUNCH_CHECK("srpde_maxpool2x2_fwd");
   return 0;
 }
@@ -1201,15 +1103,15 @@ int srpde_maxpool2x2_fwd(const float* x, int ldx, float* out, int ldo, int n, in
 int srpde_maxpool2x2_bwd(const float* x, int ldx, const float* dout, int lddo, float* dx, int lddx, int n, int h,
                          int w, int c, int accumulate, hipStream_t stream) {
   SRPDE_CHECK_ARG(x && dout && dx && c % 4 == 0 && h % 2 == 0 && w % 2 == 0, "srpde_maxpool2x2_bwd: bad args");
-  dim3 g, b;
-  if (px_geometry((long long)n * (h / 2) * (w / 2), c, &g, &b)) {
-    hipLaunchKernelGGL(maxpool2_bwd_px_kernel, g, b, 0, stream, x, ldx, dout, lddo, dx, lddx,
-                       (unsigned)(n * (h / 2) * (w / 2)), h, w, accumulate);
-    SRPDE_LAUNCH_CHECK("srpde_maxpool2x2_bwd");
-    return 0;
-  }
-  hipLaunchKernelGGL(maxpool2_bwd_kernel, dim3(grid_for((long long)n * (h / 2) * (w / 2) * (c / 4))), dim3(256), 0,
-                     stream, x, ldx, dout, lddo, dx, lddx, n, h, w, c, accumulate);
+  launch_px_or_grid_stride(
+      (long long)n * (h / 2) * (w / 2), c,
+      [&](dim3 g, dim3 b, unsigned npix) {
+        hipLaunchKernelGGL(maxpool2_bwd_px_kernel, g, b, 0, stream, x, ldx, dout, lddo, dx, lddx, npix, h, w, accumulate);
+      },
+      [&](dim3 g) {
+        hipLaunchKernelGGL(maxpool2_bwd_kernel, g, dim3(256), 0, stream, x, ldx, dout, lddo, dx, lddx, n, h, w, c,
+                           accumulate);
+      });
   SRPDE_LAUNCH_CHECK("srpde_maxpool2x2_bwd");
   return 0;
 }
@@ -1236,14 +1138,14 @@ int srpde_upsample_bilinear_fwd(const float* x, int ldx, float* out, int ldo, in
     SRPDE_LAUNCH_CHECK("srpde_upsample_bilinear_fwd");
     return 0;
   }
-  dim3 g, b;
-  if (px_geometry((long long)n * ho * wo, c, &g, &b)) {
-    hipLaunchKernelGGL(upsample_fwd_px_kernel, g, b, 0, stream, x, ldx, out, ldo, (unsigned)(n * ho * wo), h, w, ho, wo);
-    SRPDE_LAUNCH_CHECK("srpde_upsample_bilinear_fwd");
-    return 0;
-  }
-  hipLaunchKernelGGL(upsample_fwd_kernel, dim3(grid_for((long long)n * ho * wo * (c / 4))), dim3(256), 0, stream, x,
-                     ldx, out, ldo, n, h, w, ho, wo, c);
+  launch_px_or_grid_stride(
+      (long long)n * ho * wo, c,
+      [&](dim3 g, dim3 b, unsigned npix) {
+        hipLaunchKernelGGL(upsample_fwd_px_kernel, g, b, 0, stream, x, ldx, out, ldo, npix, h, w, ho, wo);
+      },
+      [&](dim3 g) {
+        hipLaunchKernelGGL(upsample_fwd_kernel, g, dim3(256), 0, stream, x, ldx, out, ldo, n, h, w, ho, wo, c);
+      });
   SRPDE_LAUNCH_CHECK("srpde_upsample_bilinear_fwd");
   return 0;
 }
@@ -1281,12 +1183,28 @@ int srpde_upsample_gate_sa(const float* x, int ldx, int n, int h, int w, int ho,
   return 0;
 }
 
+// LDS of the per-sample attention kernels: [256] float4 partials, then C and C / 8 floats
+static size_t att_lds_bytes(int c) { return (4 * 256 + c + c / 8) * sizeof(float); }
+
+static void launch_att_channel(const float* x, int ldx, int n, int hw, int c, const float* w1, const float* b1,
+                               const float* w2, const float* b2, float* m, float* hbuf, float* ca, hipStream_t stream) {
+  hipLaunchKernelGGL(att_channel_fwd_kernel, dim3(n), dim3(256), att_lds_bytes(c), stream, x, ldx, hw, c, c / 8, w1, b1,
+                     w2, b2, m, hbuf, ca);
+}
+static void launch_att_spatial(const float* g, int ldg, long long P, int gc, const float* wg, const float* bg, float* sa,
+                               hipStream_t stream) {
+  hipLaunchKernelGGL(att_spatial_fwd_kernel, dim3(grid_for(P * 8)), dim3(256), 0, stream, g, ldg, P, gc, wg, bg, sa);
+}
+static void launch_att_apply(const float* x, int ldx, const float* ca, const float* sa, float* out, int ldo, long long P,
+                             int hw, int c, hipStream_t stream) {
+  hipLaunchKernelGGL(att_apply_kernel, dim3(grid_for(P * (c / 4))), dim3(256), 0, stream, x, ldx, ca, sa, out, ldo, P,
+                     hw, c);
+}
+
 int srpde_att_apply_fwd(const float* x, int ldx, int n, int hw, int c, const float* ca, const float* sa, float* out,
                         int ldo, hipStream_t stream) {
   SRPDE_CHECK_ARG(x && ca && sa && out && c % 4 == 0, "srpde_att_apply_fwd: bad args");
-  const long long P = (long long)n * hw;
-  hipLaunchKernelGGL(att_apply_kernel, dim3(grid_for(P * (c / 4))), dim3(256), 0, stream, x, ldx, ca, sa, out, ldo,
-                     P, hw, c);
+  launch_att_apply(x, ldx, ca, sa, out, ldo, (long long)n * hw, hw, c, stream);
   SRPDE_LAUNCH_CHECK("srpde_att_apply_fwd");
   return 0;
 }
@@ -1344,15 +1262,15 @@ int srpde_upsample_bilinear_bwd(const float* dout, int lddo, float* dx, int lddx
     SRPDE_LAUNCH_CHECK("srpde_upsample_bilinear_bwd");
     return 0;
   }
-  dim3 g, b;
-  if (px_geometry((long long)n * h * w, c, &g, &b)) {
-    hipLaunchKernelGGL(upsample_bwd_px_kernel, g, b, 0, stream, dout, lddo, dx, lddx, (unsigned)(n * h * w), h, w, ho,
-                       wo, accumulate);
-    SRPDE_LAUNCH_CHECK("srpde_upsample_bilinear_bwd");
-    return 0;
-  }
-  hipLaunchKernelGGL(upsample_bwd_kernel, dim3(grid_for((long long)n * h * w * (c / 4))), dim3(256), 0, stream, dout,
-                     lddo, dx, lddx, n, h, w, ho, wo, c, accumulate);
+  launch_px_or_grid_stride(
+      (long long)n * h * w, c,
+      [&](dim3 g, dim3 b, unsigned npix) {
+        hipLaunchKernelGGL(upsample_bwd_px_kernel, g, b, 0, stream, dout, lddo, dx, lddx, npix, h, w, ho, wo, accumulate);
+      },
+      [&](dim3 g) {
+        hipLaunchKernelGGL(upsample_bwd_kernel, g, dim3(256), 0, stream, dout, lddo, dx, lddx, n, h, w, ho, wo, c,
+                           accumulate);
+      });
   SRPDE_LAUNCH_CHECK("srpde_upsample_bilinear_bwd");
   return 0;
 }
@@ -1361,10 +1279,7 @@ int srpde_att_channel_fwd(const float* x, int ldx, int n, int hw, int c, const f
                           const float* w2, const float* b2, float* m, float* hbuf, float* ca, hipStream_t stream) {
   SRPDE_CHECK_ARG(x && w1 && b1 && w2 && b2 && m && hbuf && ca, "srpde_att_channel_fwd: null");
   SRPDE_CHECK_ARG(c % 32 == 0 && c <= 1024, "srpde_att_channel_fwd: channel count");
-  const int cr = c / 8;
-  const size_t lds = (4 * 256 + c + cr) * sizeof(float);
-  hipLaunchKernelGGL(att_channel_fwd_kernel, dim3(n), dim3(256), lds, stream, x, ldx, hw, c, cr, w1, b1, w2, b2, m,
-                     hbuf, ca);
+  launch_att_channel(x, ldx, n, hw, c, w1, b1, w2, b2, m, hbuf, ca, stream);
   SRPDE_LAUNCH_CHECK("srpde_att_channel_fwd");
   return 0;
 }
@@ -1375,10 +1290,9 @@ int srpde_att_gate_fwd(const float* x, int ldx, const float* g, int ldg, int n, 
   SRPDE_CHECK_ARG(x && g && ca && wg && bg && sa && out, "srpde_att_gate_fwd: null");
   SRPDE_CHECK_ARG(c % 32 == 0 && gc % 4 == 0 && c <= 1024, "srpde_att_gate_fwd: channel counts");
   const long long P = (long long)n * hw;
-  hipLaunchKernelGGL(att_spatial_fwd_kernel, dim3(grid_for(P * 8)), dim3(256), 0, stream, g, ldg, P, gc, wg, bg, sa);
+  launch_att_spatial(g, ldg, P, gc, wg, bg, sa, stream);
   SRPDE_LAUNCH_CHECK("srpde_att_gate_fwd(spatial)");
-  hipLaunchKernelGGL(att_apply_kernel, dim3(grid_for(P * (c / 4))), dim3(256), 0, stream, x, ldx, ca, sa, out, ldo,
-                     P, hw, c);
+  launch_att_apply(x, ldx, ca, sa, out, ldo, P, hw, c, stream);
   SRPDE_LAUNCH_CHECK("srpde_att_gate_fwd(apply)");
   return 0;
 }
@@ -1389,16 +1303,12 @@ int srpde_att_fwd(const float* x, int ldx, const float* g, int ldg, int n, int h
   SRPDE_CHECK_ARG(x && g && w1 && b1 && w2 && b2 && wg && bg && m && hbuf && ca && sa && out,
                   "srpde_att_fwd: null");
   SRPDE_CHECK_ARG(c % 32 == 0 && gc % 4 == 0 && c <= 1024, "srpde_att_fwd: channel counts");
-  const int cr = c / 8;
-  const size_t lds = (4 * 256 + c + cr) * sizeof(float);
-  hipLaunchKernelGGL(att_channel_fwd_kernel, dim3(n), dim3(256), lds, stream, x, ldx, hw, c, cr, w1, b1, w2, b2, m,
-                     hbuf, ca);
+  launch_att_channel(x, ldx, n, hw, c, w1, b1, w2, b2, m, hbuf, ca, stream);
   SRPDE_LAUNCH_CHECK("srpde_att_fwd(channel)");
   const long long P = (long long)n * hw;
-  hipLaunchKernelGGL(att_spatial_fwd_kernel, dim3(grid_for(P * 8)), dim3(256), 0, stream, g, ldg, P, gc, wg, bg, sa);
+  launch_att_spatial(g, ldg, P, gc, wg, bg, sa, stream);
   SRPDE_LAUNCH_CHECK("srpde_att_fwd(spatial)");
-  hipLaunchKernelGGL(att_apply_kernel, dim3(grid_for(P * (c / 4))), dim3(256), 0, stream, x, ldx, ca, sa, out, ldo,
-                     P, hw, c);
+  launch_att_apply(x, ldx, ca, sa, out, ldo, P, hw, c, stream);
   SRPDE_LAUNCH_CHECK("srpde_att_fwd(apply)");
   return 0;
 }
@@ -1438,7 +1348,7 @@ int srpde_att_bwd(const float* dout, int lddo, const float* x, int ldx, const fl
   float2* part = reinterpret_cast<float2*>(db2r + (size_t)n * c + 2);
   part = reinterpret_cast<float2*>((reinterpret_cast<uintptr_t>(part) + 15) & ~uintptr_t(15));
 
-  const size_t lds = (4 * 256 + c + cr) * sizeof(float);
+  const size_t lds = att_lds_bytes(c);
   if (c == 64 || c == 128 || c == 256) {   // one pass over dout and x per sample
     hipLaunchKernelGGL(att_bwd_sample_kernel, dim3(n), dim3(256), lds, stream, dout, lddo, x, ldx, sa, hw, c, cr, w1,
                        w2, m, hbuf, ca, dm, dw1r, db1r, dw2r, db2r, dsa);

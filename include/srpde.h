@@ -468,6 +468,8 @@ int srpde_att_channel_fwd(const float* x, int ldx, int n, int hw, int c, const f
 int srpde_att_gate_fwd(const float* x, int ldx, const float* g, int ldg, int n, int hw, int c, int gc,
                        const float* ca, const float* wg, const float* bg, float* sa, float* out, int ldo,
                        hipStream_t stream);
+/* c a multiple of 32 in 32..1024, gc a multiple of 4 in 4..1024: the size query returns 0 for other counts and
+ * srpde_att_bwd, srpde_att_bwd_params and srpde_att_bwd_params_lowres reject them. */
 size_t srpde_att_bwd_workspace_size(int n, int hw, int c, int gc);
 /* dg == NULL: the gating gradient is not written; workspace[0, n*hw) floats then holds dsa (the
  * spatial gate's pre-sigmoid gradient) for srpde_upsample_bilinear_bwd_gated. */
@@ -509,6 +511,7 @@ int srpde_att_bwd_params_lowres(const float* d, int ldd, int n, int h, int w, in
 /* ---- output head: final 1x1 conv + residual x[:,0:1] (models.py:61,74,98,101) ------- */
 int srpde_head_fwd(const float* z, int ldz, int c, const float* wf, const float* bf, const float* xin, int xin_c,
                    int n, int hw, float* out, hipStream_t stream);
+/* c a multiple of 4 in 4..1024: the size query returns 0 for other counts and srpde_head_bwd rejects them. */
 size_t srpde_head_bwd_workspace_size(int n, int hw, int c);
 int srpde_head_bwd(const float* dout, const float* z, int ldz, int c, const float* wf, int n, int hw, float* dz,
                    int lddz, float* dwf, float* dbf, void* workspace, size_t ws_bytes, hipStream_t stream);

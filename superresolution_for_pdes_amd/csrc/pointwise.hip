@@ -1048,6 +1048,11 @@ __global__ void mse_bwd_kernel(const float* __restrict__ y, const float* __restr
     dy[i] = norm * (y[i] - t[i]) * g;
 }
 
+// the channel counts weighted_colsum_kernel (and so colsum_blocks) takes: 1..256 float4 lanes per row
+static bool colsum_ok(int C) { return C % 4 == 0 && C >= 4 && C <= 1024; }
+// ... and the per-sample attention kernels' c (att_lds_bytes, cr = c / 8) beside the gating input's gc
+static bool att_bwd_counts_ok(int c, int gc) { return c % 32 == 0 && c >= 32 && c <= 1024 && colsum_ok(gc); }
+
 static int colsum_blocks(long long P, int C, int* rpb) {
   const int rs = 256 / (C >> 2);
   long long r = (P + 1023) / 1024;
@@ -1314,6 +1319,7 @@ int srpde_att_fwd(const float* x, int ldx, const float* g, int ldg, int n, int h
 }
 
 size_t srpde_att_bwd_workspace_size(int n, int hw, int c, int gc) {
+  if (!att_bwd_counts_ok(c, gc)) return 0;   // the entries reject such counts
   const long long P = (long long)n * hw;
   const int cr = c / 8;
   int rpb;
@@ -1332,7 +1338,7 @@ int srpde_att_bwd(const float* dout, int lddo, const float* x, int ldx, const fl
                   int dg_accumulate, float* dw1, float* db1, float* dw2, float* db2, float* dwg, float* dbg,
                   void* workspace, size_t ws_bytes, hipStream_t stream) {
   SRPDE_CHECK_ARG(dout && x && g && workspace, "srpde_att_bwd: null");
-  SRPDE_CHECK_ARG(c % 32 == 0 && gc % 4 == 0, "srpde_att_bwd: channel counts");
+  SRPDE_CHECK_ARG(att_bwd_counts_ok(c, gc), "srpde_att_bwd: channel counts (c %% 32, gc %% 4, both <= 1024)");
   if (ws_bytes < srpde_att_bwd_workspace_size(n, hw, c, gc)) {
     set_error("srpde_att_bwd: workspace too small");
     return kErrWorkspace;
@@ -1420,9 +1426,11 @@ static void att_params_outer(int n, int c, const float* m, const float* hbuf, co
 int srpde_att_bwd_params_lowres(const float* d, int ldd, int n, int h, int w, int ho, int wo, int c, int gc,
                                 const float* m, const float* hbuf, float* dw1, float* db1, float* dw2, float* db2,
                                 float* dwg, float* dbg, void* workspace, size_t ws_bytes, hipStream_t stream) {
-  SRPDE_CHECK_ARG(d && m && hbuf && dw1 && db1 && dw2 && db2 && dwg && dbg && workspace && ldd % 4 == 0 && gc % 4 == 0 &&
-                      c % 32 == 0 && ho >= h && wo >= w,
+  SRPDE_CHECK_ARG(d && m && hbuf && dw1 && db1 && dw2 && db2 && dwg && dbg && workspace && ldd % 4 == 0 && ho >= h &&
+                      wo >= w,
                   "srpde_att_bwd_params_lowres: bad args");
+  SRPDE_CHECK_ARG(att_bwd_counts_ok(c, gc),
+                  "srpde_att_bwd_params_lowres: channel counts (c %% 32, gc %% 4, both <= 1024)");
   const int hw = ho * wo;
   if (ws_bytes < srpde_att_bwd_workspace_size(n, hw, c, gc)) {
     set_error("srpde_att_bwd_params_lowres: workspace too small");
@@ -1463,6 +1471,7 @@ int srpde_att_bwd_params(const float* g, int ldg, int n, int hw, int c, int gc, 
                          size_t ws_bytes, hipStream_t stream) {
   SRPDE_CHECK_ARG(g && m && hbuf && dw1 && db1 && dw2 && db2 && dwg && dbg && workspace,
                   "srpde_att_bwd_params: null");
+  SRPDE_CHECK_ARG(att_bwd_counts_ok(c, gc), "srpde_att_bwd_params: channel counts (c %% 32, gc %% 4, both <= 1024)");
   if (ws_bytes < srpde_att_bwd_workspace_size(n, hw, c, gc)) {
     set_error("srpde_att_bwd_params: workspace too small");
     return kErrWorkspace;
@@ -1503,6 +1512,7 @@ int srpde_head_fwd(const float* z, int ldz, int c, const float* wf, const float*
 }
 
 size_t srpde_head_bwd_workspace_size(int n, int hw, int c) {
+  if (!colsum_ok(c)) return 0;   // srpde_head_bwd rejects such counts
   int rpb;
   const int nb = colsum_blocks((long long)n * hw, c, &rpb);
   return (size_t)nb * (c + 1) * sizeof(float2);
@@ -1510,7 +1520,8 @@ size_t srpde_head_bwd_workspace_size(int n, int hw, int c) {
 
 int srpde_head_bwd(const float* dout, const float* z, int ldz, int c, const float* wf, int n, int hw, float* dz,
                    int lddz, float* dwf, float* dbf, void* workspace, size_t ws_bytes, hipStream_t stream) {
-  SRPDE_CHECK_ARG(dout && z && wf && dz && dwf && dbf && workspace && c % 4 == 0, "srpde_head_bwd: bad args");
+  SRPDE_CHECK_ARG(dout && z && wf && dz && dwf && dbf && workspace, "srpde_head_bwd: bad args");
+  SRPDE_CHECK_ARG(colsum_ok(c), "srpde_head_bwd: channel count (c %% 4, 4 <= c <= 1024)");
   if (ws_bytes < srpde_head_bwd_workspace_size(n, hw, c)) {
     set_error("srpde_head_bwd: workspace too small");
     return kErrWorkspace;

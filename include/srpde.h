@@ -60,8 +60,9 @@ typedef struct ihipStream_t* hipStream_t;
  *  12  the batched cascade: srpde_cascade_level_stats(_workspace_size), srpde_cascade_level_assemble,
  *      srpde_cascade_stitch_denorm, srpde_field_metrics(_workspace_size)
  *  13  the direct sine-transform Poisson solver: srpde_poisson_dst_plan(_size), srpde_poisson_dst_lds_max_n,
- *      srpde_poisson_dst_workspace_size, srpde_poisson_dst_batched, srpde_poisson_dst_apply */
-#define SRPDE_ABI_VERSION 13
+ *      srpde_poisson_dst_workspace_size, srpde_poisson_dst_batched, srpde_poisson_dst_apply
+ *  14  the device-side sample stream: srpde_stream_raw, srpde_stream_draw, srpde_stream_window */
+#define SRPDE_ABI_VERSION 14
 
 /* Kernel-family bits (per call; bit 0 of the same argument is the accumulate flag): the forward / dgrad
  * families compute the same outputs, statistics and stored splits bit for bit, so these only route a call to
@@ -613,6 +614,42 @@ int srpde_poisson_rows_iter_b(int n, int nloc, int world, const double* gath, co
                               size_t ws_bytes, double* send, hipStream_t stream);
 int srpde_poisson_rows_finish(double* u, int* iters, int n, int nloc, int maxit, void* ws, size_t ws_bytes,
                               hipStream_t stream);
+
+/* ---- Streamed training samples (online.SampleStream): the random draws of the reference's dataset generators
+ *      (np.random.uniform / randint per sample, src/data_generation.py:130-131, src/enhanced_data_generation.py:
+ *      123-138) from a counter-based generator on the device, and the crop / stride / fp32 cast of
+ *      generate_subdomain_dataset + PDEDataset (enhanced_data_generation.py:141-148, src/models.py:132-203) as one
+ *      pass.  The generator is Philox4x32-10, a pure function of (seed, sample, field, element):
+ *          key = (seed low word, seed high word), counter = (element, field, sample low word, sample high word)
+ *      so a sample's values depend on nothing else -- not on B, the rank count or the launch geometry.  An
+ *      ordered pair of output words (a, b) gives the double u = (((uint64)a << 32 | b) >> 11) * 2^-53 in [0, 1).
+ *          field 0, element 0: k1 from words 0,1 and k2 from words 2,3
+ *          field 0, element 1: start_x from words 0,1 and start_y from words 2,3
+ *          field 1, element e: theta pixels 2e (words 0,1) and 2e + 1 (words 2,3) of the row-major [n][n] grid
+ *      A value in [lo, hi) is lo + (hi - lo) * u (a rounded product, then a rounded sum), a start is
+ *      (int)floor(u * max_start), so 0 <= start < max_start as np.random.randint(0, max_start).  All entries are
+ *      stream-ordered, keep no state and never synchronise the host. ---- */
+/* The raw words: out[(s * n_elements + e) * 4 + w] = word w of (seed, sample0 + s, field, element0 + e), for
+ * n_samples x n_elements <= 2^31 counters; field and element0 + n_elements - 1 fit 32 bits, sample0 + s wraps in
+ * 64 bits.  (The known-answer hook: any Philox4x32-10 counter / key can be asked for.) */
+int srpde_stream_raw(long long seed, long long sample0, long long n_samples, long long field, long long element0,
+                     long long n_elements, unsigned* out, hipStream_t stream);
+/* The draws of samples sample0 .. sample0 + B - 1 in one launch: k12 [B][2] fp64 in [k_lo, k_hi); starts [B][2]
+ * int32 (x, y) in [0, max_start) (nullable: no starts drawn, max_start ignored); theta [B][n][n] fp64 (nullable:
+ * n ignored), with theta_mode 0 exactly 1.0 everywhere and with theta_mode 1 uniform in [theta_lo, theta_hi);
+ * theta_half (nullable) [B][(n + 1) / 2][(n + 1) / 2] = theta[:, ::2, ::2], the coefficient of a coarse solve. */
+int srpde_stream_draw(long long seed, long long sample0, int B, double k_lo, double k_hi, int theta_mode,
+                      double theta_lo, double theta_hi, int n, int max_start, double* k12, int* starts, double* theta,
+                      double* theta_half, hipStream_t stream);
+/* From the solved fields u, f, theta [B][ns][ns] fp64 and starts [B][2] int32 (x, y) on the device: the fp32 training
+ * fields u_fine, f_fine, theta_fine [B][nf][nf] = field[start_y + i][start_x + j] and u_coarse [B][nc][nc],
+ * nc = (nf + 1) / 2, the stride-2 subsample of the u window -- extract_subdomain + downsample + the fp32 cast.  A
+ * start outside [0, ns - nf] is clamped into it.  starts == NULL is the pass-through for standard samples: ns == nf,
+ * the window at (0, 0), and u_coarse is the fp32 cast of u_coarse_in [B][nc][nc], the sample's own coarse solve
+ * (u_coarse_in == NULL: the subsample, as above; u_coarse_in with starts is refused). */
+int srpde_stream_window(const double* u, const double* f, const double* theta, const int* starts,
+                        const double* u_coarse_in, int B, int ns, int nf, float* u_fine, float* f_fine,
+                        float* theta_fine, float* u_coarse, hipStream_t stream);
 
 #ifdef __cplusplus
 }

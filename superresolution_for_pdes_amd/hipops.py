@@ -887,6 +887,57 @@ def field_metrics(pred, gt):
     return out
 
 
+# ------------------------------ streamed training samples ------------------------------
+def stream_raw(seed, sample0, n_samples, field, element0, n_elements, device="cuda"):
+    """srpde_stream_raw: the Philox4x32-10 words of (seed, sample0 + s, field, element0 + e) ->
+    [n_samples, n_elements, 4] (int32 storage: view the host copy as uint32)."""
+    out = torch.empty(n_samples, n_elements, 4, dtype=torch.int32, device=device)
+    call("srpde_stream_raw", int(seed), int(sample0), int(n_samples), int(field), int(element0), int(n_elements),
+         out.data_ptr(), stream_ptr())
+    return out
+
+
+def stream_draw(seed, sample0, B, k_range, theta_range=None, n=0, max_start=0, theta_half=False, device="cuda"):
+    """srpde_stream_draw: the draws of samples sample0 .. sample0 + B - 1 -> (k12 [B, 2] fp64, starts [B, 2] int32 or
+    None (max_start = 0), theta [B, n, n] fp64 or None (n = 0; ones when ``theta_range`` is None), and
+    theta[:, ::2, ::2] or None).  Seed, indices and sizes are kernel arguments: nothing is copied to the device."""
+    f64 = dict(dtype=torch.float64, device=device)
+    k12 = torch.empty(B, 2, **f64)
+    starts = torch.empty(B, 2, dtype=torch.int32, device=device) if max_start else None
+    theta = torch.empty(B, n, n, **f64) if n else None
+    half = torch.empty(B, (n + 1) // 2, (n + 1) // 2, **f64) if n and theta_half else None
+    lo, hi = (0.0, 0.0) if theta_range is None else theta_range
+    call("srpde_stream_draw", int(seed), int(sample0), int(B), float(k_range[0]), float(k_range[1]),
+         int(theta_range is not None), float(lo), float(hi), int(n), int(max_start), k12.data_ptr(), _p(starts),
+         _p(theta), _p(half), stream_ptr())
+    return k12, starts, theta, half
+
+
+def stream_window(u, f, theta, starts, nf, u_coarse_in=None, out=None):
+    """srpde_stream_window: solved fp64 fields [B, ns, ns] (+ starts [B, 2] int32, or None for the pass-through
+    with the coarse solve ``u_coarse_in``) -> fp32 (u_fine, f_fine, theta_fine [B, nf, nf], u_coarse [B, nc, nc]),
+    written into ``out`` (four contiguous tensors, e.g. row slices of a batch's buffers) when given."""
+    _fields("stream_window", torch.float64, u, f, theta, *([] if u_coarse_in is None else [u_coarse_in]))
+    if u.dim() != 3 or u.shape[1] != u.shape[2] or f.shape != u.shape or theta.shape != u.shape:
+        raise ValueError("stream_window: u, f, theta must share one [B, ns, ns] shape")
+    B, ns, _ = u.shape
+    nc = (nf + 1) // 2
+    if starts is not None:
+        _fields("stream_window", torch.int32, starts)
+        if tuple(starts.shape) != (B, 2):
+            raise ValueError("stream_window: starts is [B, 2]")
+    if u_coarse_in is not None and tuple(u_coarse_in.shape) != (B, nc, nc):
+        raise ValueError(f"stream_window: u_coarse_in is [B, {nc}, {nc}]")
+    if out is None:
+        out = tuple(torch.empty(B, m, m, dtype=F32, device=u.device) for m in (nf, nf, nf, nc))
+    _fields("stream_window", F32, *out)
+    if [tuple(t.shape) for t in out] != [(B, nf, nf)] * 3 + [(B, nc, nc)]:
+        raise ValueError("stream_window: out is (u_fine, f_fine, theta_fine [B, nf, nf], u_coarse [B, nc, nc])")
+    call("srpde_stream_window", u.data_ptr(), f.data_ptr(), theta.data_ptr(), _p(starts), _p(u_coarse_in), B, ns,
+         int(nf), out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), out[3].data_ptr(), stream_ptr())
+    return tuple(out)
+
+
 def upsample_bwd(dout, dx, n, h, w, ho, wo, accumulate, gate=None, bn=None):
     """``gate = (dsa, wg)``: the upsampled tensor's gradient is dout + dsa (x) wg (the attention
     gating gradient left unapplied by att_bwd(dg=None)).  ``bn = (y, mean, invstd, gamma, beta)``: the BN +

@@ -1,0 +1,219 @@
+"""Training on an endless stream of freshly solved samples, generated on the device.
+
+``SampleStream.next_batch()`` draws, solves and assembles one batch in the current stream: the wave numbers,
+crop starts and (optionally) the coefficient field come from a counter-based generator on the GPU
+(csrc/datastream.hip: Philox4x32-10, a pure function of (seed, global sample index, field, element)), the forcing
+and the Poisson solves are the kernels the fixed dataset uses, one window pass crops / strides / casts the solved
+fields and ``srpde_pde_dataset_assemble`` normalises them with FROZEN statistics.  Per batch there is no host draw,
+no host->device copy of per-sample data (seed, indices and sizes are kernel arguments) and no host sync.  No sample
+is seen twice.  The fixed, seeded dataset (train_enhanced.generate_on_device + PDEDataset) is untouched: this is a
+second data source for the same ``train_model``.
+
+Samples.  A batch of B has ``B - round(B * sub_fraction)`` standard samples in its first slots and subdomain
+samples in the rest, so every shape is static.
+  * standard  (reference data_generation.py): k1, k2 ~ U(k_std); independent solves on the fine and the coarse
+    grid, f_coarse the forcing on the coarse grid, theta_coarse = theta_fine[::2, ::2];
+  * subdomain (reference enhanced_data_generation.py): k1, k2 ~ U(k_sub); one solve on the super-fine grid, a
+    random n_fine window (start_x, start_y in [0, n_superfine - n_fine)) and its stride-2 subsample.
+theta is 1 (``theta_range=None``, what both reference generators train on) or U(theta_range) per pixel of the
+solve grid (``(0.5, 2.0)`` is the distribution of the cascade and subdomain studies).
+
+Global sample indices.  Local slot i of step t on rank r of ``world`` is sample
+    s = (t * world + r) * B + i,
+so a world of W ranks at step t consumes exactly the samples of the single-process steps t*W .. t*W + W - 1.  The
+63-bit index space is split into three ranges that can never overlap:
+    training     [0, 2^61)            next_batch (refuses to run past the end)
+    calibration  [2^61, 2^62)         the frozen statistics: fixed_set(n_calib, CALIB_FIRST)
+    validation   [2^62, 2^63)         held-out evaluation:   fixed_set(n, VALID_FIRST)
+``fixed_set`` takes indices from the two held-out ranges only.
+
+Frozen statistics.  ``stream.stats`` = (u_mean, u_std, f_mean, f_std, theta_mean, theta_std) in fp32, computed once
+in the constructor from the calibration set with PDEDataset's arithmetic (fp32 mean, unbiased std, theta passed
+through as (0, 1) when its std < 1e-6), then held fixed for every batch and for the validation set.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from . import hipops as H
+from . import poisson as P
+
+TRAIN_END = 1 << 61
+CALIB_FIRST = 1 << 61
+CALIB_END = 1 << 62
+VALID_FIRST = 1 << 62
+VALID_END = 1 << 63
+HELD_OUT = ((CALIB_FIRST, CALIB_END), (VALID_FIRST, VALID_END))
+
+
+def sample_indices(step: int, batch_size: int, rank: int = 0, world: int = 1) -> range:
+    """The global sample indices of ``rank``'s batch at ``step``."""
+    first = (step * world + rank) * batch_size
+    return range(first, first + batch_size)
+
+
+def n_standard(n: int, sub_fraction: float) -> int:
+    """Standard samples among n slots (they come first); the other ``round(n * sub_fraction)`` are subdomain samples."""
+    return n - int(round(n * sub_fraction))
+
+
+class FrozenSet:
+    """A fixed set normalised with a stream's frozen statistics: what DeviceBatchLoader needs of a PDEDataset."""
+
+    def __init__(self, inputs, targets, stats):
+        self.inputs, self.targets, self.stats = inputs, targets, stats
+        self.u_mean, self.u_std = stats[0], stats[1]
+
+    def __len__(self):
+        return self.inputs.shape[0]
+
+    def __getitem__(self, idx):
+        return self.inputs[idx], self.targets[idx]
+
+    def batch(self, idx):
+        return self.inputs.index_select(0, idx), self.targets.index_select(0, idx)
+
+    def denormalize(self, x):
+        return x * self.u_std + self.u_mean
+
+
+class SampleStream:
+    def __init__(self, seed, batch_size, sub_fraction=0.5, k_std=(0.5, 5.0), k_sub=(0.5, 12.0), theta_range=None,
+                 solver="dst", rank=0, world=1, device="cuda", n_coarse=20, n_fine=40, n_superfine=80, n_calib=2048):
+        if not str(device).startswith("cuda"):
+            raise RuntimeError("SampleStream generates on a ROCm device (the HIP path has no CPU fallback)")
+        if batch_size < 1 or not 0.0 <= sub_fraction <= 1.0:
+            raise ValueError("batch_size >= 1 and 0 <= sub_fraction <= 1")
+        if not 0 <= rank < world:
+            raise ValueError(f"rank {rank} outside world {world}")
+        if n_fine != 2 * n_coarse or n_superfine <= n_fine:
+            raise ValueError("n_fine = 2 n_coarse (the stride-2 coarse grid) and n_superfine > n_fine (a window to draw)")
+        self.seed, self.batch_size, self.sub_fraction = int(seed), int(batch_size), float(sub_fraction)
+        self.k_std, self.k_sub = tuple(k_std), tuple(k_sub)
+        self.theta_range = None if theta_range is None else tuple(float(v) for v in theta_range)
+        self.solver = P.check_solver(solver)
+        self.rank, self.world, self.device = int(rank), int(world), device
+        self.n_coarse, self.n_fine, self.n_superfine = n_coarse, n_fine, n_superfine
+        self.step = 0
+        self.last_fields = None
+        if self.solver == "dst":   # the plans are built here, never inside a step (or a stream capture)
+            for n in (n_coarse, n_fine, n_superfine):
+                P.dst_plan(n, device)
+        # frozen statistics, PDEDataset's arithmetic on the calibration set (the one host read of the stream)
+        cal = self.fixed_set(n_calib, CALIB_FIRST)
+        u_mean, u_std = cal["u_fine"].mean(), cal["u_fine"].std()
+        f_mean, f_std = cal["f_fine"].mean(), cal["f_fine"].std()
+        self.theta_is_constant = bool(cal["theta_fine"].std() < 1e-6)
+        if self.theta_is_constant:
+            t_mean, t_std = torch.zeros((), device=device), torch.ones((), device=device)
+        else:
+            t_mean, t_std = cal["theta_fine"].mean(), cal["theta_fine"].std()
+        self.stats = torch.stack([u_mean, u_std, f_mean, f_std, t_mean, t_std]).float().contiguous()
+
+    # ---- generation -------------------------------------------------------------------------------------------
+    def _solve(self, f, theta):
+        return P.solve_batched(f, theta, device=self.device, method=self.solver)
+
+    def _fields(self, first_index: int, n: int, keep: bool = False) -> dict:
+        """The fp32 training fields of samples first_index .. first_index + n - 1 (standard slots first).
+        ``keep``: also the fp64 fields behind them, under "fp64"."""
+        nc, nf, nsf, dev = self.n_coarse, self.n_fine, self.n_superfine, self.device
+        n_std = n_standard(n, self.sub_fraction)
+        n_sub = n - n_std
+        f32 = dict(dtype=torch.float32, device=dev)
+        out = {"u_fine": torch.empty(n, nf, nf, **f32), "f_fine": torch.empty(n, nf, nf, **f32),
+               "theta_fine": torch.empty(n, nf, nf, **f32), "u_coarse": torch.empty(n, nc, nc, **f32)}
+        order = ("u_fine", "f_fine", "theta_fine", "u_coarse")
+        behind = {}
+        if n_std:
+            k, _, th_f, th_c = H.stream_draw(self.seed, first_index, n_std, self.k_std, self.theta_range, n=nf,
+                                             theta_half=True, device=dev)
+            f_f, f_c = P.forcing_batched(k, nf, dev), P.forcing_batched(k, nc, dev)
+            u_f, u_c = self._solve(f_f, th_f), self._solve(f_c, th_c)
+            H.stream_window(u_f, f_f, th_f, None, nf, u_coarse_in=u_c, out=tuple(out[key][:n_std] for key in order))
+            behind["standard"] = {"k12": k, "u_fine": u_f, "f_fine": f_f, "theta_fine": th_f, "u_coarse": u_c,
+                                  "f_coarse": f_c, "theta_coarse": th_c}
+        if n_sub:
+            k, starts, th, _ = H.stream_draw(self.seed, first_index + n_std, n_sub, self.k_sub, self.theta_range, n=nsf,
+                                             max_start=nsf - nf, device=dev)
+            f = P.forcing_batched(k, nsf, dev)
+            u = self._solve(f, th)
+            H.stream_window(u, f, th, starts, nf, out=tuple(out[key][n_std:] for key in order))
+            behind["subdomain"] = {"k12": k, "starts": starts, "u": u, "f": f, "theta": th}
+        flag = np.zeros(n, dtype=bool)
+        flag[n_std:] = True
+        out["is_subdomain"] = flag
+        if keep:
+            out["fp64"] = behind
+        return out
+
+    def _assemble(self, fields: dict):
+        return H.pde_dataset_assemble(fields["u_coarse"], fields["u_fine"], fields["theta_fine"], fields["f_fine"],
+                                      self.stats, self.theta_is_constant)
+
+    def indices(self, step: int = None) -> range:
+        """The global sample indices of this rank's batch at ``step`` (default: the next one)."""
+        return sample_indices(self.step if step is None else step, self.batch_size, self.rank, self.world)
+
+    def next_batch(self, keep_fields: bool = False):
+        """(inputs [B, 3, nf, nf], targets [B, 1, nf, nf]) fp32, normalised with the frozen statistics; stream-ordered,
+        no host sync.  ``keep_fields``: ``self.last_fields`` keeps the batch's fields, the fp64 solves included."""
+        idx = self.indices()
+        if idx.stop > TRAIN_END:
+            raise RuntimeError("SampleStream: the training index range [0, 2^61) is used up")
+        fields = self._fields(idx.start, self.batch_size, keep=keep_fields)
+        self.last_fields = fields if keep_fields else None
+        self.step += 1
+        return self._assemble(fields)
+
+    def fixed_set(self, n: int, first_index: int) -> dict:
+        """The training fields (u_coarse, u_fine, f_fine, theta_fine in fp32 on the device, and the host flag
+        is_subdomain -- what PDEDataset takes) of the n samples first_index .. first_index + n - 1 of a held-out
+        range (CALIB_FIRST.. for calibration, VALID_FIRST.. for validation; module docstring)."""
+        if n < 1 or not any(lo <= first_index and first_index + n <= hi for lo, hi in HELD_OUT):
+            raise ValueError(f"fixed_set: samples [{first_index}, {first_index + n}) are not inside one held-out range "
+                             f"(calibration [2^61, 2^62), validation [2^62, 2^63))")
+        return self._fields(int(first_index), int(n))
+
+    def frozen_set(self, n: int, first_index: int = VALID_FIRST) -> FrozenSet:
+        """``fixed_set`` normalised with the frozen statistics (a validation set)."""
+        return FrozenSet(*self._assemble(self.fixed_set(n, first_index)), self.stats)
+
+    def validation_loader(self, n: int, batch_size: int = None, first_index: int = VALID_FIRST):
+        """A fixed validation loader over ``frozen_set(n, first_index)``: the single-process batches dealt to the
+        ranks (DeviceBatchLoader's shard_batches), so the reduced loss equals the single-process one."""
+        from .train_enhanced import DeviceBatchLoader
+        return DeviceBatchLoader(self.frozen_set(n, first_index), batch_size or self.batch_size, shuffle=False,
+                                 rank=self.rank, world=self.world, shard_batches=True)
+
+    def denormalize(self, x):
+        return x * self.stats[1] + self.stats[0]
+
+    # ---- resuming ---------------------------------------------------------------------------------------------
+    def state_dict(self) -> dict:
+        return {"seed": self.seed, "step": self.step}
+
+    def load_state_dict(self, state: dict):
+        if int(state["seed"]) != self.seed:
+            raise ValueError(f"SampleStream: the state belongs to seed {state['seed']}, this stream has {self.seed}")
+        self.step = int(state["step"])
+
+
+class OnlineBatchLoader:
+    """``steps_per_epoch`` new batches of a SampleStream per pass: a train_loader for train_model."""
+
+    def __init__(self, stream: SampleStream, steps_per_epoch: int):
+        if steps_per_epoch < 1:
+            raise ValueError("steps_per_epoch >= 1")
+        self.stream, self.steps_per_epoch = stream, int(steps_per_epoch)
+
+    def __len__(self):
+        return self.steps_per_epoch
+
+    def __iter__(self):
+        for _ in range(self.steps_per_epoch):
+            yield self.stream.next_batch()
+
+    def denormalize(self, x):
+        return self.stream.denormalize(x)

@@ -11,7 +11,8 @@ checkpoint on improvement; early stopping.  Differences that do not change resul
 * batches are gathered by index on the device (``DeviceBatchLoader``) -- the reference's
   DataLoader workers (:286-300) cannot touch device tensors anyway;
 * ``main`` accepts overrides (``--epochs``, ``--batch-size``, ``--data``, ``--generate``
-  for on-device data generation, config #3) and runs data-parallel over RCCL when
+  for on-device data generation, config #3, ``--online`` for a stream of new samples
+  generated on the device, online.py) and runs data-parallel over RCCL when
   launched with torchrun (one process per GPU, distributed.DataParallel): the generated
   dataset's solves are sharded over the ranks and all-gathered, the batch size is per rank
   (global batch = world x batch), and validation deals the single-process batches to the
@@ -290,12 +291,34 @@ def arg_parser():
                     help="per-rank batch (under torchrun the global batch is world x batch-size, as torch DDP)")
     ap.add_argument("--results", default="results")
     ap.add_argument("--solver", choices=("cg", "dst"), default="cg",
-                    help="Poisson solver of --generate: conjugate gradients (default) or the direct sine transform")
+                    help="Poisson solver of --generate / --online: conjugate gradients (default) or the direct sine "
+                         "transform")
+    ap.add_argument("--online", type=int, metavar="STEPS_PER_EPOCH", default=None,
+                    help="train on a stream of new samples generated on the device (online.SampleStream), this many "
+                         "batches per epoch, instead of a fixed dataset")
+    ap.add_argument("--online-theta", type=float, nargs=2, metavar=("LO", "HI"), default=None,
+                    help="with --online: theta ~ U(LO, HI) per pixel instead of theta = 1")
     return ap
+
+
+ONLINE_VAL_SAMPLES = 400   # the fixed validation set of --online (the default dataset's split: 20 % of 2000)
+
+
+def online_loaders(args, config, rank, world, device):
+    """The loaders of --online: an endless training stream (seed 42, as the rest of main) and a fixed validation
+    set from its held-out indices, both normalised with the stream's frozen statistics."""
+    from .online import OnlineBatchLoader, SampleStream
+    if args.online < 1:
+        raise SystemExit("--online: at least one step per epoch")
+    stream = SampleStream(42, config["batch_size"], theta_range=args.online_theta, solver=args.solver, rank=rank,
+                          world=world, device=device)
+    return OnlineBatchLoader(stream, args.online), stream.validation_loader(ONLINE_VAL_SAMPLES, config["batch_size"])
 
 
 def main(argv=None):
     args = arg_parser().parse_args(argv)
+    if args.online_theta is not None and args.online is None:
+        raise SystemExit("--online-theta needs --online")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world > 1 and not dist.is_initialized():
@@ -321,16 +344,19 @@ def main(argv=None):
             json.dump(config, f, indent=4)
     writer = ScalarWriter(str(save_dir / "tensorboard")) if rank == 0 else None
 
-    if args.generate is not None:
-        data = generate_on_device(*args.generate, solver=args.solver)
+    if args.online is not None:
+        train_loader, val_loader = online_loaders(args, config, rank, world, device)
     else:
-        data = dict(np.load(args.data))
-    train_idx, val_idx = stratified_split(data, config["val_split"], config["stratify_by_subdomain"])
-    train_ds = PDEDataset(select(data, train_idx), device=device)
-    val_ds = PDEDataset(select(data, val_idx), device=device)
-    train_loader = DeviceBatchLoader(train_ds, config["batch_size"], shuffle=True, seed=42, rank=rank, world=world)
-    val_loader = DeviceBatchLoader(val_ds, config["batch_size"], shuffle=False, rank=rank, world=world,
-                                   shard_batches=True)
+        if args.generate is not None:
+            data = generate_on_device(*args.generate, solver=args.solver)
+        else:
+            data = dict(np.load(args.data))
+        train_idx, val_idx = stratified_split(data, config["val_split"], config["stratify_by_subdomain"])
+        train_ds = PDEDataset(select(data, train_idx), device=device)
+        val_ds = PDEDataset(select(data, val_idx), device=device)
+        train_loader = DeviceBatchLoader(train_ds, config["batch_size"], shuffle=True, seed=42, rank=rank, world=world)
+        val_loader = DeviceBatchLoader(val_ds, config["batch_size"], shuffle=False, rank=rank, world=world,
+                                       shard_batches=True)
 
     model = UNet().to(device)
     model.apply(init_weights)

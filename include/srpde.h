@@ -61,8 +61,10 @@ typedef struct ihipStream_t* hipStream_t;
  *      srpde_cascade_stitch_denorm, srpde_field_metrics(_workspace_size)
  *  13  the direct sine-transform Poisson solver: srpde_poisson_dst_plan(_size), srpde_poisson_dst_lds_max_n,
  *      srpde_poisson_dst_workspace_size, srpde_poisson_dst_batched, srpde_poisson_dst_apply
- *  14  the device-side sample stream: srpde_stream_raw, srpde_stream_draw, srpde_stream_window */
-#define SRPDE_ABI_VERSION 14
+ *  14  the device-side sample stream: srpde_stream_raw, srpde_stream_draw, srpde_stream_window
+ *  15  the PDE residual as a loss term and a metric: srpde_physics_loss_workspace_size, srpde_physics_loss_fwd,
+ *      srpde_physics_loss_bwd, srpde_pde_residual_metrics(_workspace_size) */
+#define SRPDE_ABI_VERSION 15
 
 /* Kernel-family bits (per call; bit 0 of the same argument is the accumulate flag): the forward / dgrad
  * families compute the same outputs, statistics and stored splits bit for bit, so these only route a call to
@@ -522,6 +524,37 @@ size_t srpde_mse_workspace_size(void);
 int srpde_mse_fwd(const float* y, const float* t, long long n, float* loss, void* workspace, size_t ws_bytes,
                   hipStream_t stream);
 int srpde_mse_bwd(const float* y, const float* t, long long n, const float* gout, float* dy, hipStream_t stream);
+
+/* ---- MSE plus the residual of the discrete equation the samples solve (no counterpart in the reference, whose
+ *      README lists "physics-informed loss functions that incorporate PDE residuals" as future work) ----------
+ * y, t [B][1][n][n] fp32: normalised prediction and target; x [B][3][n][n] fp32 (NCHW): the model input, channel 1
+ * theta and channel 2 f as the dataset stores them; stats: 6 floats on the device (u_mean, u_std, f_mean, f_std,
+ * theta_mean, theta_std; (0, 1) for a constant theta); kind [B] int32: 0 = whole-domain sample (zero ghost ring, all
+ * n^2 nodes counted, 1 / h^2 = inv_h2_std), 1 = crop of a finer solve (the (n - 2)^2 interior nodes counted,
+ * 1 / h^2 = inv_h2_sub).  With theta = theta_std x1 + theta_mean, f = f_std x2 + f_mean, A the 5-point stencil with
+ * zero outside the grid (A 1 = -(number of missing neighbours)) and m the mask of the counted nodes,
+ *     r    = (theta (u_std A y + u_mean A 1) / h^2 - f) / f_std          (fp32, in this split form)
+ *     loss = {mse + weight pde, mse, pde},  mse = mean((y - t)^2),  pde = sum(m r^2) / M,  M = sum(m)
+ * (fp64 sums in a fixed order: bit-reproducible).  dy_unit (nullable) [B][1][n][n]: the gradient for grad_out = 1,
+ *     2 (y - t) / (B n^2) + weight (2 u_std / (M f_std h^2)) A(m r theta)         (h per sample)
+ * -- NULL: no gradient is computed or written.  3 <= n <= 64.  Two launches, no atomics, no host sync; workspace:
+ * srpde_physics_loss_workspace_size bytes (0 for an unsupported shape), 8-byte aligned.  srpde_physics_loss_bwd:
+ * dy = grad_out[0] * dy_unit over count values (grad_out NULL: 1), one launch. */
+size_t srpde_physics_loss_workspace_size(int B, int n);
+int srpde_physics_loss_fwd(const float* y, const float* t, const float* x, const int* kind, const float* stats, int B,
+                           int n, float weight, float inv_h2_std, float inv_h2_sub, float* loss, float* dy_unit,
+                           void* workspace, size_t ws_bytes, hipStream_t stream);
+int srpde_physics_loss_bwd(const float* dy_unit, long long count, const float* gout, float* dy, hipStream_t stream);
+/* How well raw fields satisfy the discrete equation: out [E][2] fp64 = {sqrt(mean r^2), max |r|} per example over
+ * the counted nodes (all, or the (n - 2)^2 interior ones with interior_only != 0), r = theta A u inv_h2 - f in fp64
+ * with u [E][n][n] fp32 (u_is_f32 != 0) or fp64, f and theta fp64.  r is evaluated as
+ * (theta * (((up + down) + (left + right)) - 4 u)) * inv_h2 - f, every operation rounded on its own, so a host
+ * restatement in that order reproduces it bit for bit.  Two launches; workspace:
+ * srpde_pde_residual_metrics_workspace_size bytes, 8-byte aligned. */
+size_t srpde_pde_residual_metrics_workspace_size(int E, int n);
+int srpde_pde_residual_metrics(const void* u, int u_is_f32, const double* f, const double* theta, int E, int n,
+                               double inv_h2, int interior_only, double* out, void* workspace, size_t ws_bytes,
+                               hipStream_t stream);
 
 /* ---- clip_grad_norm_ + AdamW on one flat buffer (src/train_enhanced.py:74-75,308) ---- */
 size_t srpde_grad_norm_workspace_size(void);

@@ -1,0 +1,338 @@
+// The discrete equation as a loss term and as an evaluation metric, gfx950.
+//
+// Every training sample is a solution of  theta * L u = f  on an n x n grid, L = A / h^2 with A the 5-point
+// stencil (sum of the four neighbours minus 4x the centre).  From the normalised fields the model sees
+// (y = (u - mu_u) / sigma_u, x1 = (theta - mu_t) / sigma_t, x2 = (f - mu_f) / sigma_f) the residual is
+//
+//     r = (theta * (sigma_u * A y + mu_u * A 1) / h^2 - f) / sigma_f
+//
+// in this split form: A y is a difference of O(1) numbers and A 1 = -(number of missing neighbours) is exact, so
+// nothing of the size of mu_u / h^2 is ever added to and subtracted from a single fp32 value.
+//   kind 0 (whole-domain solve): zero ghost ring outside the grid, all n^2 nodes counted;
+//   kind 1 (crop of a finer solve): the ring outside the crop is unknown, so only the (n - 2)^2 interior nodes
+//          are counted (the mask m); the crop's own boundary nodes still enter as neighbours.
+// The two 1 / h^2 values are arguments.
+//
+//   srpde_physics_loss_fwd   loss = mean((y - t)^2) + weight * sum(m r^2) / sum(m)             [2 launches]
+//                            and, when asked, the gradient for grad_out = 1:
+//                            dy = 2 (y - t) / N + weight * (2 sigma_u / (M sigma_f h^2)) A(m r theta)
+//   srpde_physics_loss_bwd   dy = grad_out * that                                                [1 launch]
+//   srpde_pde_residual_metrics  per example (RMS, max |.|) of theta * A u / h^2 - f in fp64     [2 launches]
+//
+// Loss kernel: a workgroup takes spw consecutive samples.  Their y planes are staged in LDS with a zero halo
+// (pitch n + 2), so the stencil needs no bounds test; q = m r theta goes to a second halo tile and y - t to a
+// third plane, so the adjoint (A is symmetric: the same stencil on q) is formed after one barrier without reading
+// global memory again.  y, t, theta and f are each read once.  M = sum(m) follows from the kinds alone, so every
+// workgroup counts it from kind[] (integers, the same value everywhere) and the gradient needs no second pass.
+// Each workgroup leaves fp64 partials {sum (y - t)^2, sum m r^2, sum m}; one block adds them in index order.  The
+// node -> thread -> workgroup assignment depends on the shape alone and there are no atomics: results are
+// bit-reproducible.
+#include "common.h"
+
+namespace srpde {
+namespace {
+
+constexpr int kPhysThreads = 256;
+constexpr int kPhysMaxSpw = 2;            // samples per workgroup, LDS permitting
+constexpr int kPhysLdsBudget = 48 * 1024;
+constexpr int kPhysMinN = 3, kPhysMaxN = 64;
+
+// LDS floats per sample: the y and q halo tiles and the y - t plane
+inline size_t phys_lds_floats(int n) { return 2 * (size_t)(n + 2) * (n + 2) + (size_t)n * n; }
+inline int phys_spw(int n) {
+  const size_t per = phys_lds_floats(n) * sizeof(float);
+  return (int)std::max<size_t>(1, std::min<size_t>(kPhysMaxSpw, kPhysLdsBudget / per));
+}
+inline int phys_blocks(int B, int n) { return ceil_div(B, phys_spw(n)); }
+
+// sum over the 256 threads, valid on thread 0; sh: 4 doubles
+__device__ __forceinline__ double phys_block_sum(double v, double* sh) {
+  v = wave_sum(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+
+__device__ __forceinline__ double phys_wave_max(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+  return v;
+}
+
+// (a + b) + (c + d) - 4 e on a halo tile around p
+__device__ __forceinline__ float stencil5(const float* p, int pitch) {
+  return fmaf(-4.f, p[0], (p[-pitch] + p[pitch]) + (p[-1] + p[1]));
+}
+
+// grid: ceil(B / spw) workgroups; dynamic LDS: spw * phys_lds_floats(n) floats
+__global__ __launch_bounds__(kPhysThreads) void physics_loss_kernel(
+    const float* __restrict__ y, const float* __restrict__ t, const float* __restrict__ x,
+    const int* __restrict__ kind, const float* __restrict__ stats, int B, int n, int spw, float weight, float ih2_std,
+    float ih2_sub, float* __restrict__ dy, double* __restrict__ part) {
+  extern __shared__ float lds[];
+  __shared__ double sh[4];
+  __shared__ long long shM;
+  const int tid = threadIdx.x;
+  const int P = n + 2, T2 = P * P, nn = n * n;
+  const int b0 = blockIdx.x * spw;
+  const int ns = min(spw, B - b0);            // samples of this workgroup (>= 1)
+  float* ytile = lds;                         // [spw][P][P]
+  float* qtile = lds + (size_t)spw * T2;      // [spw][P][P]
+  float* dpl = qtile + (size_t)spw * T2;      // [spw][n][n]
+
+  const float mu_u = stats[0], sg_u = stats[1], mu_f = stats[2], sg_f = stats[3], mu_t = stats[4], sg_t = stats[5];
+
+  // stage y with its zero halo; zero q's halo
+  for (int k = tid; k < ns * T2; k += kPhysThreads) {
+    const int s = k / T2, rem = k - s * T2;
+    const int ii = rem / P, jj = rem - ii * P;
+    const bool inner = ii >= 1 && ii <= n && jj >= 1 && jj <= n;
+    float v = 0.f;
+    if (inner) v = y[(long long)(b0 + s) * nn + (ii - 1) * n + (jj - 1)];
+    ytile[k] = v;
+    if (!inner) qtile[k] = 0.f;
+  }
+  // M = sum of the masks of the whole batch, from the kinds (only the gradient's scale needs it here)
+  if (dy != nullptr) {
+    long long cnt = 0;
+    for (int b = tid; b < B; b += kPhysThreads) cnt += kind[b] ? (long long)(n - 2) * (n - 2) : (long long)nn;
+    const double tot = phys_block_sum((double)cnt, sh);   // exact: integers far below 2^53
+    if (tid == 0) shM = (long long)tot;
+  }
+  __syncthreads();
+
+  double sse = 0.0, spr = 0.0, sm = 0.0;
+  for (int k = tid; k < ns * nn; k += kPhysThreads) {
+    const int s = k / nn, rem = k - s * nn;
+    const int i = rem / n, j = rem - i * n;
+    const long long b = b0 + s;
+    const long long g = b * nn + rem;
+    const float* xb = x + b * 3 * nn + rem;
+    const float th = fmaf(sg_t, xb[nn], mu_t);
+    const float f = fmaf(sg_f, xb[2 * nn], mu_f);
+    const float tv = t[g];
+    const int kd = kind[b];
+    const float ih2 = kd ? ih2_sub : ih2_std;
+    const float* yc = ytile + s * T2 + (i + 1) * P + (j + 1);
+    const float ay = stencil5(yc, P);
+    const int edge_i = (i == 0) + (i == n - 1), edge_j = (j == 0) + (j == n - 1);
+    const float a1 = -(float)(edge_i + edge_j);
+    const bool m = !kd || (edge_i + edge_j == 0);
+    const float lap = fmaf(sg_u, ay, mu_u * a1);
+    const float r = (th * lap * ih2 - f) / sg_f;
+    const float d = yc[0] - tv;
+    sse += (double)(d * d);
+    if (m) {
+      spr += (double)r * (double)r;
+      sm += 1.0;
+    }
+    if (dy != nullptr) {
+      qtile[s * T2 + (i + 1) * P + (j + 1)] = m ? r * th : 0.f;
+      dpl[k] = d;
+    }
+  }
+
+  if (dy != nullptr) {
+    __syncthreads();
+    const double M = (double)shM;
+    const double base = 2.0 * (double)weight * (double)sg_u / (M * (double)sg_f);
+    const float c_std = (float)(base * (double)ih2_std), c_sub = (float)(base * (double)ih2_sub);
+    const float c_mse = (float)(2.0 / ((double)B * (double)nn));
+    for (int k = tid; k < ns * nn; k += kPhysThreads) {
+      const int s = k / nn, rem = k - s * nn;
+      const int i = rem / n, j = rem - i * n;
+      const long long b = b0 + s;
+      const float aq = stencil5(qtile + s * T2 + (i + 1) * P + (j + 1), P);
+      dy[b * nn + rem] = fmaf(kind[b] ? c_sub : c_std, aq, c_mse * dpl[k]);
+    }
+  }
+
+  sse = phys_block_sum(sse, sh);
+  spr = phys_block_sum(spr, sh);
+  sm = phys_block_sum(sm, sh);
+  if (tid == 0) {
+    double* o = part + (long long)blockIdx.x * 3;
+    o[0] = sse;
+    o[1] = spr;
+    o[2] = sm;
+  }
+}
+
+// one block: loss = {mse + weight * pde, mse, pde}
+__global__ __launch_bounds__(kPhysThreads) void physics_loss_final_kernel(const double* __restrict__ part, int nblk,
+                                                                           long long N, float weight,
+                                                                           float* __restrict__ loss) {
+  __shared__ double sh[4];
+  double a = 0.0, b = 0.0, c = 0.0;
+  for (int k = threadIdx.x; k < nblk; k += kPhysThreads) {
+    a += part[3 * (long long)k];
+    b += part[3 * (long long)k + 1];
+    c += part[3 * (long long)k + 2];
+  }
+  a = phys_block_sum(a, sh);
+  b = phys_block_sum(b, sh);
+  c = phys_block_sum(c, sh);
+  if (threadIdx.x == 0) {
+    const double mse = a / (double)N, pde = b / c;
+    loss[0] = (float)(mse + (double)weight * pde);
+    loss[1] = (float)mse;
+    loss[2] = (float)pde;
+  }
+}
+
+__global__ void physics_scale_kernel(const float* __restrict__ unit, long long n, const float* __restrict__ gout,
+                                     float* __restrict__ dy) {
+  const float g = gout ? gout[0] : 1.f;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+    dy[i] = unit[i] * g;
+}
+
+// ---- the residual metric ---------------------------------------------------------------------------------
+constexpr int kResThreads = 256;
+constexpr int kResChunk = 2048;
+constexpr int kResMaxBlocks = 256;
+
+inline int res_blocks(long long nn) {
+  return (int)std::min<long long>(std::max<long long>((nn + kResChunk - 1) / kResChunk, 1), kResMaxBlocks);
+}
+
+// grid (res_blocks, E): part[(e * nb + b) * 2] = {sum r^2, max |r|} over the counted nodes.  Every operation is
+// rounded on its own (no contraction), in the order of the header's formula, so a host restatement in that order
+// reproduces r bit for bit.
+template <typename TU>
+__global__ __launch_bounds__(kResThreads) void pde_residual_partial_kernel(const TU* __restrict__ u,
+                                                                           const double* __restrict__ f,
+                                                                           const double* __restrict__ theta, int n,
+                                                                           double inv_h2, int interior_only,
+                                                                           double* __restrict__ part) {
+#pragma clang fp contract(off)
+  __shared__ double sh[4];
+  const int e = blockIdx.y;
+  const long long nn = (long long)n * n;
+  const TU* ue = u + e * nn;
+  const double* fe = f + e * nn;
+  const double* te = theta + e * nn;
+  double sq = 0.0, mx = 0.0;
+  for (long long k = (long long)blockIdx.x * kResThreads + threadIdx.x; k < nn; k += (long long)gridDim.x * kResThreads) {
+    const int i = (int)(k / n), j = (int)(k - (long long)i * n);
+    const bool edge = i == 0 || i == n - 1 || j == 0 || j == n - 1;
+    if (interior_only && edge) continue;
+    const double up = i > 0 ? (double)ue[k - n] : 0.0, dn = i < n - 1 ? (double)ue[k + n] : 0.0;
+    const double lf = j > 0 ? (double)ue[k - 1] : 0.0, rt = j < n - 1 ? (double)ue[k + 1] : 0.0;
+    const double lap = ((up + dn) + (lf + rt)) - 4.0 * (double)ue[k];
+    const double r = (te[k] * lap) * inv_h2 - fe[k];
+    sq += r * r;
+    mx = fmax(mx, fabs(r));
+  }
+  sq = phys_block_sum(sq, sh);
+  mx = phys_wave_max(mx);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = mx;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double* o = part + ((long long)e * gridDim.x + blockIdx.x) * 2;
+    o[0] = sq;
+    o[1] = fmax(fmax(sh[0], sh[1]), fmax(sh[2], sh[3]));
+  }
+}
+
+__global__ __launch_bounds__(64) void pde_residual_final_kernel(const double* __restrict__ part, int nb, double count,
+                                                                double* __restrict__ out) {
+  const int e = blockIdx.x, lane = threadIdx.x;
+  const double* p = part + (long long)e * nb * 2;
+  double sq = 0.0, mx = 0.0;
+  for (int j = lane; j < nb; j += 64) {
+    sq += p[2 * j];
+    mx = fmax(mx, p[2 * j + 1]);
+  }
+  sq = wave_sum(sq);
+  mx = phys_wave_max(mx);
+  if (lane == 0) {
+    out[e * 2] = sqrt(sq / count);
+    out[e * 2 + 1] = mx;
+  }
+}
+
+}  // namespace
+}  // namespace srpde
+
+using namespace srpde;
+
+#define PHYS_FAIL(code, ...)         \
+  do {                               \
+    ::srpde::set_error(__VA_ARGS__); \
+    return code;                     \
+  } while (0)
+
+extern "C" {
+
+size_t srpde_physics_loss_workspace_size(int B, int n) {
+  if (B <= 0 || n < kPhysMinN || n > kPhysMaxN) return 0;
+  return (size_t)phys_blocks(B, n) * 3 * sizeof(double);
+}
+
+int srpde_physics_loss_fwd(const float* y, const float* t, const float* x, const int* kind, const float* stats, int B,
+                           int n, float weight, float inv_h2_std, float inv_h2_sub, float* loss, float* dy_unit,
+                           void* workspace, size_t ws_bytes, hipStream_t stream) {
+  SRPDE_CHECK_ARG(y && t && x && kind && stats && loss && workspace, "srpde_physics_loss_fwd: null pointer");
+  if (B <= 0 || n < kPhysMinN || n > kPhysMaxN)
+    PHYS_FAIL(kErrShape, "srpde_physics_loss_fwd: bad shape B=%d n=%d (B >= 1, %d <= n <= %d)", B, n, kPhysMinN,
+              kPhysMaxN);
+  if (reinterpret_cast<uintptr_t>(workspace) & 7u)
+    PHYS_FAIL(kErrAlign, "srpde_physics_loss_fwd: workspace not 8-byte aligned");
+  if (ws_bytes < srpde_physics_loss_workspace_size(B, n))
+    PHYS_FAIL(kErrWorkspace, "srpde_physics_loss_fwd: workspace too small");
+  const int spw = phys_spw(n), nb = phys_blocks(B, n);
+  const size_t lds = (size_t)spw * phys_lds_floats(n) * sizeof(float);
+  double* part = static_cast<double*>(workspace);
+  hipLaunchKernelGGL(physics_loss_kernel, dim3(nb), dim3(kPhysThreads), lds, stream, y, t, x, kind, stats, B, n, spw,
+                     weight, inv_h2_std, inv_h2_sub, dy_unit, part);
+  SRPDE_LAUNCH_CHECK("srpde_physics_loss_fwd");
+  hipLaunchKernelGGL(physics_loss_final_kernel, dim3(1), dim3(kPhysThreads), 0, stream, part, nb,
+                     (long long)B * n * n, weight, loss);
+  SRPDE_LAUNCH_CHECK("srpde_physics_loss_fwd");
+  return 0;
+}
+
+int srpde_physics_loss_bwd(const float* dy_unit, long long count, const float* gout, float* dy, hipStream_t stream) {
+  SRPDE_CHECK_ARG(dy_unit && dy, "srpde_physics_loss_bwd: null pointer");
+  if (count <= 0) PHYS_FAIL(kErrShape, "srpde_physics_loss_bwd: bad count %lld", count);
+  const int nb = (int)std::min<long long>((count + 255) / 256, 8192);
+  hipLaunchKernelGGL(physics_scale_kernel, dim3(nb), dim3(256), 0, stream, dy_unit, count, gout, dy);
+  SRPDE_LAUNCH_CHECK("srpde_physics_loss_bwd");
+  return 0;
+}
+
+size_t srpde_pde_residual_metrics_workspace_size(int E, int n) {
+  if (E <= 0 || n <= 0) return 0;
+  return (size_t)E * res_blocks((long long)n * n) * 2 * sizeof(double);
+}
+
+int srpde_pde_residual_metrics(const void* u, int u_is_f32, const double* f, const double* theta, int E, int n,
+                               double inv_h2, int interior_only, double* out, void* workspace, size_t ws_bytes,
+                               hipStream_t stream) {
+  SRPDE_CHECK_ARG(u && f && theta && out && workspace, "srpde_pde_residual_metrics: null pointer");
+  if (E <= 0 || n <= 0 || E > 65535 || n > 16384 || (interior_only && n < 3))
+    PHYS_FAIL(kErrShape, "srpde_pde_residual_metrics: bad shape E=%d n=%d (interior_only needs n >= 3)", E, n);
+  if (reinterpret_cast<uintptr_t>(workspace) & 7u)
+    PHYS_FAIL(kErrAlign, "srpde_pde_residual_metrics: workspace not 8-byte aligned");
+  if (ws_bytes < srpde_pde_residual_metrics_workspace_size(E, n))
+    PHYS_FAIL(kErrWorkspace, "srpde_pde_residual_metrics: workspace too small");
+  const long long nn = (long long)n * n;
+  const int nb = res_blocks(nn);
+  const double count = interior_only ? (double)(n - 2) * (n - 2) : (double)nn;
+  double* part = static_cast<double*>(workspace);
+  if (u_is_f32)
+    hipLaunchKernelGGL(pde_residual_partial_kernel<float>, dim3(nb, E), dim3(kResThreads), 0, stream,
+                       static_cast<const float*>(u), f, theta, n, inv_h2, interior_only, part);
+  else
+    hipLaunchKernelGGL(pde_residual_partial_kernel<double>, dim3(nb, E), dim3(kResThreads), 0, stream,
+                       static_cast<const double*>(u), f, theta, n, inv_h2, interior_only, part);
+  SRPDE_LAUNCH_CHECK("srpde_pde_residual_metrics");
+  hipLaunchKernelGGL(pde_residual_final_kernel, dim3(E), dim3(64), 0, stream, part, nb, count, out);
+  SRPDE_LAUNCH_CHECK("srpde_pde_residual_metrics");
+  return 0;
+}
+
+}  // extern "C"

@@ -39,3 +39,83 @@ class MSELoss(nn.Module):
 
     def forward(self, input: torch.Tensor, target: torch.Tensor) -> torch.Tensor:  # noqa: A002
         return mse_loss(input, target)
+
+
+# 1 / h^2 of the training samples: a whole-domain solve on 40^2 nodes, a 40^2 crop of a solve on 80^2 nodes
+DEFAULT_INV_H2 = (39.0 ** 2, 79.0 ** 2)
+
+
+class _PhysicsMSEFn(torch.autograd.Function):
+    """(terms [3] = (total, mse, pde)) of srpde_physics_loss_fwd; only terms[0] carries a gradient.  The forward
+    pass emits the gradient for grad_out = 1 (when one is wanted), the backward pass scales it."""
+
+    @staticmethod
+    def forward(ctx, y, t, x, kind, stats, weight, inv_h2, want_grad):
+        terms, unit = H.physics_loss_fwd(y, t, x, kind, stats, weight, inv_h2, want_grad)
+        ctx.unit = unit
+        return terms
+
+    @staticmethod
+    def backward(ctx, gterms):
+        if ctx.unit is None:
+            raise RuntimeError("physics_mse_loss: backward through a loss evaluated without a gradient")
+        dy = H.physics_loss_bwd(ctx.unit, gterms.contiguous())   # reads gterms[0], the total's grad_out
+        return dy, None, None, None, None, None, None, None
+
+
+def physics_loss_terms(y, t, x, kind, stats, weight, inv_h2=DEFAULT_INV_H2):
+    """The device tensor (mse + weight * pde, mse, pde) behind ``physics_mse_loss``; differentiable through its
+    first element only (the other two are reports of the same pass)."""
+    if y.shape != t.shape:
+        raise ValueError(f"physics_mse_loss: shape mismatch {tuple(y.shape)} vs {tuple(t.shape)}")
+    if y.dim() != 4 or y.shape[1] != 1 or y.shape[2] != y.shape[3]:
+        raise ValueError(f"physics_mse_loss: fields must be [B, 1, n, n], got {tuple(y.shape)}")
+    B, _, n, _ = y.shape
+    if tuple(x.shape) != (B, 3, n, n):
+        raise ValueError(f"physics_mse_loss: the model input must be [{B}, 3, {n}, {n}], got {tuple(x.shape)}")
+    if tuple(kind.shape) != (B,) or kind.dtype != torch.int32:
+        raise ValueError(f"physics_mse_loss: kind must be [{B}] int32, got {tuple(kind.shape)} {kind.dtype}")
+    if stats.numel() != 6:
+        raise ValueError("physics_mse_loss: stats = (u_mean, u_std, f_mean, f_std, theta_mean, theta_std)")
+    if not 3 <= n <= 64:
+        raise ValueError(f"physics_mse_loss: 3 <= n <= 64, got n={n}")
+    if len(inv_h2) != 2:
+        raise ValueError("physics_mse_loss: inv_h2 = (1 / h^2 of kind 0, 1 / h^2 of kind 1)")
+    for v in (y, t, x, kind, stats):
+        if not v.is_cuda:
+            raise RuntimeError("physics_mse_loss: HIP path needs ROCm tensors (no CPU fallback)")
+    if not all(v.dtype == torch.float32 for v in (y, t, x, stats)):
+        raise RuntimeError("physics_mse_loss: HIP path needs float32 ROCm tensors (no CPU fallback)")
+    want_grad = torch.is_grad_enabled() and y.requires_grad
+    return _PhysicsMSEFn.apply(y.contiguous(), t.contiguous(), x.contiguous(), kind.contiguous(),
+                               stats.contiguous(), float(weight), (float(inv_h2[0]), float(inv_h2[1])), want_grad)
+
+
+def physics_mse_loss(y, t, x, kind, stats, weight, inv_h2=DEFAULT_INV_H2) -> torch.Tensor:
+    """mean((y - t)^2) + weight * L_pde: the MSE plus the mean squared residual of the discrete equation
+    theta * L u = f that the samples solve, evaluated from the normalised fields (include/srpde.h,
+    srpde_physics_loss_fwd).  x: the model input (theta and f are its channels 1 and 2), kind [B] int32: 0 for a
+    whole-domain sample, 1 for a crop; stats: the dataset's six statistics on the device."""
+    return physics_loss_terms(y, t, x, kind, stats, weight, inv_h2)[0]
+
+
+class PhysicsMSELoss(nn.Module):
+    """``criterion(outputs, targets, inputs, kind)``: MSE + weight * PDE residual.  ``needs_inputs`` tells
+    train_model to pass the batch's inputs and kinds; ``last_terms`` holds the last call's (total, mse, pde) as a
+    device tensor (no host sync)."""
+
+    needs_inputs = True
+
+    def __init__(self, weight: float, stats: torch.Tensor, inv_h2=DEFAULT_INV_H2):
+        super().__init__()
+        if weight < 0:
+            raise ValueError("PhysicsMSELoss: weight >= 0")
+        self.weight = float(weight)
+        self.inv_h2 = (float(inv_h2[0]), float(inv_h2[1]))
+        self.register_buffer("stats", stats.detach().float().contiguous().clone(), persistent=False)
+        self.last_terms = None
+
+    def forward(self, input, target, x, kind):  # noqa: A002
+        terms = physics_loss_terms(input, target, x, kind, self.stats, self.weight, self.inv_h2)
+        self.last_terms = terms.detach()
+        return terms[0]

@@ -1148,6 +1148,55 @@ def mse_bwd(y, t, gout):
     return dy
 
 
+# ------------------------------ MSE + PDE residual ---------------------------------
+def physics_loss_fwd(y, t, x, kind, stats, weight, inv_h2, want_grad=True):
+    """srpde_physics_loss_fwd: y, t [B, 1, n, n] and x [B, 3, n, n] fp32, kind [B] int32, stats 6 floats, all on one
+    device -> (loss [3] = (mse + weight * pde, mse, pde), the gradient for grad_out = 1 or None).  ``inv_h2``: the
+    1 / h^2 of (kind 0, kind 1).  Without ``want_grad`` no gradient is computed or written."""
+    _fields("physics_loss_fwd", F32, y, t, x, stats)
+    _fields("physics_loss_fwd", torch.int32, kind)
+    if y.dim() != 4 or y.shape[1] != 1 or y.shape[2] != y.shape[3] or t.shape != y.shape:
+        raise ValueError(f"physics_loss_fwd: y and t must share one [B, 1, n, n] shape, got {tuple(y.shape)} and "
+                         f"{tuple(t.shape)}")
+    B, _, n, _ = y.shape
+    if x.shape != (B, 3, n, n) or kind.shape != (B,) or stats.numel() != 6:
+        raise ValueError(f"physics_loss_fwd: x must be [{B}, 3, {n}, {n}], kind [{B}], stats 6 values; got "
+                         f"{tuple(x.shape)}, {tuple(kind.shape)}, {stats.numel()}")
+    nbytes = int(query("srpde_physics_loss_workspace_size", B, n))
+    ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=y.device)
+    loss = torch.empty(3, dtype=F32, device=y.device)
+    unit = torch.empty_like(y) if want_grad else None
+    call("srpde_physics_loss_fwd", y.data_ptr(), t.data_ptr(), x.data_ptr(), kind.data_ptr(), stats.data_ptr(), B, n,
+         float(weight), float(inv_h2[0]), float(inv_h2[1]), loss.data_ptr(), _p(unit), ws.data_ptr(), nbytes,
+         stream_ptr())
+    return loss, unit
+
+
+def physics_loss_bwd(unit, gout):
+    """srpde_physics_loss_bwd: grad_out (a device scalar, or None for 1) times the unit gradient."""
+    dy = torch.empty_like(unit)
+    call("srpde_physics_loss_bwd", unit.data_ptr(), unit.numel(), _p(gout), dy.data_ptr(), stream_ptr())
+    return dy
+
+
+def pde_residual_metrics(u, f, theta, inv_h2, interior_only=False):
+    """srpde_pde_residual_metrics: raw fields u [E, n, n] (fp32 or fp64), f and theta fp64 -> [E, 2] fp64 device tensor
+    of (RMS, max abs) of theta * A u * inv_h2 - f per example, over all nodes or the interior ones."""
+    _fields("pde_residual_metrics", torch.float64, f, theta)
+    if u.dtype not in (F32, torch.float64):
+        raise RuntimeError("pde_residual_metrics: u must be fp32 or fp64")
+    _fields("pde_residual_metrics", u.dtype, u)
+    if f.dim() != 3 or f.shape[1] != f.shape[2] or u.shape != f.shape or theta.shape != f.shape:
+        raise ValueError("pde_residual_metrics: u, f and theta must share one [E, n, n] shape")
+    E, n, _ = f.shape
+    out = torch.empty(E, 2, dtype=torch.float64, device=f.device)
+    nbytes = int(query("srpde_pde_residual_metrics_workspace_size", E, n))
+    ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=f.device)
+    call("srpde_pde_residual_metrics", u.data_ptr(), int(u.dtype == F32), f.data_ptr(), theta.data_ptr(), E, n,
+         float(inv_h2), int(bool(interior_only)), out.data_ptr(), ws.data_ptr(), nbytes, stream_ptr())
+    return out
+
+
 # ----------------------------------- optimizer -------------------------------------
 def clip_coef(flat_grad, grad_scale, max_norm, coef):
     ws_bytes = int(query("srpde_grad_norm_workspace_size"))

@@ -252,6 +252,8 @@ class PDEDataset(torch.utils.data.Dataset):
         self.has_subdomain_flag = "is_subdomain" in data_dict
         if self.has_subdomain_flag:
             self.is_subdomain = torch.as_tensor(data_dict["is_subdomain"]).bool().to(device)
+        # 0 = whole-domain sample, 1 = crop of a finer solve (functional.physics_mse_loss); None: unknown
+        self.kind = self.is_subdomain.to(torch.int32) if self.has_subdomain_flag else None
         self.u_mean = self.u_fine.mean()
         self.u_std = self.u_fine.std()
         self.f_mean = self.f_fine.mean()
@@ -269,6 +271,7 @@ class PDEDataset(torch.utils.data.Dataset):
         tm = zero if self.theta_is_constant else self.theta_mean
         ts = one if self.theta_is_constant else self.theta_std
         stats = torch.stack([self.u_mean, self.u_std, self.f_mean, self.f_std, tm, ts]).float().contiguous()
+        self.stats = stats
         self.inputs, self.targets = H.pde_dataset_assemble(self.u_coarse.contiguous(), self.u_fine.contiguous(),
                                                            self.theta_fine.contiguous(), self.f_fine.contiguous(),
                                                            stats, self.theta_is_constant)
@@ -300,8 +303,13 @@ class PDEDataset(torch.utils.data.Dataset):
     def __getitem__(self, idx: int) -> Tuple[torch.Tensor, torch.Tensor]:
         return self.inputs[idx], self.targets[idx]
 
-    def batch(self, idx):
-        return self.inputs.index_select(0, idx), self.targets.index_select(0, idx)
+    def batch(self, idx, with_kind: bool = False):
+        if not with_kind:
+            return self.inputs.index_select(0, idx), self.targets.index_select(0, idx)
+        if self.kind is None:
+            raise ValueError("PDEDataset: sample kinds were asked for, but the data has no 'is_subdomain' flags, so the "
+                             "grid spacing of its samples is unknown")
+        return self.inputs.index_select(0, idx), self.targets.index_select(0, idx), self.kind.index_select(0, idx)
 
     def denormalize(self, x: torch.Tensor) -> torch.Tensor:
         return x * self.u_std + self.u_mean

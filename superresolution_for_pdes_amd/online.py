@@ -58,11 +58,18 @@ def n_standard(n: int, sub_fraction: float) -> int:
     return n - int(round(n * sub_fraction))
 
 
-class FrozenSet:
-    """A fixed set normalised with a stream's frozen statistics: what DeviceBatchLoader needs of a PDEDataset."""
+def slot_kinds(n: int, sub_fraction: float) -> list:
+    """The kind of each of n slots: 0 for the standard samples (first), 1 for the subdomain samples."""
+    n_std = n_standard(n, sub_fraction)
+    return [0] * n_std + [1] * (n - n_std)
 
-    def __init__(self, inputs, targets, stats):
-        self.inputs, self.targets, self.stats = inputs, targets, stats
+
+class FrozenSet:
+    """A fixed set normalised with a stream's frozen statistics: what DeviceBatchLoader needs of a PDEDataset.
+    ``kind`` (optional): [N] int32 on the device, 0 = standard sample, 1 = subdomain sample."""
+
+    def __init__(self, inputs, targets, stats, kind=None):
+        self.inputs, self.targets, self.stats, self.kind = inputs, targets, stats, kind
         self.u_mean, self.u_std = stats[0], stats[1]
 
     def __len__(self):
@@ -71,8 +78,12 @@ class FrozenSet:
     def __getitem__(self, idx):
         return self.inputs[idx], self.targets[idx]
 
-    def batch(self, idx):
-        return self.inputs.index_select(0, idx), self.targets.index_select(0, idx)
+    def batch(self, idx, with_kind: bool = False):
+        if not with_kind:
+            return self.inputs.index_select(0, idx), self.targets.index_select(0, idx)
+        if self.kind is None:
+            raise ValueError("FrozenSet: sample kinds were asked for, but the set was built without them")
+        return self.inputs.index_select(0, idx), self.targets.index_select(0, idx), self.kind.index_select(0, idx)
 
     def denormalize(self, x):
         return x * self.u_std + self.u_mean
@@ -110,6 +121,10 @@ class SampleStream:
         else:
             t_mean, t_std = cal["theta_fine"].mean(), cal["theta_fine"].std()
         self.stats = torch.stack([u_mean, u_std, f_mean, f_std, t_mean, t_std]).float().contiguous()
+        self.kind = self._kinds(self.batch_size)   # every batch has the same slots
+
+    def _kinds(self, n: int):
+        return torch.tensor(slot_kinds(n, self.sub_fraction), dtype=torch.int32, device=self.device)
 
     # ---- generation -------------------------------------------------------------------------------------------
     def _solve(self, f, theta):
@@ -156,15 +171,19 @@ class SampleStream:
         """The global sample indices of this rank's batch at ``step`` (default: the next one)."""
         return sample_indices(self.step if step is None else step, self.batch_size, self.rank, self.world)
 
-    def next_batch(self, keep_fields: bool = False):
+    def next_batch(self, keep_fields: bool = False, with_kind: bool = False):
         """(inputs [B, 3, nf, nf], targets [B, 1, nf, nf]) fp32, normalised with the frozen statistics; stream-ordered,
-        no host sync.  ``keep_fields``: ``self.last_fields`` keeps the batch's fields, the fp64 solves included."""
+        no host sync.  ``keep_fields``: ``self.last_fields`` keeps the batch's fields, the fp64 solves included.
+        ``with_kind``: a third element, the slots' kinds [B] int32 (0 standard, 1 subdomain; the same tensor every
+        batch)."""
         idx = self.indices()
         if idx.stop > TRAIN_END:
             raise RuntimeError("SampleStream: the training index range [0, 2^61) is used up")
         fields = self._fields(idx.start, self.batch_size, keep=keep_fields)
         self.last_fields = fields if keep_fields else None
         self.step += 1
+        if with_kind:
+            return (*self._assemble(fields), self.kind)
         return self._assemble(fields)
 
     def fixed_set(self, n: int, first_index: int) -> dict:
@@ -178,14 +197,15 @@ class SampleStream:
 
     def frozen_set(self, n: int, first_index: int = VALID_FIRST) -> FrozenSet:
         """``fixed_set`` normalised with the frozen statistics (a validation set)."""
-        return FrozenSet(*self._assemble(self.fixed_set(n, first_index)), self.stats)
+        return FrozenSet(*self._assemble(self.fixed_set(n, first_index)), self.stats, self._kinds(n))
 
-    def validation_loader(self, n: int, batch_size: int = None, first_index: int = VALID_FIRST):
+    def validation_loader(self, n: int, batch_size: int = None, first_index: int = VALID_FIRST,
+                          with_kind: bool = False):
         """A fixed validation loader over ``frozen_set(n, first_index)``: the single-process batches dealt to the
         ranks (DeviceBatchLoader's shard_batches), so the reduced loss equals the single-process one."""
         from .train_enhanced import DeviceBatchLoader
         return DeviceBatchLoader(self.frozen_set(n, first_index), batch_size or self.batch_size, shuffle=False,
-                                 rank=self.rank, world=self.world, shard_batches=True)
+                                 rank=self.rank, world=self.world, shard_batches=True, with_kind=with_kind)
 
     def denormalize(self, x):
         return x * self.stats[1] + self.stats[0]
@@ -203,17 +223,17 @@ class SampleStream:
 class OnlineBatchLoader:
     """``steps_per_epoch`` new batches of a SampleStream per pass: a train_loader for train_model."""
 
-    def __init__(self, stream: SampleStream, steps_per_epoch: int):
+    def __init__(self, stream: SampleStream, steps_per_epoch: int, with_kind: bool = False):
         if steps_per_epoch < 1:
             raise ValueError("steps_per_epoch >= 1")
-        self.stream, self.steps_per_epoch = stream, int(steps_per_epoch)
+        self.stream, self.steps_per_epoch, self.with_kind = stream, int(steps_per_epoch), with_kind
 
     def __len__(self):
         return self.steps_per_epoch
 
     def __iter__(self):
         for _ in range(self.steps_per_epoch):
-            yield self.stream.next_batch()
+            yield self.stream.next_batch(with_kind=self.with_kind)
 
     def denormalize(self, x):
         return self.stream.denormalize(x)

@@ -121,6 +121,26 @@ def dst2(x, device="cuda"):
     return y[0] if single else y
 
 
+def residual_metrics(u, f, theta, interior_only: bool = False, inv_h2: float = None, device="cuda"):
+    """How well raw fields satisfy the discrete equation: [E, 2] fp64 device tensor of (RMS, max abs) of
+    theta * A u / h^2 - f per example (A the 5-point stencil with a zero ghost ring).  u [E, n, n] fp32 or fp64
+    (a tensor keeps its precision), f and theta fp64.  ``inv_h2`` defaults to (n - 1)^2, the whole-domain operator
+    solve_batched / solve_multi_resolution solve; ``interior_only`` leaves the boundary nodes out (a crop of a
+    larger solve, whose ring is not zero).  Stream-ordered, no host sync (srpde_pde_residual_metrics)."""
+    from . import hipops as H
+    if isinstance(u, torch.Tensor) and u.dtype == torch.float32:
+        u = u.to(device).contiguous()
+    else:
+        u = _dev_f64(u, device)
+    f, theta = _dev_f64(f, device), _dev_f64(theta, device)
+    if u.dim() == 2:
+        u, f, theta = u.unsqueeze(0), f.unsqueeze(0), theta.unsqueeze(0)
+    if theta.shape != f.shape:
+        theta = theta.expand_as(f).contiguous()
+    n = u.shape[-1]
+    return H.pde_residual_metrics(u, f, theta, float((n - 1) ** 2 if inv_h2 is None else inv_h2), interior_only)
+
+
 def solve_batched(f, theta, rtol: float = DEFAULT_RTOL, maxit: int = None, device="cuda",
                   return_iters: bool = False, check: bool = True, _start_aborted: bool = False,
                   method: str = "cg"):

@@ -72,13 +72,15 @@ class DeviceBatchLoader:
     strided shard of it (DistributedSampler semantics: ``batch_size`` is per rank, the global
     batch is world x batch_size, as under torch DDP).  ``shard_batches`` (evaluation): the
     single-process batches themselves are dealt round-robin to the ranks, unpadded, so the
-    all-reduced (sum of batch losses, batch count) gives exactly the single-process mean."""
+    all-reduced (sum of batch losses, batch count) gives exactly the single-process mean.
+    ``with_kind``: batches are (inputs, targets, kind), the dataset's ``batch(idx, with_kind=True)``."""
 
     def __init__(self, dataset, batch_size, shuffle=False, seed=0, rank=0, world=1, drop_last=False,
-                 shard_batches=False):
+                 shard_batches=False, with_kind=False):
         self.ds, self.bs, self.shuffle = dataset, batch_size, shuffle
         self.seed, self.rank, self.world, self.drop_last = seed, rank, world, drop_last
         self.shard_batches = shard_batches
+        self.with_kind = with_kind
         self.epoch = 0
 
     def _indices(self):
@@ -106,7 +108,7 @@ class DeviceBatchLoader:
         idx = self._indices().to(self.ds.inputs.device)
         self.epoch += 1
         for b in self._batches(idx):
-            yield self.ds.batch(b)
+            yield self.ds.batch(b, with_kind=True) if self.with_kind else self.ds.batch(b)
 
 
 def _is_main():
@@ -122,6 +124,29 @@ def _global_mean(total, count, device):
     return float(t[0] / torch.clamp(t[1], min=1.0))
 
 
+def _global_means(totals, count, device):
+    """``_global_mean`` for a vector of sums sharing one batch count -> a list of means (one all-reduce)."""
+    t = torch.cat([totals.to(torch.float64), torch.tensor([float(count)], dtype=torch.float64, device=device)])
+    if dist.is_initialized() and dist.get_world_size() > 1:
+        dist.all_reduce(t)
+    return (t[:-1] / torch.clamp(t[-1], min=1.0)).tolist()
+
+
+def _unpack(batch, device):
+    """(inputs, targets, kind or None) of a 2- or 3-tuple batch, on ``device``."""
+    inputs, targets = batch[0].to(device), batch[1].to(device)
+    return inputs, targets, (batch[2].to(device) if len(batch) > 2 else None)
+
+
+def _criterion_call(criterion, outputs, targets, inputs, kind):
+    if getattr(criterion, "needs_inputs", False):
+        if kind is None:
+            raise ValueError("this criterion needs (inputs, targets, kind) batches: build the loaders with "
+                             "with_kind=True")
+        return criterion(outputs, targets, inputs, kind)
+    return criterion(outputs, targets)
+
+
 def train_model(model: nn.Module, train_loader, val_loader, criterion: nn.Module, optimizer: optim.Optimizer,
                 scheduler, num_epochs: int, device: str, save_dir: Path, writer, grad_clip: float = 1.0,
                 early_stopping_patience: int = 20) -> dict:
@@ -131,15 +156,21 @@ def train_model(model: nn.Module, train_loader, val_loader, criterion: nn.Module
     save_dir = Path(save_dir)
     fused = isinstance(optimizer, FusedAdamW)
     module = model.module if hasattr(model, "module") else model
+    # a criterion with ``needs_inputs`` (functional.PhysicsMSELoss) is called with the batch's inputs and kinds and
+    # reports its (total, mse, pde) terms: four more history lists, accumulated and reduced like the loss
+    terms = getattr(criterion, "needs_inputs", False)
+    if terms:
+        history.update({"train_mse": [], "train_pde": [], "val_mse": [], "val_pde": []})
     for epoch in range(num_epochs):
         model.train()
         acc = torch.zeros((), dtype=torch.float64, device=device)
+        tacc = torch.zeros(2, dtype=torch.float64, device=device) if terms else None
         nb = 0
-        for inputs, targets in train_loader:
-            inputs, targets = inputs.to(device), targets.to(device)
+        for batch in train_loader:
+            inputs, targets, kind = _unpack(batch, device)
             optimizer.zero_grad()
             outputs = model(inputs)
-            loss = criterion(outputs, targets)
+            loss = _criterion_call(criterion, outputs, targets, inputs, kind)
             loss.backward()
             if fused:
                 optimizer.step(max_grad_norm=grad_clip)
@@ -147,8 +178,12 @@ def train_model(model: nn.Module, train_loader, val_loader, criterion: nn.Module
                 torch.nn.utils.clip_grad_norm_(module.parameters(), grad_clip)
                 optimizer.step()
             acc += loss.detach()
+            if terms:
+                tacc += criterion.last_terms[1:]
             nb += 1
         train_loss = _global_mean(acc, nb, device)
+        if terms:
+            train_mse, train_pde = _global_means(tacc, nb, device)
 
         # under data parallelism each rank's last training forward updated its BN running
         # statistics with its own shard: validate every rank with rank 0's buffers (the state
@@ -157,13 +192,21 @@ def train_model(model: nn.Module, train_loader, val_loader, criterion: nn.Module
             model.sync_buffers()
         model.eval()
         vacc = torch.zeros((), dtype=torch.float64, device=device)
+        vtacc = torch.zeros(2, dtype=torch.float64, device=device) if terms else None
         vb = 0
         with torch.no_grad():
-            for inputs, targets in val_loader:
-                inputs, targets = inputs.to(device), targets.to(device)
-                vacc += criterion(model(inputs), targets).detach()
+            for batch in val_loader:
+                inputs, targets, kind = _unpack(batch, device)
+                vacc += _criterion_call(criterion, model(inputs), targets, inputs, kind).detach()
+                if terms:
+                    vtacc += criterion.last_terms[1:]
                 vb += 1
         val_loss = _global_mean(vacc, vb, device)
+        if terms:
+            val_mse, val_pde = _global_means(vtacc, vb, device)
+            for key, v in (("train_mse", train_mse), ("train_pde", train_pde), ("val_mse", val_mse),
+                           ("val_pde", val_pde)):
+                history[key].append(v)
 
         scheduler.step(val_loss)
         current_lr = optimizer.param_groups[0]["lr"]
@@ -298,6 +341,9 @@ def arg_parser():
                          "batches per epoch, instead of a fixed dataset")
     ap.add_argument("--online-theta", type=float, nargs=2, metavar=("LO", "HI"), default=None,
                     help="with --online: theta ~ U(LO, HI) per pixel instead of theta = 1")
+    ap.add_argument("--pde-weight", type=float, default=0.0, metavar="LAMBDA",
+                    help="add LAMBDA x the mean squared residual of the discrete equation to the MSE loss "
+                         "(functional.PhysicsMSELoss); 0 (default): plain MSE")
     return ap
 
 
@@ -312,13 +358,29 @@ def online_loaders(args, config, rank, world, device):
         raise SystemExit("--online: at least one step per epoch")
     stream = SampleStream(42, config["batch_size"], theta_range=args.online_theta, solver=args.solver, rank=rank,
                           world=world, device=device)
-    return OnlineBatchLoader(stream, args.online), stream.validation_loader(ONLINE_VAL_SAMPLES, config["batch_size"])
+    with_kind = args.pde_weight > 0
+    return (OnlineBatchLoader(stream, args.online, with_kind=with_kind),
+            stream.validation_loader(ONLINE_VAL_SAMPLES, config["batch_size"], with_kind=with_kind))
+
+
+def physics_criterion(weight, stats, save_dir=None):
+    """The criterion of --pde-weight; with ``save_dir`` its settings go to physics_loss.json beside config.json."""
+    from .functional import PhysicsMSELoss
+    criterion = PhysicsMSELoss(weight, stats)
+    if save_dir is not None:
+        with open(Path(save_dir) / "physics_loss.json", "w") as f:
+            json.dump({"weight": criterion.weight, "inv_h2": list(criterion.inv_h2),
+                       "stats": [float(v) for v in stats.detach().cpu()]}, f, indent=4)
+    return criterion
 
 
 def main(argv=None):
     args = arg_parser().parse_args(argv)
     if args.online_theta is not None and args.online is None:
         raise SystemExit("--online-theta needs --online")
+    if args.pde_weight < 0:
+        raise SystemExit("--pde-weight: a weight >= 0")
+    with_kind = args.pde_weight > 0
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world > 1 and not dist.is_initialized():
@@ -346,6 +408,7 @@ def main(argv=None):
 
     if args.online is not None:
         train_loader, val_loader = online_loaders(args, config, rank, world, device)
+        stats = train_loader.stream.stats
     else:
         if args.generate is not None:
             data = generate_on_device(*args.generate, solver=args.solver)
@@ -354,9 +417,11 @@ def main(argv=None):
         train_idx, val_idx = stratified_split(data, config["val_split"], config["stratify_by_subdomain"])
         train_ds = PDEDataset(select(data, train_idx), device=device)
         val_ds = PDEDataset(select(data, val_idx), device=device)
-        train_loader = DeviceBatchLoader(train_ds, config["batch_size"], shuffle=True, seed=42, rank=rank, world=world)
+        train_loader = DeviceBatchLoader(train_ds, config["batch_size"], shuffle=True, seed=42, rank=rank, world=world,
+                                         with_kind=with_kind)
         val_loader = DeviceBatchLoader(val_ds, config["batch_size"], shuffle=False, rank=rank, world=world,
-                                       shard_batches=True)
+                                       shard_batches=True, with_kind=with_kind)
+        stats = train_ds.stats
 
     model = UNet().to(device)
     model.apply(init_weights)
@@ -364,7 +429,7 @@ def main(argv=None):
     if world > 1:
         from .distributed import DataParallel
         net = DataParallel(model)
-    criterion = MSELoss()
+    criterion = physics_criterion(args.pde_weight, stats, save_dir if rank == 0 else None) if with_kind else MSELoss()
     optimizer = FusedAdamW(model.parameters(), lr=config["learning_rate"], weight_decay=1e-4)
     scheduler = optim.lr_scheduler.ReduceLROnPlateau(optimizer, mode="min", factor=0.5, patience=config["patience"],
                                                      min_lr=config["min_lr"])

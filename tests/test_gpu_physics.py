@@ -1,0 +1,334 @@
+"""The PDE-residual loss term and metric on the GPU (csrc/physics.hip, ABI 15) against the fp64 restatements of
+tests/test_physics_host.py, evaluated on the CPU from the kernel's own fp32 inputs (gradient: torch autograd in fp64).
+
+Tolerances are computed from the inputs.  With c = u_std * inv_h2 / f_std (the largest inv_h2 in the batch) and
+eps = 2^-23, the residual of one node is off by at most
+    delta = 16 eps c max|theta| max|y| + 4 eps max|r|
+(the stencil's four additions and one fused multiply-add on values up to 8 max|y|, then a handful of roundings of a
+value of the size of r), so
+    |pde - pde64|  <= 2 sqrt(pde64) delta + delta^2            (triangle inequality on the RMS norm)
+    |mse - mse64|  <= 4 eps mse64
+    |dy - dy64|    <= weight (2 c / M) (8 max|theta| delta + 16 eps max|q|) + (2 / N) 4 eps max|y - t|   (elementwise)
+On the reference's own solutions the term is <= 1e-11 (5.4e-13 measured for this formulation in fp32 on the CPU; the
+margin allows another operation order and fused multiply-adds).
+"""
+import glob
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from test_physics_host import INV_H2, fixture_cases, residual_metrics_ref, restatement
+
+pytestmark = pytest.mark.gpu
+
+EPS = 2.0 ** -23
+WEIGHT = 0.01
+
+
+def gpu_loss(y, t, x, kind, stats, weight, inv_h2=INV_H2, grad=True):
+    """The kernel on fp32 copies of the inputs -> (terms [3] float64 numpy of the fp32 results, dy fp32 cpu or None)."""
+    from superresolution_for_pdes_amd.functional import physics_loss_terms
+    yd = y.float().cuda().requires_grad_(grad)
+    terms = physics_loss_terms(yd, t.float().cuda(), x.float().cuda(), kind.to(torch.int32).cuda(),
+                               stats.float().cuda(), weight, inv_h2)
+    if grad:
+        terms[0].backward()
+    return terms.detach().cpu().double().numpy(), (yd.grad.cpu() if grad else None)
+
+
+def reference(y, t, x, kind, stats, weight, inv_h2=INV_H2):
+    """The restatement on the same fp32 values, with its autograd gradient and the bounds of the module docstring."""
+    y32, t32, x32, s32 = y.float(), t.float(), x.float(), stats.float()
+    yd = y32.double().requires_grad_(True)
+    out = restatement(yd, t32, x32, kind, s32, weight, inv_h2)
+    out["total"].backward()
+    sg_u, sg_f = float(s32[1]), float(s32[3])
+    c = sg_u * max(inv_h2[int(k != 0)] for k in kind.tolist()) / sg_f
+    th_max = float(out["theta"].abs().max())
+    r_max = float((out["m"] * out["r"]).detach().abs().max())
+    delta = 16 * EPS * c * th_max * float(y32.abs().max()) + 4 * EPS * r_max
+    pde, mse = float(out["pde"].detach()), float(out["mse"].detach())
+    N = y32.numel()
+    return {"pde": pde, "mse": mse, "total": float(out["total"].detach()), "dy": yd.grad, "out": out, "delta": delta,
+            "pde_bound": 2 * np.sqrt(pde) * delta + delta * delta, "mse_bound": 4 * EPS * mse,
+            "dy_bound": weight * (2 * c / out["M"]) * (8 * th_max * delta + 16 * EPS * float(out["q"].detach().abs().max()))
+            + (2.0 / N) * 4 * EPS * float((y32 - t32).abs().max())}
+
+
+def check(name, got, dy, ref):
+    e_pde, e_mse = abs(got[2] - ref["pde"]), abs(got[1] - ref["mse"])
+    e_dy = float((dy.double() - ref["dy"]).abs().max())
+    print(f"{name}: pde {got[2]:.6e} err {e_pde:.3e} (bound {ref['pde_bound']:.3e})  mse err {e_mse:.3e} "
+          f"(bound {ref['mse_bound']:.3e})  dy err {e_dy:.3e} (bound {ref['dy_bound']:.3e})")
+    assert e_pde <= ref["pde_bound"], (name, e_pde, ref["pde_bound"])
+    assert e_mse <= ref["mse_bound"], (name, e_mse, ref["mse_bound"])
+    assert e_dy <= ref["dy_bound"], (name, e_dy, ref["dy_bound"])
+
+
+@pytest.fixture(scope="module")
+def cases(golden):
+    return fixture_cases(golden)
+
+
+def batch_of(cases, kinds, theta_mode, seed=0):
+    """(y, t, x, kind, stats): fixture samples of the asked kinds, y = t + 0.05 randn.  "normalised": theta is replaced
+    by a seeded U(0.5, 2) field with its own statistics (t is then no solution; the comparison does not need one)."""
+    y, x, kind, stats = cases["combined"]
+    pool = {0: [i for i, k in enumerate(kind.tolist()) if k == 0], 1: [i for i, k in enumerate(kind.tolist()) if k]}
+    rows = [pool[k][j % len(pool[k])] for j, k in enumerate(kinds)]
+    t, x, stats = y[rows].clone(), x[rows].clone(), stats.clone()
+    g = torch.Generator().manual_seed(seed)
+    if theta_mode == "normalised":
+        th = 0.5 + 1.5 * torch.rand(t.shape, generator=g, dtype=torch.float64)[:, 0]
+        stats[4], stats[5] = th.mean(), th.std()
+        x[:, 1] = (th - stats[4]) / stats[5]
+    yp = t + 0.05 * torch.randn(t.shape, generator=g, dtype=torch.float64)
+    return yp, t, x, torch.tensor(kinds, dtype=torch.int32), stats
+
+
+def test_term_vanishes_on_the_reference_solutions(cases):
+    for name, (y, x, kind, stats) in cases.items():
+        got, _ = gpu_loss(y, y, x, kind, stats, 1.0)
+        print(f"{name}: pde on the truth, fp32 kernel: {got[2]:.3e}")
+        assert got[2] <= 1e-11, (name, got[2])
+        assert got[1] == 0.0 and got[0] == got[2]
+
+
+@pytest.mark.parametrize("theta_mode", ["constant", "normalised"])
+@pytest.mark.parametrize("kinds", [[0], [1], [1, 0, 1], [0, 0, 1, 1, 0]], ids=lambda k: "k" + "".join(map(str, k)))
+def test_perturbed_against_the_restatement(cases, kinds, theta_mode):
+    args = batch_of(cases, kinds, theta_mode)
+    got, dy = gpu_loss(*args, WEIGHT)
+    ref = reference(*args, WEIGHT)
+    assert ref["pde"] > 1e-3                    # ten orders above the truth's 1e-13: a real signal to compare
+    check(f"{kinds} {theta_mode}", got, dy, ref)
+    assert abs(got[0] - (got[1] + WEIGHT * got[2])) <= 2 * EPS * got[0]
+
+
+def _support(v, thr):
+    return {tuple(i) for i in (v.abs() > thr).nonzero().tolist()}
+
+
+def test_impulses(cases):
+    """One node off the truth.  With t = y the MSE part of the gradient vanishes, so dy = weight * scale * A(q)
+    shows where q = m r theta is non-zero."""
+    y, x, kind, stats = cases["combined"]
+    std, sub = kind.tolist().index(0), kind.tolist().index(1)
+    # kind 0, a corner node: r is non-zero on the corner and its two neighbours (the ghost ring supplies the rest)
+    y0 = y[std:std + 1].clone()
+    y0[0, 0, 0, 0] += 1.0
+    a0 = (y0, y0, x[std:std + 1], kind[std:std + 1], stats)
+    got, dy = gpu_loss(*a0, 1.0)
+    ref = reference(*a0, 1.0)
+    check("corner impulse, kind 0", got, dy, ref)
+    r_sup = _support(ref["out"]["q"][0, 0], 1e-6 * float(ref["out"]["q"].abs().max()))
+    assert r_sup == {(0, 0), (0, 1), (1, 0)}
+    thr = 1e-3 * float(ref["dy"].abs().max())
+    assert thr > 2 * ref["dy_bound"]            # the threshold is above anything rounding can produce
+    want = _support(ref["dy"][0, 0], thr)
+    assert want == {(0, 0), (0, 1), (1, 0), (1, 1), (0, 2), (2, 0)}    # A(q): q's support and its neighbours
+    assert _support(dy[0, 0], thr) == want
+    # kind 1, a boundary node: its own residual is masked, the interior neighbour's is not
+    y1 = y[sub:sub + 1].clone()
+    y1[0, 0, 0, 5] += 1.0
+    a1 = (y1, y1, x[sub:sub + 1], kind[sub:sub + 1], stats)
+    got, dy = gpu_loss(*a1, 1.0)
+    ref = reference(*a1, 1.0)
+    check("boundary impulse, kind 1", got, dy, ref)
+    o = ref["out"]
+    assert _support(o["q"][0, 0], 1e-6 * float(o["q"].abs().max())) == {(1, 5)}
+    unmasked = float((o["r"] ** 2).sum() / o["M"])
+    assert unmasked > 10 * ref["pde"] and abs(got[2] - unmasked) > 100 * ref["pde_bound"]   # the ring is masked
+    thr = 1e-3 * float(ref["dy"].abs().max())
+    assert thr > 2 * ref["dy_bound"]
+    want = _support(ref["dy"][0, 0], thr)
+    assert want == {(0, 5), (1, 4), (1, 5), (1, 6), (2, 5)}
+    assert _support(dy[0, 0], thr) == want
+    assert abs(float(dy[0, 0, 0, 5])) > thr                  # the perturbed boundary node still receives gradient
+
+
+def test_weight_zero_is_the_mse(cases):
+    from superresolution_for_pdes_amd.functional import mse_loss
+    args = batch_of(cases, [0, 0, 1, 1, 0], "constant")
+    got, dy = gpu_loss(*args, 0.0)
+    assert got[0] == got[1]
+    y32, t32 = args[0].float().cuda().requires_grad_(True), args[1].float().cuda()
+    plain = mse_loss(y32, t32)
+    plain.backward()
+    ulp = float(np.spacing(np.float32(plain.item())))
+    assert abs(got[0] - float(plain)) <= 2 * ulp
+    assert float((dy - y32.grad.cpu()).abs().max()) <= 4 * EPS * float(y32.grad.abs().max())
+
+
+def test_grad_out_no_grad_and_determinism(cases):
+    from superresolution_for_pdes_amd.functional import PhysicsMSELoss
+    yp, t, x, kind, stats = batch_of(cases, [1, 0, 1], "normalised")
+    crit = PhysicsMSELoss(WEIGHT, stats.float().cuda())
+    td, xd, kd = t.float().cuda(), x.float().cuda(), kind.cuda()
+
+    def run(scale):
+        yd = yp.float().cuda().requires_grad_(True)
+        loss = crit(yd, td, xd, kd)
+        (scale * loss).backward()
+        return loss.detach().clone(), yd.grad.clone(), crit.last_terms.clone()
+    l1, g1, terms = run(1.0)
+    l1b, g1b, _ = run(1.0)
+    l3, g3, _ = run(3.0)
+    assert torch.equal(l1, l1b) and torch.equal(g1, g1b)                  # bit-reproducible
+    assert torch.equal(l3, l1) and torch.equal(g3, 3.0 * g1)              # grad_out scales the unit gradient
+    assert terms.shape == (3,) and terms.is_cuda and not terms.requires_grad and torch.equal(terms[0], l1)
+    with torch.no_grad():
+        quiet = crit(yp.float().cuda().requires_grad_(True), td, xd, kd)
+    assert torch.equal(quiet, l1) and not quiet.requires_grad
+    from superresolution_for_pdes_amd import hipops as H
+    terms2, unit = H.physics_loss_fwd(yp.float().cuda(), td, xd, kd, crit.stats, WEIGHT, INV_H2, want_grad=False)
+    assert unit is None and torch.equal(terms2, terms)                    # no gradient buffer at all
+
+
+@pytest.mark.parametrize("n", [3, 6, 43, 44, 64])
+def test_other_grids_through_the_raw_entry(n):
+    """n = 3: one interior node; n = 6: 16 of 36; 43 / 44: the last size with two samples per workgroup and the first
+    with one; 64: the largest.  Random fields, kinds [0, 1, 1]."""
+    from superresolution_for_pdes_amd import hipops as H
+    g = torch.Generator().manual_seed(n)
+    B = 3
+    t = torch.randn(B, 1, n, n, generator=g, dtype=torch.float64)
+    y = t + 0.05 * torch.randn(B, 1, n, n, generator=g, dtype=torch.float64)
+    x = torch.randn(B, 3, n, n, generator=g, dtype=torch.float64)
+    kind = torch.tensor([0, 1, 1], dtype=torch.int32)
+    stats = torch.tensor([0.3, 0.02, -0.1, 0.5, 1.25, 0.43], dtype=torch.float64)
+    inv_h2 = (float((n - 1) ** 2), float((2 * n - 1) ** 2))
+    terms, unit = H.physics_loss_fwd(y.float().cuda(), t.float().cuda(), x.float().cuda(), kind.cuda(),
+                                     stats.float().cuda(), WEIGHT, inv_h2)
+    dy = H.physics_loss_bwd(unit, None)
+    ref = reference(y, t, x, kind, stats, WEIGHT, inv_h2)
+    assert ref["out"]["M"] == n * n + 2 * (n - 2) ** 2
+    check(f"n={n}", terms.cpu().double().numpy(), dy.cpu(), ref)
+
+
+def test_loss_is_capturable_in_a_graph(cases):
+    from superresolution_for_pdes_amd import hipops as H
+    yp, t, x, kind, stats = (v.cuda() for v in batch_of(cases, [0, 0, 1, 1, 0], "constant"))
+    yp, t, x, stats = yp.float(), t.float(), x.float(), stats.float()
+    eager, eunit = H.physics_loss_fwd(yp, t, x, kind, stats, WEIGHT, INV_H2)
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        H.physics_loss_fwd(yp, t, x, kind, stats, WEIGHT, INV_H2)
+    torch.cuda.current_stream().wait_stream(side)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        terms, unit = H.physics_loss_fwd(yp, t, x, kind, stats, WEIGHT, INV_H2)
+        dy = H.physics_loss_bwd(unit, terms[1:2])
+    terms.zero_()
+    graph.replay()
+    torch.cuda.synchronize()
+    assert torch.equal(terms, eager) and torch.equal(unit, eunit) and torch.equal(dy, eunit * eager[1])
+
+
+def test_dataset_kinds():
+    from superresolution_for_pdes_amd.models import PDEDataset
+    g = np.random.default_rng(0)
+    data = {"u_coarse": g.standard_normal((4, 20, 20)), "u_fine": g.standard_normal((4, 40, 40)),
+            "f_fine": g.standard_normal((4, 40, 40)), "theta_fine": np.ones((4, 40, 40)),
+            "is_subdomain": np.array([False, True, True, False])}
+    ds = PDEDataset(data, device="cuda")
+    idx = torch.tensor([2, 0, 1], device="cuda")
+    assert len(ds.batch(idx)) == 2
+    xb, tb, kb = ds.batch(idx, with_kind=True)
+    assert kb.dtype == torch.int32 and kb.tolist() == [1, 0, 1] and ds.kind.tolist() == [0, 1, 1, 0]
+    assert ds.stats.shape == (6,) and ds.stats[4:].tolist() == [0.0, 1.0]
+    del data["is_subdomain"]
+    with pytest.raises(ValueError, match="is_subdomain"):
+        PDEDataset(data, device="cuda").batch(idx, with_kind=True)
+
+
+# ---- the residual metric ---------------------------------------------------------------------------------------
+def bilinear_ac(a, n):
+    """align_corners=True bilinear resize of [E, m, m] to [E, n, n] (numpy, fp64)."""
+    m = a.shape[-1]
+    pos = np.linspace(0.0, m - 1.0, n)
+    lo = np.minimum(pos.astype(int), m - 2)
+    w = pos - lo
+    rows = a[:, lo] * (1 - w)[None, :, None] + a[:, lo + 1] * w[None, :, None]
+    return rows[:, :, lo] * (1 - w) + rows[:, :, lo + 1] * w
+
+
+@pytest.mark.parametrize("n", [40, 150])
+def test_residual_metrics(n):
+    from superresolution_for_pdes_amd import poisson as P
+    E = 3
+    g = np.random.default_rng(n)
+    k12 = g.uniform(0.5, 5.0, size=(E, 2))
+    theta = g.uniform(0.5, 2.0, size=(E, n, n))
+    f = P.forcing_batched(k12, n)
+    u = P.solve_direct(f, theta)
+    fn, un = f.cpu().numpy(), u.cpu().numpy()
+    inv_h2 = float((n - 1) ** 2)
+    want = residual_metrics_ref(un, fn, theta, inv_h2)
+    got = P.residual_metrics(u, f, theta).cpu().numpy()
+    print(f"n={n}: solution rms {got[:, 0]}, max {got[:, 1]}; rel err {np.abs(got / want - 1).max():.2e}")
+    assert got.shape == (E, 2) and np.abs(got / want - 1).max() <= 1e-12
+    inner = P.residual_metrics(u, f, theta, interior_only=True, inv_h2=inv_h2).cpu().numpy()
+    assert np.abs(inner / residual_metrics_ref(un, fn, theta, inv_h2, interior_only=True) - 1).max() <= 1e-12
+    # fp32 u: the same arithmetic on the widened values, and within the rounding of u of the fp64 figures
+    u32 = u.float()
+    got32 = P.residual_metrics(u32, f, theta).cpu().numpy()
+    want32 = residual_metrics_ref(u32.cpu().numpy().astype(np.float64), fn, theta, inv_h2)
+    assert np.abs(got32 / want32 - 1).max() <= 1e-12
+    delta = theta.max() * inv_h2 * 8 * np.abs(un).max() * 2.0 ** -24     # A u moves by <= 8 max|u| 2^-24 per node
+    print(f"n={n}: fp32 u rms {got32[:, 0]} (bound on the shift {delta:.3e})")
+    assert np.abs(got32 - want).max() <= delta
+    # the bilinear upsample of the half-resolution solution is no solution at all
+    m = n // 2
+    u_half = P.solve_direct(P.forcing_batched(k12, m), theta[:, ::2, ::2][:, :m, :m]).cpu().numpy()
+    up = bilinear_ac(u_half, n)
+    want_up = residual_metrics_ref(up, fn, theta, inv_h2)
+    assert (want_up[:, 0] >= 1e3 * want[:, 0]).all()                      # the inputs show the contrast (restatement)
+    got_up = P.residual_metrics(torch.from_numpy(up), f, theta).cpu().numpy()
+    assert np.abs(got_up / want_up - 1).max() <= 1e-12 and (got_up[:, 0] >= 1e3 * got[:, 0]).all()
+
+
+# ---- end to end -------------------------------------------------------------------------------------------------
+OLD_KEYS = {"train_loss", "val_loss", "best_val_loss", "best_epoch", "num_epochs"}
+CONFIG_KEYS = {"batch_size", "num_epochs", "learning_rate", "min_lr", "patience", "early_stopping_patience",
+               "val_split", "grad_clip", "device", "num_workers", "pin_memory", "stratify_by_subdomain"}
+
+
+def _check_run(hist, tmp_path):
+    assert set(hist) == OLD_KEYS | {"train_mse", "train_pde", "val_mse", "val_pde"}
+    for k in ("train_loss", "val_loss", "train_mse", "train_pde", "val_mse", "val_pde"):
+        assert len(hist[k]) == 2 and np.isfinite(hist[k]).all(), (k, hist[k])
+    for loss, mse, pde in zip(hist["val_loss"], hist["val_mse"], hist["val_pde"]):
+        assert abs(loss - (mse + 0.01 * pde)) <= 1e-6 * loss, (loss, mse, pde)
+    (run,) = glob.glob(os.path.join(str(tmp_path), "enhanced_run_*"))
+    rec = json.load(open(os.path.join(run, "physics_loss.json")))
+    assert rec["weight"] == 0.01 and rec["inv_h2"] == list(INV_H2) and len(rec["stats"]) == 6
+    assert set(json.load(open(os.path.join(run, "config.json")))) == CONFIG_KEYS
+
+
+def test_command_line_generated_set(tmp_path):
+    from superresolution_for_pdes_amd.train_enhanced import main
+    hist = main(["--generate", "16", "16", "--solver", "dst", "--epochs", "2", "--batch-size", "8", "--pde-weight",
+                 "0.01", "--results", str(tmp_path)])
+    _check_run(hist, tmp_path)
+
+
+def test_command_line_online(tmp_path):
+    from superresolution_for_pdes_amd.train_enhanced import main
+    hist = main(["--online", "2", "--solver", "dst", "--epochs", "2", "--batch-size", "8", "--pde-weight", "0.01",
+                 "--results", str(tmp_path)])
+    _check_run(hist, tmp_path)
+
+
+def test_command_line_without_the_term_is_unchanged(tmp_path):
+    from superresolution_for_pdes_amd.train_enhanced import main
+    hist = main(["--generate", "16", "16", "--solver", "dst", "--epochs", "1", "--batch-size", "8", "--results",
+                 str(tmp_path)])
+    assert set(hist) == OLD_KEYS
+    (run,) = glob.glob(os.path.join(str(tmp_path), "enhanced_run_*"))
+    assert not os.path.exists(os.path.join(run, "physics_loss.json"))
+    assert set(json.load(open(os.path.join(run, "config.json")))) == CONFIG_KEYS

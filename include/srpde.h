@@ -63,8 +63,10 @@ typedef struct ihipStream_t* hipStream_t;
  *      srpde_poisson_dst_workspace_size, srpde_poisson_dst_batched, srpde_poisson_dst_apply
  *  14  the device-side sample stream: srpde_stream_raw, srpde_stream_draw, srpde_stream_window
  *  15  the PDE residual as a loss term and a metric: srpde_physics_loss_workspace_size, srpde_physics_loss_fwd,
- *      srpde_physics_loss_bwd, srpde_pde_residual_metrics(_workspace_size) */
-#define SRPDE_ABI_VERSION 15
+ *      srpde_physics_loss_bwd, srpde_pde_residual_metrics(_workspace_size)
+ *  16  overlapping-tile cascade levels without ground truth: srpde_tiled_tiles_per_side,
+ *      srpde_tiled_level_stats(_workspace_size), srpde_tiled_assemble, srpde_tiled_blend_denorm */
+#define SRPDE_ABI_VERSION 16
 
 /* Kernel-family bits (per call; bit 0 of the same argument is the accumulate flag): the forward / dgrad
  * families compute the same outputs, statistics and stored splits bit for bit, so these only route a call to
@@ -389,6 +391,42 @@ int srpde_cascade_stitch_denorm(const float* y, const float* stats, int E, int S
 size_t srpde_field_metrics_workspace_size(int E, int n);
 int srpde_field_metrics(const void* pred, int pred_is_f32, const double* gt, int E, int n, double* out,
                         void* workspace, size_t ws_bytes, hipStream_t stream);
+
+/* ---- overlapping-tile cascade levels (ABI 16): the batched cascade above for a user's own fields.  Windows of
+ *      tile^2 coarse points overlap and are blended with a partition of unity, so tile borders are no seams and S
+ *      need not be a multiple of the tile; the statistics come from the level's inputs, not from its ground truth.
+ *      Geometry, the same on both axes: window k of m = ceil((S - tile) / stride) + 1 starts at
+ *      start_k = min(k stride, S - tile) on the coarse grid and covers [2 start_k, 2 start_k + 2 tile) on the fine
+ *      grid.  Valid: 1 <= stride <= tile <= S <= 16384 and E m^2 within an int.  Tiles are ordered example-major,
+ *      then row-major over the m x m windows.  Fields, stats and model tensors as in the section above.
+ *      Measured on one MI355X (profiles/tiled_inference_bench.json; E = 10, S = 320, tile 20, stride 10, 9610
+ *      windows): statistics 21 us, assemble 98 us, blend 35 us; the whole 40 -> 640 cascade 92.0 ms per call
+ *      against 27.4 ms with disjoint tiles, the U-Net forwards being the rest. -------- */
+/* m for a geometry; a negative code (-2) with a message for an invalid one.  Host only. */
+int srpde_tiled_tiles_per_side(int S, int tile, int stride);
+/* The stats rows and theta_const flags of srpde_cascade_level_stats, from what the level is given: {u_mean, u_std}
+ * from u_cur [E][S][S], the f and theta columns from f_next / theta_next [E][2S][2S].  Every field is reduced with
+ * the partition and order srpde_cascade_level_stats uses for a field of its own length, so the u columns are
+ * bit-equal to srpde_cascade_level_stats(u_cur, u_cur, u_cur, E, S) and the others to
+ * srpde_cascade_level_stats(f_next, f_next, theta_next, E, 2S).  Two launches, no atomics; workspace:
+ * srpde_tiled_level_stats_workspace_size(E, S) bytes, 8-byte aligned. */
+size_t srpde_tiled_level_stats_workspace_size(int E, int S);
+int srpde_tiled_level_stats(const double* u_cur, const double* f_next, const double* theta_next, int E, int S,
+                            float* stats, int* theta_const, void* workspace, size_t ws_bytes, hipStream_t stream);
+/* The U-Net input x [E m^2][3][2 tile][2 tile]: srpde_cascade_level_assemble's expressions element for element with
+ * the window origin at start_k, so tile (e, i, j) is bit-equal to srpde_cascade_level_assemble run on the fields
+ * cropped to that window.  With stride == tile and S a multiple of tile the whole output equals it. */
+int srpde_tiled_assemble(const double* u_cur, const double* f_next, const double* theta_next, const float* stats,
+                         int E, int S, int tile, int stride, float* x, hipStream_t stream);
+/* The way back: per pixel of u_next [E][2S][2S] fp64, over the windows that cover it in ascending tile order,
+ * num = sum w (double)y (fp64) and den = sum w (integer); v = num / den rounded once to fp32; u_next = v * u_std +
+ * u_mean as in srpde_cascade_stitch_denorm (an fp32 multiply, then an fp32 add, widened).  w = w1(y) w1(x) at the
+ * pixel's position inside the window: window = 0 ("linear") w1(i) = min(i + 1, 2 tile - i), window = 1 ("flat")
+ * w1(i) = 1.  Every product w y is exact in fp64, so a pixel under one window gets that window's value unchanged
+ * (stride == tile: srpde_cascade_stitch_denorm bit for bit) and windows that agree blend to the value they agree
+ * on.  Gather form, one launch, no atomics: bit-reproducible. */
+int srpde_tiled_blend_denorm(const float* y, const float* stats, int E, int S, int tile, int stride, int window,
+                             double* u_next, hipStream_t stream);
 
 /* ---- bicubic, align_corners=True, single-channel fields [planes][h][w] -> [planes][ho][wo]:
  *      F.interpolate(mode='bicubic') of the cascade's interpolation baselines

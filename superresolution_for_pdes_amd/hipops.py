@@ -11,7 +11,7 @@ import os
 
 import torch
 
-from ._lib import call, query, stream_ptr
+from ._lib import call, last_error, query, stream_ptr
 
 F32 = torch.float32
 
@@ -884,6 +884,71 @@ def field_metrics(pred, gt):
     ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=gt.device)
     call("srpde_field_metrics", pred.data_ptr(), int(pred.dtype == F32), gt.data_ptr(), E, n, out.data_ptr(),
          ws.data_ptr(), nbytes, stream_ptr())
+    return out
+
+
+# ------------------------------ overlapping-tile cascade levels ------------------------------
+TILED_WINDOWS = {"linear": 0, "flat": 1}
+
+
+def tiled_tiles_per_side(S, tile=20, stride=10):
+    """srpde_tiled_tiles_per_side: the number m of overlapping windows per axis (host only, no GPU needed)."""
+    m = int(query("srpde_tiled_tiles_per_side", int(S), int(tile), int(stride)))
+    if m <= 0:
+        raise ValueError(f"tiled_tiles_per_side: {last_error()}")
+    return m
+
+
+def _tiled_level_shapes(name, u_cur, f_next, theta_next):
+    _fields(name, torch.float64, u_cur, f_next, theta_next)
+    E, S = u_cur.shape[0], u_cur.shape[-1]
+    if u_cur.dim() != 3 or u_cur.shape != (E, S, S) or f_next.shape != (E, 2 * S, 2 * S) or \
+            theta_next.shape != f_next.shape:
+        raise ValueError(f"{name}: u_cur [E, S, S], f_next / theta_next [E, 2S, 2S]")
+    return E, S
+
+
+def tiled_level_stats(u_cur, f_next, theta_next):
+    """srpde_tiled_level_stats: the statistics of one level from its inputs alone -- u_cur [E, S, S] gives the u
+    columns, f_next / theta_next [E, 2S, 2S] (fp64) the others -> (stats [E, 6] fp32, theta_const [E] int32);
+    nothing is read back to the host."""
+    E, S = _tiled_level_shapes("tiled_level_stats", u_cur, f_next, theta_next)
+    stats = torch.empty(E, 6, dtype=F32, device=u_cur.device)
+    flags = torch.empty(E, dtype=torch.int32, device=u_cur.device)
+    nbytes = int(query("srpde_tiled_level_stats_workspace_size", E, S))
+    ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=u_cur.device)
+    call("srpde_tiled_level_stats", u_cur.data_ptr(), f_next.data_ptr(), theta_next.data_ptr(), E, S,
+         stats.data_ptr(), flags.data_ptr(), ws.data_ptr(), nbytes, stream_ptr())
+    return stats, flags
+
+
+def tiled_assemble(u_cur, f_next, theta_next, stats, tile=20, stride=10):
+    """srpde_tiled_assemble: u_cur [E, S, S], f_next / theta_next [E, 2S, 2S] (fp64), stats [E, 6] -> the U-Net
+    input [E m^2, 3, 2 tile, 2 tile] fp32 of the m x m overlapping windows, example-major then row-major."""
+    E, S = _tiled_level_shapes("tiled_assemble", u_cur, f_next, theta_next)
+    _fields("tiled_assemble", F32, stats)
+    if stats.shape != (E, 6):
+        raise ValueError("tiled_assemble: stats [E, 6]")
+    m = tiled_tiles_per_side(S, tile, stride)
+    x = torch.empty(E * m * m, 3, 2 * tile, 2 * tile, dtype=F32, device=u_cur.device)
+    call("srpde_tiled_assemble", u_cur.data_ptr(), f_next.data_ptr(), theta_next.data_ptr(), stats.data_ptr(), E, S,
+         tile, stride, x.data_ptr(), stream_ptr())
+    return x
+
+
+def tiled_blend_denorm(y, stats, E, S, tile=20, stride=10, window="linear"):
+    """srpde_tiled_blend_denorm: the U-Net output y [E m^2, 1, 2 tile, 2 tile] of the overlapping windows -> the
+    next level's fields [E, 2S, 2S] fp64: the windows' partition-of-unity blend (``window``: "linear" or "flat"),
+    rounded once to fp32, then y * u_std + u_mean (fp32)."""
+    _fields("tiled_blend_denorm", F32, y, stats)
+    if window not in TILED_WINDOWS:
+        raise ValueError(f"tiled_blend_denorm: window must be one of {sorted(TILED_WINDOWS)}")
+    m = tiled_tiles_per_side(S, tile, stride)
+    if y.numel() != E * m * m * 4 * tile * tile or stats.shape != (E, 6):
+        raise ValueError("tiled_blend_denorm: y must hold E m^2 (2 tile)^2 values, stats [E, 6]")
+    out = torch.empty(E, 2 * S, 2 * S, dtype=torch.float64, device=y.device)
+    call("srpde_tiled_blend_denorm", y.data_ptr(), stats.data_ptr(), E, S, tile, stride, TILED_WINDOWS[window],
+         out.data_ptr(), stream_ptr())
     return out
 
 

@@ -65,8 +65,10 @@ typedef struct ihipStream_t* hipStream_t;
  *  15  the PDE residual as a loss term and a metric: srpde_physics_loss_workspace_size, srpde_physics_loss_fwd,
  *      srpde_physics_loss_bwd, srpde_pde_residual_metrics(_workspace_size)
  *  16  overlapping-tile cascade levels without ground truth: srpde_tiled_tiles_per_side,
- *      srpde_tiled_level_stats(_workspace_size), srpde_tiled_assemble, srpde_tiled_blend_denorm */
-#define SRPDE_ABI_VERSION 16
+ *      srpde_tiled_level_stats(_workspace_size), srpde_tiled_assemble, srpde_tiled_blend_denorm
+ *  17  weighted-Jacobi sweeps of the discrete equation, blocked in LDS: srpde_pde_relax_sweeps_per_launch,
+ *      srpde_pde_relax_workspace_size, srpde_pde_relax */
+#define SRPDE_ABI_VERSION 17
 
 /* Kernel-family bits (per call; bit 0 of the same argument is the accumulate flag): the forward / dgrad
  * families compute the same outputs, statistics and stored splits bit for bit, so these only route a call to
@@ -593,6 +595,25 @@ size_t srpde_pde_residual_metrics_workspace_size(int E, int n);
 int srpde_pde_residual_metrics(const void* u, int u_is_f32, const double* f, const double* theta, int E, int n,
                                double inv_h2, int interior_only, double* out, void* workspace, size_t ws_bytes,
                                hipStream_t stream);
+/* Weighted-Jacobi sweeps of theta * L u = f (csrc/relax.hip): the smoother that takes the grid-scale error out of a
+ * field that is right at low frequencies (a cascade level's output).  u_in, f, theta, u_out [E][n][n] fp64.  One
+ * sweep, every operation rounded once in this order (no contraction), from the previous sweep's u throughout:
+ *     g  = f / (theta * inv_h2)
+ *     s  = (u[y-1][x] + u[y+1][x]) + (u[y][x-1] + u[y][x+1])        a neighbour outside the grid is 0
+ *     r  = (s - 4.0 * u) - g
+ *     u' = u + (0.25 * omega) * r
+ * so a host restatement in that order reproduces the result bit for bit, whatever the tiling.  interior_only != 0
+ * (n >= 3): the nodes with y or x in {0, n - 1} keep their input value and only the inner (n - 2)^2 move (a crop
+ * whose ring is not zero).  0 < omega <= 1: no error component grows.  A launch does up to
+ * srpde_pde_relax_sweeps_per_launch() sweeps on tiles held in LDS; more sweeps alternate between u_out and the
+ * workspace (one [E][n][n] fp64 field, srpde_pde_relax_workspace_size bytes, 0 when one launch suffices) so that the
+ * last launch writes u_out; sweeps = 0 copies u_in to u_out.  E <= 65535, n <= 16384, pointers 8-byte aligned; u_out
+ * must not overlap u_in, f, theta or the workspace.  Stream-ordered, no host sync, no state. */
+int srpde_pde_relax_sweeps_per_launch(void);
+size_t srpde_pde_relax_workspace_size(int E, int n, int sweeps);
+int srpde_pde_relax(const double* u_in, const double* f, const double* theta, double* u_out, int E, int n,
+                    double inv_h2, int sweeps, double omega, int interior_only, void* workspace, size_t ws_bytes,
+                    hipStream_t stream);
 
 /* ---- clip_grad_norm_ + AdamW on one flat buffer (src/train_enhanced.py:74-75,308) ---- */
 size_t srpde_grad_norm_workspace_size(void);

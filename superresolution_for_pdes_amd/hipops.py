@@ -1262,6 +1262,31 @@ def pde_residual_metrics(u, f, theta, inv_h2, interior_only=False):
     return out
 
 
+RELAX_TILE = 48   # the output tile of pde_relax_kernel (csrc/relax.hip kRelaxT): tests place their sizes around it
+
+
+def pde_relax_sweeps_per_launch():
+    """srpde_pde_relax_sweeps_per_launch: the sweeps one launch does on its LDS tiles (host only)."""
+    return int(query("srpde_pde_relax_sweeps_per_launch"))
+
+
+def pde_relax(u, f, theta, inv_h2, sweeps, omega=0.8, interior_only=False):
+    """srpde_pde_relax: ``sweeps`` weighted-Jacobi sweeps of theta * A u * inv_h2 = f on fp64 fields [E, n, n] -> a new
+    [E, n, n] fp64 tensor (the inputs are left alone); over all nodes against a zero ghost ring, or with the ring of
+    the fields held (``interior_only``)."""
+    _fields("pde_relax", torch.float64, u, f, theta)
+    if f.dim() != 3 or f.shape[1] != f.shape[2] or u.shape != f.shape or theta.shape != f.shape:
+        raise ValueError("pde_relax: u, f and theta must share one [E, n, n] shape")
+    E, n, _ = f.shape
+    sweeps = int(sweeps)
+    out = torch.empty_like(u)
+    nbytes = int(query("srpde_pde_relax_workspace_size", E, n, sweeps))
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=f.device) if nbytes else None
+    call("srpde_pde_relax", u.data_ptr(), f.data_ptr(), theta.data_ptr(), out.data_ptr(), E, n, float(inv_h2), sweeps,
+         float(omega), int(bool(interior_only)), _p(ws), nbytes, stream_ptr())
+    return out
+
+
 # ----------------------------------- optimizer -------------------------------------
 def clip_coef(flat_grad, grad_scale, max_norm, coef):
     ws_bytes = int(query("srpde_grad_norm_workspace_size"))

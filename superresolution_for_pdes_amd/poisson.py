@@ -141,6 +141,31 @@ def residual_metrics(u, f, theta, interior_only: bool = False, inv_h2: float = N
     return H.pde_residual_metrics(u, f, theta, float((n - 1) ** 2 if inv_h2 is None else inv_h2), interior_only)
 
 
+def relax(u, f, theta, sweeps: int, omega: float = 0.8, interior_only: bool = False, inv_h2: float = None,
+          device="cuda"):
+    """``sweeps`` weighted-Jacobi sweeps of theta * A u / h^2 = f (A the 5-point stencil with a zero ghost ring):
+    u <- u + (omega / 4) (A u - h^2 f / theta), each from the previous sweep's u.  It damps the error at the grid
+    scale (for omega = 0.8 every component with a wavenumber >= pi / 2 shrinks by at least 0.6 per sweep) and, for
+    0 < omega <= 1, grows none, so it polishes a field that is right at low frequencies: a cascade level's output.
+    u, f [n, n] or [E, n, n], numpy or tensors; theta is broadcast.  ``inv_h2`` defaults to (n - 1)^2, the whole-domain
+    operator that solve_batched solves and residual_metrics scores; ``interior_only`` holds the boundary nodes at
+    their values (a crop of a larger solve, whose ring is not zero).  -> a new [E, n, n] fp64 device tensor.
+    Stream-ordered, no host sync (srpde_pde_relax)."""
+    from . import hipops as H
+    if int(sweeps) < 0:
+        raise ValueError(f"relax: sweeps must be >= 0, got {sweeps}")
+    if not 0.0 < float(omega) <= 1.0:
+        raise ValueError(f"relax: omega must be in (0, 1], got {omega}")
+    u, f, theta = _dev_f64(u, device), _dev_f64(f, device), _dev_f64(theta, device)
+    if u.dim() == 2:
+        u, f = u.unsqueeze(0), f.unsqueeze(0)
+    if theta.shape != f.shape:
+        theta = theta.expand_as(f).contiguous()
+    n = u.shape[-1]
+    return H.pde_relax(u, f, theta, float((n - 1) ** 2 if inv_h2 is None else inv_h2), int(sweeps), float(omega),
+                       interior_only)
+
+
 def solve_batched(f, theta, rtol: float = DEFAULT_RTOL, maxit: int = None, device="cuda",
                   return_iters: bool = False, check: bool = True, _start_aborted: bool = False,
                   method: str = "cg"):

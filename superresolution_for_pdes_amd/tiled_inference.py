@@ -15,15 +15,21 @@ the path for someone who has a coarse solution plus f and theta on the fine grid
 With ``stride == tile``, ``stats="truth"``, S a multiple of the tile and the same ``max_batch`` the result is bit-equal
 to ml_multi_level_upscale_batched.  A level is four passes (statistics, assemble, the U-Net, blend), all stream-ordered,
 with no host synchronisation.
+
+``polish=k`` (default 0: nothing changes, no extra launch) ends a level with k weighted-Jacobi sweeps of the level's own
+equation, poisson.relax(blend, f_next, theta_next, k, polish_omega, inv_h2=(2S - 1)^2): the U-Net is the prolongation,
+this the post-smoother that takes out the grid-scale error the network leaves, also before the next level reads it.
 """
 from __future__ import annotations
 
+import numbers
 from typing import Dict, List
 
 import numpy as np
 import torch
 
 from . import hipops as H
+from . import poisson as P
 from .resolution_comparison import eval_forward
 
 
@@ -48,6 +54,13 @@ def _f64(a, device) -> torch.Tensor:
     return (t[None] if t.dim() == 2 else t).contiguous()
 
 
+def _check_polish(name, polish, polish_omega):
+    if not isinstance(polish, numbers.Integral) or polish < 0:
+        raise ValueError(f"{name}: polish must be an integer >= 0, got {polish!r}")
+    if not 0.0 < float(polish_omega) <= 1.0:
+        raise ValueError(f"{name}: polish_omega must be in (0, 1], got {polish_omega!r}")
+
+
 def _level_stats(stats, u_cur, f_next, theta_next, u_next):
     E = u_cur.shape[0]
     if isinstance(stats, torch.Tensor):
@@ -68,12 +81,15 @@ def _level_stats(stats, u_cur, f_next, theta_next, u_next):
 
 @torch.no_grad()
 def upscale_level(model, u_cur, f_next, theta_next, *, tile: int = 20, stride: int = 10, window: str = "linear",
-                  stats="input", max_batch: int = MAX_BATCH, graphs: bool = True, u_next=None) -> torch.Tensor:
+                  stats="input", max_batch: int = MAX_BATCH, graphs: bool = True, u_next=None, polish: int = 0,
+                  polish_omega: float = 0.8) -> torch.Tensor:
     """One level: u_cur [E, S, S] with f_next / theta_next [E, 2S, 2S] -> [E, 2S, 2S] fp64 on the model's device.
 
     ``stats``: "input" (no ground truth), "truth" (needs ``u_next``: cascade_level_stats of the next level's
     solution, as the reference) or an [E, 6] / [6] fp32 tensor {u_mean, u_std, f_mean, f_std, theta_mean, theta_std}.
-    The U-Net runs through eval_forward in chunks of ``max_batch`` windows."""
+    The U-Net runs through eval_forward in chunks of ``max_batch`` windows.  ``polish`` > 0: that many
+    weighted-Jacobi sweeps (``polish_omega`` in (0, 1]) of the whole-domain equation on the blended field."""
+    _check_polish("upscale_level", polish, polish_omega)
     model.eval()
     device = next(model.parameters()).device
     u_cur, f_next, theta_next = (_f64(a, device) for a in (u_cur, f_next, theta_next))
@@ -85,16 +101,22 @@ def upscale_level(model, u_cur, f_next, theta_next, *, tile: int = 20, stride: i
     x = H.tiled_assemble(u_cur, f_next, theta_next, st, tile, stride)
     outs = [eval_forward(model, x[s:s + max_batch], graphs) for s in range(0, x.shape[0], max_batch)]
     y = outs[0] if len(outs) == 1 else torch.cat(outs)
-    return H.tiled_blend_denorm(y.contiguous(), st, E, S, tile, stride, window)
+    u = H.tiled_blend_denorm(y.contiguous(), st, E, S, tile, stride, window)
+    if polish > 0:
+        u = P.relax(u, f_next, theta_next, polish, polish_omega, inv_h2=float((2 * S - 1) ** 2), device=device)
+    return u
 
 
 @torch.no_grad()
 def upscale_cascade(model, u_start, f: Dict[int, object], theta: Dict[int, object], target_resolution: int, *,
                     tile: int = 20, stride: int = 10, window: str = "linear", stats="input", max_batch: int = MAX_BATCH,
-                    graphs: bool = True, u_truth: Dict[int, object] = None) -> torch.Tensor:
+                    graphs: bool = True, u_truth: Dict[int, object] = None, polish: int = 0,
+                    polish_omega: float = 0.8) -> torch.Tensor:
     """The level loop: from u_start [E, S0, S0] by doublings to ``target_resolution``; ``f`` and ``theta`` are
     {res: [E, res, res]} for every resolution above S0 on the way.  ``u_truth`` {res: [E, res, res]} is needed for
-    stats="truth" only.  -> [E, target, target] fp64 (device tensor)."""
+    stats="truth" only.  ``polish`` / ``polish_omega``: as upscale_level, at every level, so the next level reads the
+    polished field.  -> [E, target, target] fp64 (device tensor)."""
+    _check_polish("upscale_cascade", polish, polish_omega)
     device = next(model.parameters()).device
     cur = _f64(u_start, device)
     res = cur.shape[-1]
@@ -106,6 +128,7 @@ def upscale_cascade(model, u_start, f: Dict[int, object], theta: Dict[int, objec
     while res < target_resolution:
         nxt = res * 2
         cur = upscale_level(model, cur, f[nxt], theta[nxt], tile=tile, stride=stride, window=window, stats=stats,
-                            max_batch=max_batch, graphs=graphs, u_next=None if u_truth is None else u_truth[nxt])
+                            max_batch=max_batch, graphs=graphs, u_next=None if u_truth is None else u_truth[nxt],
+                            polish=polish, polish_omega=polish_omega)
         res = nxt
     return cur

@@ -14,15 +14,31 @@
 
 namespace srpde {
 
-__device__ __forceinline__ void cubic_coeffs(float t, float c[4]) {
+// Keys' two polynomials with aten's rounding points stated, not left to the compiler's contraction: the outer
+// one, ((A x - 5A) x + 8A) x - 4A, passes through values near 4 on its way to |c| < 0.07, so a multiply-add fused
+// or not moves it by up to 2^-20 -- 24 x (4 x 2^-24 x sum |tap cx cy|) at 40 -> 80 where the inner taps are small.
+// aten's CPU kernels (AVX2 / AVX512 builds) fuse the first two steps and round the last product before its
+// subtraction; the inner polynomial fuses its first step only.  These give aten's coefficients bit for bit.
+__device__ __forceinline__ float cubic_convolution2(float x) {
+#pragma clang fp contract(off)
   const float A = -0.75f;
-  const float x1 = t + 1.0f;                  // cubic_convolution2
-  c[0] = ((A * x1 - 5.0f * A) * x1 + 8.0f * A) * x1 - 4.0f * A;
-  c[1] = ((A + 2.0f) * t - (A + 3.0f)) * t * t + 1.0f;      // cubic_convolution1
+  const float q = __builtin_fmaf(__builtin_fmaf(A, x, -5.0f * A), x, 8.0f * A);
+  return q * x - 4.0f * A;
+}
+__device__ __forceinline__ float cubic_convolution1(float x) {
+#pragma clang fp contract(off)
+  const float A = -0.75f;
+  const float q = __builtin_fmaf(A + 2.0f, x, -(A + 3.0f)) * x;
+  return q * x + 1.0f;
+}
+
+__device__ __forceinline__ void cubic_coeffs(float t, float c[4]) {
+#pragma clang fp contract(off)
+  c[0] = cubic_convolution2(t + 1.0f);
+  c[1] = cubic_convolution1(t);
   const float x2 = 1.0f - t;
-  c[2] = ((A + 2.0f) * x2 - (A + 3.0f)) * x2 * x2 + 1.0f;
-  const float x3 = x2 + 1.0f;                 // (1 - t) + 1, as aten (not 2 - t: one rounding differs)
-  c[3] = ((A * x3 - 5.0f * A) * x3 + 8.0f * A) * x3 - 4.0f * A;
+  c[2] = cubic_convolution1(x2);
+  c[3] = cubic_convolution2(x2 + 1.0f);   // (1 - t) + 1, as aten (not 2 - t: one rounding differs)
 }
 
 __global__ __launch_bounds__(256) void resize_bicubic_ac_kernel(const float* __restrict__ x, float* __restrict__ out,
@@ -49,12 +65,17 @@ __global__ __launch_bounds__(256) void resize_bicubic_ac_kernel(const float* __r
 #pragma unroll
     for (int j = 0; j < 4; ++j) xs[j] = min(max(ix - 1 + j, 0), w - 1);
     const float* src = x + pl * h * w;
+    // one rounded product, then fused multiply-adds in tap order, along x and then along y (stated, so the
+    // result does not depend on what the compiler contracts)
     float acc = 0.f;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const float* row = src + (size_t)min(max(iy - 1 + k, 0), h - 1) * w;
-      const float r = row[xs[0]] * cx[0] + row[xs[1]] * cx[1] + row[xs[2]] * cx[2] + row[xs[3]] * cx[3];
-      acc += r * cy[k];
+      float r = row[xs[0]] * cx[0];
+      r = __builtin_fmaf(row[xs[1]], cx[1], r);
+      r = __builtin_fmaf(row[xs[2]], cx[2], r);
+      r = __builtin_fmaf(row[xs[3]], cx[3], r);
+      acc = k == 0 ? r * cy[0] : __builtin_fmaf(r, cy[k], acc);
     }
     out[e] = acc;
   }

@@ -67,8 +67,11 @@ typedef struct ihipStream_t* hipStream_t;
  *  16  overlapping-tile cascade levels without ground truth: srpde_tiled_tiles_per_side,
  *      srpde_tiled_level_stats(_workspace_size), srpde_tiled_assemble, srpde_tiled_blend_denorm
  *  17  weighted-Jacobi sweeps of the discrete equation, blocked in LDS: srpde_pde_relax_sweeps_per_launch,
- *      srpde_pde_relax_workspace_size, srpde_pde_relax */
-#define SRPDE_ABI_VERSION 17
+ *      srpde_pde_relax_workspace_size, srpde_pde_relax
+ *  18  the divergence-form operator div(theta grad u) and its sine-preconditioned CG: srpde_div_apply,
+ *      srpde_div_cg_workspace_size, srpde_div_cg_done_offset, srpde_div_cg_init, srpde_div_cg_iterate,
+ *      srpde_div_cg_finish */
+#define SRPDE_ABI_VERSION 18
 
 /* Kernel-family bits (per call; bit 0 of the same argument is the accumulate flag): the forward / dgrad
  * families compute the same outputs, statistics and stored splits bit for bit, so these only route a call to
@@ -685,6 +688,46 @@ int srpde_poisson_dst_batched(const double* f, const double* theta, double* u, i
  * LDS limit. */
 int srpde_poisson_dst_apply(const double* x, double* y, int B, int n, const void* plan, size_t plan_bytes, void* ws,
                             size_t ws_bytes, hipStream_t stream);
+
+/* ---- Divergence-form operator D_theta u = div(theta grad u) (csrc/poisson_div.hip): the conservative
+ *      variable-coefficient problem, beside theta * L u = f of every entry above.  Same grid (all n^2 nodes unknown,
+ *      a zero ghost ring, h = 1 / (n - 1)).  For node a with nodal theta_a and neighbour b the face coefficient is
+ *          face_mean 0 (arithmetic):  c = 0.5 * (ta + tb)
+ *          face_mean 1 (harmonic):    c = (2.0 * (ta * tb)) / (ta + tb)
+ *          b outside the grid:        c = ta, u_b = 0
+ *      and, every operation rounded once in this order (no contraction),
+ *          y = ((cE*(uE - u) + cW*(uW - u)) + (cS*(uS - u) + cN*(uN - u))) * inv_h2
+ *      so a host restatement in that order reproduces y bit for bit, whatever the tiling.  c is bit-symmetric in
+ *      (a, b): D_theta is exactly symmetric, negative definite, and theta * L for a constant theta. ---- */
+/* y = D_theta u for B fields: u, theta, y [B][n][n] fp64, 1 <= B <= 65535, 2 <= n <= 16384, pointers 8-byte
+ * aligned, y must not alias u or theta; inv_h2 > 0 ((n - 1)^2 for the whole-domain operator).  One launch. */
+int srpde_div_apply(const double* u, const double* theta, double* y, int B, int n, int face_mean, double inv_h2,
+                    hipStream_t stream);
+/* D_theta u = f by CG preconditioned with the sine-transform solve of L (srpde_poisson_dst_*, the caller's plan for
+ * n): cond(L^-1 D_theta) <= theta_max / theta_min for every n, so the iteration count does not grow with n.  B
+ * independent problems; per iteration three streaming launches and the sine-transform solve -- no atomics, no
+ * cooperative launch, no grid barrier, no host sync; all sums in a fixed order, so a problem's result is the same
+ * bits whatever B is and wherever it stands in the batch.  inv_h2 = (n - 1)^2.
+ *   init     x = 0, r = f, z = L^-1 r; a problem with |f| = 0 is done at once (u = 0, iters = 0, resid = 0)
+ *   iterate  iterations k_begin .. k_begin + k_count - 1; iterations count from 1 and successive calls continue
+ *            where the last one stopped (k_begin = 1, then 1 + k_count, ...), with the same theta, face_mean and
+ *            rtol.  A problem is done once |r| <= rtol |f|; it is then frozen -- x, r, p, its iteration count and
+ *            residual no longer change and no 0/0 is formed -- so further iterations are harmless and a batch's
+ *            results do not depend on its slowest member
+ *   finish   u [B][n][n], iters [B] int32 (iterations performed; nullable), resid [B] fp64 (|r| / |f| at the last
+ *            one, 0 for f = 0; nullable).  May be called after any iterate; the caller decides when to stop.
+ * The int32 vector [B] at byte srpde_div_cg_done_offset of the workspace holds each problem's done flag, valid after
+ * init (poll it every few iterations, or never: a fixed iteration count needs no host read and is capturable in a
+ * graph).  Workspace: srpde_div_cg_workspace_size bytes (0 for a bad shape), 16-byte aligned, kept by the caller
+ * from init to finish; no other state. */
+size_t srpde_div_cg_workspace_size(int B, int n);
+size_t srpde_div_cg_done_offset(int B, int n);
+int srpde_div_cg_init(const double* f, int B, int n, const void* plan, size_t plan_bytes, void* ws, size_t ws_bytes,
+                      hipStream_t stream);
+int srpde_div_cg_iterate(const double* theta, int B, int n, int face_mean, double rtol, int k_begin, int k_count,
+                         const void* plan, size_t plan_bytes, void* ws, size_t ws_bytes, hipStream_t stream);
+int srpde_div_cg_finish(double* u, int* iters, double* resid, int B, int n, void* ws, size_t ws_bytes,
+                        hipStream_t stream);
 
 /* ---- Row-sharded CG for ONE n x n problem over `world` ranks (the 640^2 ground
  *      truth of solve_multi_resolution, src/resolution_comparison.py:62-73).  Rank `rank` owns the

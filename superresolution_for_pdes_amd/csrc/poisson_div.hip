@@ -1,0 +1,429 @@
+// Divergence-form Poisson operator  D_theta u = div(theta grad u) = f  and its sine-preconditioned CG, fp64, gfx950.
+//
+// Grid: all n^2 nodes unknown, a zero ghost ring one h outside, h = 1 / (n - 1).  For node a with nodal theta_a and
+// neighbour b the face coefficient is
+//     arithmetic (face_mean 0):  c = 0.5 * (ta + tb)
+//     harmonic   (face_mean 1):  c = (2.0 * (ta * tb)) / (ta + tb)
+//     b outside the grid:        c = ta, u_b = 0
+// and, every operation rounded once in this order (contraction is off for the whole file),
+//     y = ((cE*(uE - u) + cW*(uW - u)) + (cS*(uS - u) + cN*(uN - u))) * inv_h2
+// c is bit-symmetric in (a, b), so D_theta is exactly symmetric; it is negative definite, and for a constant theta it
+// is theta * L (L the 5-point Laplacian of poisson.hip / poisson_dst.hip).
+//
+// Both D_theta and L are sums over the same faces with coefficients c and 1, so theta_min (-L) <= -D_theta <=
+// theta_max (-L): with M = L, solved exactly by the sine transform, cond(M^-1 D_theta) <= theta_max / theta_min for
+// every n, and CG needs a number of iterations that does not grow with n.
+//
+//     x = 0;  r = f;  z = M^-1 r;  p = z
+//     k = 1, 2, ...:  alpha = (r.z) / (p.D p);  x += alpha p;  r -= alpha D p
+//                     the problem stops when |r| <= rtol |f|
+//                     z = M^-1 r;  beta = (r.z)_new / (r.z)_old;  p = z + beta p
+//
+// Launches of iteration k (grid: 64 x 32-node tiles x B problems, 256 threads, a thread owns one column of 8 rows):
+//   (a) div_apply_kernel<PCG>  beta from the r.z partials of the two previous (d); p = z + beta p for the tile and its
+//                              one-node halo, staged in LDS with theta (k = 1: p = z); stores p (into the other of
+//                              two p buffers: a neighbour block still reads the old one for its halo), q = D p and
+//                              the block's partial of p.q
+//   (b) div_update_kernel      alpha from the partials; x += alpha p, r -= alpha q; the block's partial of r.r
+//   (c) the sine-transform solve z = L^-1 r (poisson_dst.h: no division by a coefficient)
+//   (d) div_rz_kernel          the block's partial of r.z; block 0 of each problem sums the r.r partials and sets the
+//                              problem's iteration count, residual and done flag
+// Every block that needs a scalar re-sums the problem's partials itself, in one fixed order, so all blocks of a problem
+// get the same bits: no atomics, no grid barrier, no cooperative launch, no host sync.  A problem's arithmetic sees
+// nothing of the other problems, so its result does not depend on B or on its place in the batch.
+//
+// Freeze rule.  done[b] is written only by (d) and read only by the (a) and (b) after it.  Once set, (a) and (b)
+// return at once for that problem: x, r, p, iters and resid stay as they are, no 0/0 is formed, and further
+// iterations are harmless.  |f| = 0 sets done in init's (d): x = 0 exactly, iters = 0, resid = 0.
+#include <cmath>
+
+#include "common.h"
+#include "poisson_dst.h"
+
+#pragma clang fp contract(off)
+
+namespace srpde {
+namespace {
+
+constexpr int kDivTX = 64;                 // tile width: one column per lane
+constexpr int kDivTY = 32;                 // tile height
+constexpr int kDivThreads = 256;
+constexpr int kDivR = kDivTY / (kDivThreads / 64);   // rows per thread
+constexpr int kDivLX = kDivTX + 2, kDivLY = kDivTY + 2;
+constexpr int kDivMaxN = 16384;
+constexpr int kDivMaxB = 65535;
+static_assert(kDivR * (kDivThreads / 64) == kDivTY, "the waves' strips tile the tile");
+
+struct DivCG {
+  double *x, *r, *z, *q, *p[2];            // [B][n][n]
+  double *prr, *ppq, *prz[2];              // [B][nb] per-block partials
+  double *ff, *resid;                      // [B]
+  int *iters, *done;                       // [B]
+  void* dst_ws;
+  int n, nb;
+  size_t bytes;
+};
+
+inline size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+DivCG carve(void* ws, int B, int n) {
+  DivCG g;
+  char* c = static_cast<char*>(ws);
+  size_t at = 0;
+  auto take = [&](size_t bytes) {
+    char* p = c + at;
+    at += up16(bytes);
+    return p;
+  };
+  const size_t field = (size_t)B * n * n * sizeof(double);
+  g.n = n;
+  g.nb = ceil_div(n, kDivTX) * ceil_div(n, kDivTY);
+  const size_t part = (size_t)B * g.nb * sizeof(double);
+  g.x = reinterpret_cast<double*>(take(field));
+  g.r = reinterpret_cast<double*>(take(field));
+  g.z = reinterpret_cast<double*>(take(field));
+  g.q = reinterpret_cast<double*>(take(field));
+  g.p[0] = reinterpret_cast<double*>(take(field));
+  g.p[1] = reinterpret_cast<double*>(take(field));
+  g.dst_ws = take(srpde_poisson_dst_workspace_size(B, n));
+  g.prr = reinterpret_cast<double*>(take(part));
+  g.ppq = reinterpret_cast<double*>(take(part));
+  g.prz[0] = reinterpret_cast<double*>(take(part));
+  g.prz[1] = reinterpret_cast<double*>(take(part));
+  g.ff = reinterpret_cast<double*>(take((size_t)B * sizeof(double)));
+  g.resid = reinterpret_cast<double*>(take((size_t)B * sizeof(double)));
+  g.iters = reinterpret_cast<int*>(take((size_t)B * sizeof(int)));
+  g.done = reinterpret_cast<int*>(take((size_t)B * sizeof(int)));
+  g.bytes = at;
+  return g;
+}
+
+template <bool HARM>
+__device__ __forceinline__ double face_mean(double ta, double tb) {
+  return HARM ? (2.0 * (ta * tb)) / (ta + tb) : 0.5 * (ta + tb);
+}
+
+// the block's sum of v, the same bits in every thread; red: 4 doubles of LDS, free again on return
+__device__ __forceinline__ double block_sum(double v, double* red) {
+  v = wave_sum(v);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  const double s = (red[0] + red[1]) + (red[2] + red[3]);
+  __syncthreads();
+  return s;
+}
+
+// the sum of a problem's nb partials in the one order every block uses
+__device__ __forceinline__ double resum(const double* part, int nb, double* red) {
+  double v = 0.0;
+  for (int i = threadIdx.x; i < nb; i += kDivThreads) v += part[i];
+  return block_sum(v, red);
+}
+
+__device__ __forceinline__ int block_id() { return (int)(blockIdx.y * gridDim.x + blockIdx.x); }
+
+// y = D_theta u for one tile.  PCG: u = p = z + beta p_old is formed here (header, launch (a)).
+template <bool PCG, bool HARM>
+__global__ __launch_bounds__(kDivThreads) void div_apply_kernel(const double* __restrict__ u,
+                                                                const double* __restrict__ theta,
+                                                                double* __restrict__ y, DivCG g, double inv_h2, int n,
+                                                                int k) {
+  __shared__ double us[kDivLY * kDivLX];
+  __shared__ double ts[kDivLY * kDivLX];
+  __shared__ double red[4];
+  const int tid = threadIdx.x, b = blockIdx.z;
+  const long long base = (long long)b * n * n;
+  const int x0 = (int)blockIdx.x * kDivTX, y0 = (int)blockIdx.y * kDivTY;
+  double beta = 0.0;
+  const double* pold = nullptr;
+  double* pnew = nullptr;
+  if (PCG) {
+    if (g.done[b]) return;                 // the same for the whole block
+    pnew = g.p[k & 1];
+    if (k > 1) {
+      pold = g.p[(k - 1) & 1];
+      const double rz_new = resum(g.prz[(k - 1) & 1] + (size_t)b * g.nb, g.nb, red);
+      const double rz_old = resum(g.prz[k & 1] + (size_t)b * g.nb, g.nb, red);
+      beta = rz_old != 0.0 ? rz_new / rz_old : 0.0;
+    }
+  }
+  for (int i = tid; i < kDivLY * kDivLX; i += kDivThreads) {
+    const int ly = i / kDivLX, lx = i - ly * kDivLX;
+    const int gy = y0 - 1 + ly, gx = x0 - 1 + lx;
+    double uv = 0.0, tv = 1.0;
+    if (gy >= 0 && gy < n && gx >= 0 && gx < n) {
+      const long long at = base + (long long)gy * n + gx;
+      uv = u[at];
+      tv = theta[at];
+      if (PCG && k > 1) uv = uv + beta * pold[at];
+    }
+    us[i] = uv;
+    ts[i] = tv;
+  }
+  __syncthreads();
+
+  const int lx = (tid & 63) + 1, gx = x0 + (tid & 63);
+  const int ly0 = (tid >> 6) * kDivR + 1;
+  double acc = 0.0;
+  if (gx < n) {
+#pragma unroll
+    for (int r = 0; r < kDivR; ++r) {
+      const int ly = ly0 + r, gy = y0 + ly - 1;
+      if (gy < n) {
+        const int c = ly * kDivLX + lx;
+        const double uc = us[c], ta = ts[c];
+        const double cE = gx + 1 < n ? face_mean<HARM>(ta, ts[c + 1]) : ta;
+        const double cW = gx > 0 ? face_mean<HARM>(ta, ts[c - 1]) : ta;
+        const double cS = gy + 1 < n ? face_mean<HARM>(ta, ts[c + kDivLX]) : ta;
+        const double cN = gy > 0 ? face_mean<HARM>(ta, ts[c - kDivLX]) : ta;
+        const double yv = ((cE * (us[c + 1] - uc) + cW * (us[c - 1] - uc)) +
+                           (cS * (us[c + kDivLX] - uc) + cN * (us[c - kDivLX] - uc))) * inv_h2;
+        const long long at = base + (long long)gy * n + gx;
+        y[at] = yv;
+        if (PCG) {
+          pnew[at] = uc;
+          acc = acc + uc * yv;
+        }
+      }
+    }
+  }
+  if (PCG) {
+    const double s = block_sum(acc, red);
+    if (tid == 0) g.ppq[(size_t)b * g.nb + block_id()] = s;
+  }
+}
+
+// launch (b): x += alpha p, r -= alpha q, partial of r.r
+__global__ __launch_bounds__(kDivThreads) void div_update_kernel(DivCG g, int k) {
+  __shared__ double red[4];
+  const int tid = threadIdx.x, b = blockIdx.z, n = g.n;
+  if (g.done[b]) return;
+  const double pq = resum(g.ppq + (size_t)b * g.nb, g.nb, red);
+  const double rz = resum(g.prz[(k - 1) & 1] + (size_t)b * g.nb, g.nb, red);
+  const double alpha = pq != 0.0 ? rz / pq : 0.0;
+  const double* __restrict__ p = g.p[k & 1];
+  const long long base = (long long)b * n * n;
+  const int gx = (int)blockIdx.x * kDivTX + (tid & 63);
+  const int gy0 = (int)blockIdx.y * kDivTY + (tid >> 6) * kDivR;
+  double acc = 0.0;
+  if (gx < n) {
+#pragma unroll
+    for (int r = 0; r < kDivR; ++r) {
+      const int gy = gy0 + r;
+      if (gy < n) {
+        const long long at = base + (long long)gy * n + gx;
+        g.x[at] = g.x[at] + alpha * p[at];
+        const double rv = g.r[at] - alpha * g.q[at];
+        g.r[at] = rv;
+        acc = acc + rv * rv;
+      }
+    }
+  }
+  const double s = block_sum(acc, red);
+  if (tid == 0) g.prr[(size_t)b * g.nb + block_id()] = s;
+}
+
+// launch (d): partial of r.z; block 0 of a problem settles iteration k (k = 0: the state after init)
+__global__ __launch_bounds__(kDivThreads) void div_rz_kernel(DivCG g, int k, double rtol) {
+  __shared__ double red[4];
+  const int tid = threadIdx.x, b = blockIdx.z, n = g.n;
+  const long long base = (long long)b * n * n;
+  const int gx = (int)blockIdx.x * kDivTX + (tid & 63);
+  const int gy0 = (int)blockIdx.y * kDivTY + (tid >> 6) * kDivR;
+  double acc = 0.0;
+  if (gx < n) {
+#pragma unroll
+    for (int r = 0; r < kDivR; ++r) {
+      const int gy = gy0 + r;
+      if (gy < n) {
+        const long long at = base + (long long)gy * n + gx;
+        acc = acc + g.r[at] * g.z[at];
+      }
+    }
+  }
+  const double s = block_sum(acc, red);
+  if (tid == 0) g.prz[k & 1][(size_t)b * g.nb + block_id()] = s;
+  if (block_id() != 0) return;
+  const bool was_done = k > 0 && g.done[b] != 0;     // read by every thread before resum's barrier, written after it
+  if (was_done) return;
+  const double rr = resum(g.prr + (size_t)b * g.nb, g.nb, red);
+  if (tid == 0) {
+    if (k == 0) g.ff[b] = rr;
+    const double nf = sqrt(k == 0 ? rr : g.ff[b]), nr = sqrt(rr);
+    g.iters[b] = k;
+    g.resid[b] = nf > 0.0 ? nr / nf : 0.0;
+    g.done[b] = nr <= rtol * nf ? 1 : 0;
+  }
+}
+
+// init: x = 0, r = f, partial of f.f (into the r.r partials)
+__global__ __launch_bounds__(kDivThreads) void div_init_kernel(const double* __restrict__ f, DivCG g) {
+  __shared__ double red[4];
+  const int tid = threadIdx.x, b = blockIdx.z, n = g.n;
+  const long long base = (long long)b * n * n;
+  const int gx = (int)blockIdx.x * kDivTX + (tid & 63);
+  const int gy0 = (int)blockIdx.y * kDivTY + (tid >> 6) * kDivR;
+  double acc = 0.0;
+  if (gx < n) {
+#pragma unroll
+    for (int r = 0; r < kDivR; ++r) {
+      const int gy = gy0 + r;
+      if (gy < n) {
+        const long long at = base + (long long)gy * n + gx;
+        const double fv = f[at];
+        g.x[at] = 0.0;
+        g.r[at] = fv;
+        acc = acc + fv * fv;
+      }
+    }
+  }
+  const double s = block_sum(acc, red);
+  if (tid == 0) g.prr[(size_t)b * g.nb + block_id()] = s;
+}
+
+__global__ __launch_bounds__(256) void div_finish_kernel(DivCG g, double* __restrict__ u, int* __restrict__ iters,
+                                                         double* __restrict__ resid, long long total, int B) {
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    u[i] = g.x[i];
+    if (i < B) {
+      if (iters) iters[i] = g.iters[i];
+      if (resid) resid[i] = g.resid[i];
+    }
+  }
+}
+
+inline dim3 div_grid(int B, int n) { return dim3(ceil_div(n, kDivTX), ceil_div(n, kDivTY), B); }
+
+}  // namespace
+}  // namespace srpde
+
+using namespace srpde;
+
+#define DIV_FAIL(code, ...)          \
+  do {                               \
+    ::srpde::set_error(__VA_ARGS__); \
+    return code;                     \
+  } while (0)
+
+static int div_check(const char* name, int B, int n, int face_mean) {
+  if (B <= 0 || B > kDivMaxB || n < 2 || n > kDivMaxN)
+    DIV_FAIL(kErrShape, "%s: bad shape B=%d n=%d (1 <= B <= %d, 2 <= n <= %d)", name, B, n, kDivMaxB, kDivMaxN);
+  if (face_mean != 0 && face_mean != 1)
+    DIV_FAIL(kErrArg, "%s: face_mean=%d (0 arithmetic, 1 harmonic)", name, face_mean);
+  return 0;
+}
+
+static int div_check_ws(const char* name, int B, int n, const void* ws, size_t ws_bytes) {
+  if (!ws) DIV_FAIL(kErrArg, "%s: null workspace", name);
+  if (!aligned16(ws)) DIV_FAIL(kErrAlign, "%s: workspace not 16-byte aligned", name);
+  if (ws_bytes < srpde_div_cg_workspace_size(B, n))
+    DIV_FAIL(kErrWorkspace, "%s: workspace too small (%zu bytes, needs %zu)", name, ws_bytes,
+             srpde_div_cg_workspace_size(B, n));
+  return 0;
+}
+
+static int div_check_plan(const char* name, int n, const void* plan, size_t plan_bytes) {
+  if (!plan) DIV_FAIL(kErrArg, "%s: null plan", name);
+  if (reinterpret_cast<uintptr_t>(plan) & 7u) DIV_FAIL(kErrAlign, "%s: plan not 8-byte aligned", name);
+  if (plan_bytes != dst_plan_bytes_for(n))
+    DIV_FAIL(kErrWorkspace, "%s: a plan of %zu bytes is not a plan for n=%d (srpde_poisson_dst_plan_size: %zu)", name,
+             plan_bytes, n, dst_plan_bytes_for(n));
+  return 0;
+}
+
+extern "C" {
+
+size_t srpde_div_cg_workspace_size(int B, int n) {
+  if (B <= 0 || B > kDivMaxB || n < 2 || n > kDivMaxN) return 0;
+  return carve(nullptr, B, n).bytes;
+}
+
+size_t srpde_div_cg_done_offset(int B, int n) {
+  if (B <= 0 || B > kDivMaxB || n < 2 || n > kDivMaxN) return 0;
+  return (size_t)(reinterpret_cast<char*>(carve(nullptr, B, n).done) - static_cast<char*>(nullptr));
+}
+
+int srpde_div_apply(const double* u, const double* theta, double* y, int B, int n, int face_mean, double inv_h2,
+                    hipStream_t stream) {
+  const char* name = "srpde_div_apply";
+  SRPDE_CHECK_ARG(u && theta && y, "srpde_div_apply: null pointer");
+  if (int rc = div_check(name, B, n, face_mean)) return rc;
+  if (!(inv_h2 > 0.0) || !std::isfinite(inv_h2))
+    DIV_FAIL(kErrArg, "srpde_div_apply: inv_h2=%g must be positive and finite", inv_h2);
+  if ((reinterpret_cast<uintptr_t>(u) | reinterpret_cast<uintptr_t>(theta) | reinterpret_cast<uintptr_t>(y)) & 7u)
+    DIV_FAIL(kErrAlign, "srpde_div_apply: a pointer is not 8-byte aligned");
+  if (y == u || y == theta) DIV_FAIL(kErrArg, "srpde_div_apply: y aliases an input (a node reads its neighbours)");
+  DivCG none = {};
+  if (face_mean)
+    hipLaunchKernelGGL((div_apply_kernel<false, true>), div_grid(B, n), dim3(kDivThreads), 0, stream, u, theta, y, none,
+                       inv_h2, n, 0);
+  else
+    hipLaunchKernelGGL((div_apply_kernel<false, false>), div_grid(B, n), dim3(kDivThreads), 0, stream, u, theta, y,
+                       none, inv_h2, n, 0);
+  SRPDE_LAUNCH_CHECK(name);
+  return 0;
+}
+
+int srpde_div_cg_init(const double* f, int B, int n, const void* plan, size_t plan_bytes, void* ws, size_t ws_bytes,
+                      hipStream_t stream) {
+  const char* name = "srpde_div_cg_init";
+  SRPDE_CHECK_ARG(f, "srpde_div_cg_init: null pointer");
+  if (int rc = div_check(name, B, n, 0)) return rc;
+  if (reinterpret_cast<uintptr_t>(f) & 7u) DIV_FAIL(kErrAlign, "srpde_div_cg_init: f not 8-byte aligned");
+  if (int rc = div_check_plan(name, n, plan, plan_bytes)) return rc;
+  if (int rc = div_check_ws(name, B, n, ws, ws_bytes)) return rc;
+  DivCG g = carve(ws, B, n);
+  hipLaunchKernelGGL(div_init_kernel, div_grid(B, n), dim3(kDivThreads), 0, stream, f, g);
+  SRPDE_LAUNCH_CHECK(name);
+  if (int rc = dst_solve_launch(name, g.r, nullptr, g.z, B, n, plan, g.dst_ws, stream)) return rc;
+  // rtol 0: only |f| = 0 is done before the first iteration
+  hipLaunchKernelGGL(div_rz_kernel, div_grid(B, n), dim3(kDivThreads), 0, stream, g, 0, 0.0);
+  SRPDE_LAUNCH_CHECK(name);
+  return 0;
+}
+
+int srpde_div_cg_iterate(const double* theta, int B, int n, int face_mean, double rtol, int k_begin, int k_count,
+                         const void* plan, size_t plan_bytes, void* ws, size_t ws_bytes, hipStream_t stream) {
+  const char* name = "srpde_div_cg_iterate";
+  SRPDE_CHECK_ARG(theta, "srpde_div_cg_iterate: null pointer");
+  if (int rc = div_check(name, B, n, face_mean)) return rc;
+  if (reinterpret_cast<uintptr_t>(theta) & 7u) DIV_FAIL(kErrAlign, "srpde_div_cg_iterate: theta not 8-byte aligned");
+  if (!(rtol >= 0.0)) DIV_FAIL(kErrArg, "srpde_div_cg_iterate: rtol=%g must be >= 0", rtol);
+  if (k_begin < 1 || k_count < 0 || k_count > INT32_MAX - k_begin)
+    DIV_FAIL(kErrArg, "srpde_div_cg_iterate: k_begin=%d k_count=%d (iterations count from 1)", k_begin, k_count);
+  if (int rc = div_check_plan(name, n, plan, plan_bytes)) return rc;
+  if (int rc = div_check_ws(name, B, n, ws, ws_bytes)) return rc;
+  DivCG g = carve(ws, B, n);
+  const double inv_h2 = (double)(n - 1) * (double)(n - 1);
+  const dim3 grid = div_grid(B, n), block(kDivThreads);
+  for (int k = k_begin; k < k_begin + k_count; ++k) {
+    if (face_mean)
+      hipLaunchKernelGGL((div_apply_kernel<true, true>), grid, block, 0, stream, g.z, theta, g.q, g, inv_h2, n, k);
+    else
+      hipLaunchKernelGGL((div_apply_kernel<true, false>), grid, block, 0, stream, g.z, theta, g.q, g, inv_h2, n, k);
+    hipLaunchKernelGGL(div_update_kernel, grid, block, 0, stream, g, k);
+    SRPDE_LAUNCH_CHECK(name);
+    if (int rc = dst_solve_launch(name, g.r, nullptr, g.z, B, n, plan, g.dst_ws, stream)) return rc;
+    hipLaunchKernelGGL(div_rz_kernel, grid, block, 0, stream, g, k, rtol);
+    SRPDE_LAUNCH_CHECK(name);
+  }
+  return 0;
+}
+
+int srpde_div_cg_finish(double* u, int* iters, double* resid, int B, int n, void* ws, size_t ws_bytes,
+                        hipStream_t stream) {
+  const char* name = "srpde_div_cg_finish";
+  SRPDE_CHECK_ARG(u, "srpde_div_cg_finish: null pointer");
+  if (int rc = div_check(name, B, n, 0)) return rc;
+  if ((reinterpret_cast<uintptr_t>(u) | reinterpret_cast<uintptr_t>(resid)) & 7u)
+    DIV_FAIL(kErrAlign, "srpde_div_cg_finish: a pointer is not 8-byte aligned");
+  if (int rc = div_check_ws(name, B, n, ws, ws_bytes)) return rc;
+  DivCG g = carve(ws, B, n);
+  const long long total = (long long)B * n * n;
+  const int blocks = (int)std::min<long long>((total + 255) / 256, 8192);
+  hipLaunchKernelGGL(div_finish_kernel, dim3(blocks), dim3(256), 0, stream, g, u, iters, resid, total, B);
+  SRPDE_LAUNCH_CHECK(name);
+  return 0;
+}
+
+}  // extern "C"

@@ -1,0 +1,17 @@
+// The sine-transform solve of poisson_dst.hip as other translation units launch it (poisson_div.hip: the
+// preconditioner of the divergence-form CG).  The public entries check their arguments and call the same function.
+#pragma once
+#include "common.h"
+
+namespace srpde {
+
+// u = L^-1 (f / theta) for B problems [B][n][n] fp64, 2 <= n <= 16384; theta == nullptr: u = L^-1 f, no division and
+// no field of ones.  plan: S [n][n] then lam [n] (srpde_poisson_dst_plan); ws: srpde_poisson_dst_workspace_size(B, n)
+// bytes, unused up to srpde_poisson_dst_lds_max_n().  The caller has checked every argument.  One launch up to that
+// n, four above it (u must not alias f there); `name` labels a launch error.
+int dst_solve_launch(const char* name, const double* f, const double* theta, double* u, int B, int n, const void* plan,
+                     void* ws, hipStream_t stream);
+
+size_t dst_plan_bytes_for(int n);
+
+}  // namespace srpde

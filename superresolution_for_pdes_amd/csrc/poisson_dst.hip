@@ -27,6 +27,7 @@
 // The k order of every sum is ascending and fixed by n alone, there are no atomics, and a problem's blocks
 // never see another problem: results are bit-reproducible and independent of B.
 #include "common.h"
+#include "poisson_dst.h"
 
 namespace srpde {
 
@@ -153,8 +154,8 @@ __global__ __launch_bounds__(256) void dst_gemm_kernel(const double* __restrict_
 // column groups of at most three 16 x 16 tiles; each wave owns one (strip, group) -- the launch has exactly
 // that many waves (at most 12).  Products alternate X S (even) and S X (odd; S's fragment is read through its
 // symmetry, S[m][k] = S[k][m], so S is always read along its rows); the last one goes to global memory.
-// SOLVE: x / theta at the load, h^2 / (lam_i + lam_j) after the second product, four products; else two
-// (y = S x S).
+// SOLVE: h^2 / (lam_i + lam_j) after the second product, four products; else two (y = S x S).
+// DIV: x / theta at the load (without it SOLVE is the plain L u = x, the preconditioner of poisson_div.hip).
 constexpr int kFusedGroupTiles = 3;
 
 static int dst_fused_np(int n) { return (n + 15) & ~15; }
@@ -167,7 +168,7 @@ static size_t dst_fused_lds(int n) {
   return (size_t)2 * np * (np + 2) * sizeof(double);
 }
 
-template <bool SOLVE>
+template <bool SOLVE, bool DIV>
 __global__ __launch_bounds__(768) void dst_fused_kernel(const double* __restrict__ x, const double* __restrict__ th,
                                                         double* __restrict__ y, const double* __restrict__ S,
                                                         const double* __restrict__ lam, double h2, int n) {
@@ -179,7 +180,7 @@ __global__ __launch_bounds__(768) void dst_fused_kernel(const double* __restrict
   const int l15 = lane & 15, l4 = lane >> 4;
   const long long base = (long long)blockIdx.x * n * n;
   const double* xb = x + base;
-  const double* tb = SOLVE ? th + base : nullptr;
+  const double* tb = DIV ? th + base : nullptr;
   double* yb = y + base;
 
   for (int i = tid; i < np * np; i += blockDim.x) {
@@ -188,7 +189,7 @@ __global__ __launch_bounds__(768) void dst_fused_kernel(const double* __restrict
     if (r < n && c < n) {
       sv = S[r * n + c];
       xv = xb[r * n + c];
-      if (SOLVE) xv = xv / tb[r * n + c];
+      if (DIV) xv = xv / tb[r * n + c];
     }
     Sl[r * ld + c] = sv;
     Xl[r * ld + c] = xv;
@@ -255,6 +256,38 @@ static int gemm_launch(bool div, bool scale, const double* A, long long sA, cons
   return 0;
 }
 
+// u = L^-1 (f / theta) for B problems, theta == nullptr: no division (u = L^-1 f).  Arguments already checked.
+int dst_solve_launch(const char* name, const double* f, const double* theta, double* u, int B, int n, const void* plan,
+                     void* ws, hipStream_t stream) {
+  const double* S = static_cast<const double*>(plan);
+  const double* lam = S + (size_t)n * n;
+  const double h = 1.0 / (double)(n - 1), h2 = h * h;
+  if (n <= kDstLdsMaxN) {
+    const dim3 grid(B), block(64 * dst_fused_waves(n));
+    if (theta)
+      hipLaunchKernelGGL((dst_fused_kernel<true, true>), grid, block, dst_fused_lds(n), stream, f, theta, u, S, lam, h2,
+                         n);
+    else
+      hipLaunchKernelGGL((dst_fused_kernel<true, false>), grid, block, dst_fused_lds(n), stream, f, theta, u, S, lam,
+                         h2, n);
+    SRPDE_LAUNCH_CHECK(name);
+    return 0;
+  }
+  const long long nn = (long long)n * n;
+  double* w = static_cast<double*>(ws);
+  gemm_launch(theta != nullptr, false, f, nn, S, 0, w, nn, theta, lam, h2, n, B, stream);   // w = (f / theta) S
+  SRPDE_LAUNCH_CHECK(name);
+  gemm_launch(false, true, S, 0, w, nn, u, nn, nullptr, lam, h2, n, B, stream);   // u = (S w) o h^2 / (lam + lam)
+  SRPDE_LAUNCH_CHECK(name);
+  gemm_launch(false, false, u, nn, S, 0, w, nn, nullptr, lam, h2, n, B, stream);  // w = u S
+  SRPDE_LAUNCH_CHECK(name);
+  gemm_launch(false, false, S, 0, w, nn, u, nn, nullptr, lam, h2, n, B, stream);  // u = S w
+  SRPDE_LAUNCH_CHECK(name);
+  return 0;
+}
+
+size_t dst_plan_bytes_for(int n) { return dst_plan_bytes(n); }
+
 }  // namespace srpde
 
 using namespace srpde;
@@ -314,26 +347,7 @@ int srpde_poisson_dst_batched(const double* f, const double* theta, double* u, i
   const char* name = "srpde_poisson_dst_batched";
   SRPDE_CHECK_ARG(f && theta && u && plan, "srpde_poisson_dst_batched: null pointer");
   if (int rc = dst_check(name, B, n, 2, plan, plan_bytes, ws, ws_bytes)) return rc;
-  const double* S = static_cast<const double*>(plan);
-  const double* lam = S + (size_t)n * n;
-  const double h = 1.0 / (double)(n - 1), h2 = h * h;
-  if (n <= kDstLdsMaxN) {
-    hipLaunchKernelGGL(dst_fused_kernel<true>, dim3(B), dim3(64 * dst_fused_waves(n)), dst_fused_lds(n), stream, f,
-                       theta, u, S, lam, h2, n);
-    SRPDE_LAUNCH_CHECK(name);
-    return 0;
-  }
-  const long long nn = (long long)n * n;
-  double* w = static_cast<double*>(ws);
-  gemm_launch(true, false, f, nn, S, 0, w, nn, theta, lam, h2, n, B, stream);     // w = (f / theta) S
-  SRPDE_LAUNCH_CHECK(name);
-  gemm_launch(false, true, S, 0, w, nn, u, nn, nullptr, lam, h2, n, B, stream);   // u = (S w) o h^2 / (lam + lam)
-  SRPDE_LAUNCH_CHECK(name);
-  gemm_launch(false, false, u, nn, S, 0, w, nn, nullptr, lam, h2, n, B, stream);  // w = u S
-  SRPDE_LAUNCH_CHECK(name);
-  gemm_launch(false, false, S, 0, w, nn, u, nn, nullptr, lam, h2, n, B, stream);  // u = S w
-  SRPDE_LAUNCH_CHECK(name);
-  return 0;
+  return dst_solve_launch(name, f, theta, u, B, n, plan, ws, stream);
 }
 
 int srpde_poisson_dst_apply(const double* x, double* y, int B, int n, const void* plan, size_t plan_bytes, void* ws,
@@ -344,7 +358,7 @@ int srpde_poisson_dst_apply(const double* x, double* y, int B, int n, const void
   const double* S = static_cast<const double*>(plan);
   const double* lam = S + (size_t)n * n;
   if (n <= kDstLdsMaxN) {
-    hipLaunchKernelGGL(dst_fused_kernel<false>, dim3(B), dim3(64 * dst_fused_waves(n)), dst_fused_lds(n), stream, x,
+    hipLaunchKernelGGL((dst_fused_kernel<false, false>), dim3(B), dim3(64 * dst_fused_waves(n)), dst_fused_lds(n), stream, x,
                        nullptr, y, S, lam, 0.0, n);
     SRPDE_LAUNCH_CHECK(name);
     return 0;

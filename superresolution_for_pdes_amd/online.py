@@ -18,6 +18,12 @@ samples in the rest, so every shape is static.
 theta is 1 (``theta_range=None``, what both reference generators train on) or U(theta_range) per pixel of the
 solve grid (``(0.5, 2.0)`` is the distribution of the cascade and subdomain studies).
 
+Operator.  ``form="pointwise"`` (default) solves theta * Lap(u) = f, as the reference does.  ``form="divergence"``
+solves the conservative div(theta grad u) = f with ``face_mean`` on the cell faces instead -- every field (standard
+fine / coarse, the super-fine subdomain solves, the calibration set) by poisson.solve_div with a fixed ``pcg_iters``
+iterations, so a batch still needs no host sync.  It needs a ``theta_range``: with theta = 1 the two forms coincide.
+Draws, crop starts, statistics arithmetic and sample identity are the same for both.
+
 Global sample indices.  Local slot i of step t on rank r of ``world`` is sample
     s = (t * world + r) * B + i,
 so a world of W ranks at step t consumes exactly the samples of the single-process steps t*W .. t*W + W - 1.  The
@@ -58,6 +64,21 @@ def n_standard(n: int, sub_fraction: float) -> int:
     return n - int(round(n * sub_fraction))
 
 
+def default_pcg_iters(theta_range, tol: float = 1e-12, margin: int = 4) -> int:
+    """The fixed iteration count of form="divergence": the smallest k with 2 ((sqrt(c) - 1) / (sqrt(c) + 1))^k <= tol
+    for c = theta_hi / theta_lo (CG's bound at the condition number that theta_max / theta_min bounds for the
+    sine-preconditioned operator), plus ``margin``.  30 for (0.5, 2)."""
+    lo, hi = (float(v) for v in theta_range)
+    if not 0.0 < lo <= hi:
+        raise ValueError(f"theta_range {theta_range}: 0 < lo <= hi")
+    s = (hi / lo) ** 0.5
+    rho = (s - 1.0) / (s + 1.0)
+    k = 0
+    while 2.0 * rho ** k > tol:
+        k += 1
+    return k + margin
+
+
 def slot_kinds(n: int, sub_fraction: float) -> list:
     """The kind of each of n slots: 0 for the standard samples (first), 1 for the subdomain samples."""
     n_std = n_standard(n, sub_fraction)
@@ -91,7 +112,23 @@ class FrozenSet:
 
 class SampleStream:
     def __init__(self, seed, batch_size, sub_fraction=0.5, k_std=(0.5, 5.0), k_sub=(0.5, 12.0), theta_range=None,
-                 solver="dst", rank=0, world=1, device="cuda", n_coarse=20, n_fine=40, n_superfine=80, n_calib=2048):
+                 solver="dst", rank=0, world=1, device="cuda", n_coarse=20, n_fine=40, n_superfine=80, n_calib=2048,
+                 form="pointwise", face_mean="harmonic", pcg_iters=None):
+        # (checked first: these refusals need no device)
+        self.form = P.check_form(form)
+        P.check_face_mean(face_mean)
+        if self.form == "divergence":
+            if theta_range is None:
+                raise ValueError('SampleStream: form="divergence" needs a theta_range -- with theta = 1 it is the '
+                                 "pointwise operator")
+            self.face_mean = face_mean
+            self.pcg_iters = default_pcg_iters(theta_range) if pcg_iters is None else int(pcg_iters)
+            if self.pcg_iters < 1:
+                raise ValueError("SampleStream: pcg_iters >= 1")
+        else:
+            if face_mean != "harmonic" or pcg_iters is not None:
+                raise ValueError('SampleStream: face_mean and pcg_iters belong to form="divergence"')
+            self.face_mean = self.pcg_iters = None
         if not str(device).startswith("cuda"):
             raise RuntimeError("SampleStream generates on a ROCm device (the HIP path has no CPU fallback)")
         if batch_size < 1 or not 0.0 <= sub_fraction <= 1.0:
@@ -108,7 +145,7 @@ class SampleStream:
         self.n_coarse, self.n_fine, self.n_superfine = n_coarse, n_fine, n_superfine
         self.step = 0
         self.last_fields = None
-        if self.solver == "dst":   # the plans are built here, never inside a step (or a stream capture)
+        if self.solver == "dst" or self.form == "divergence":   # the plans are built here, never inside a step (or a stream capture)
             for n in (n_coarse, n_fine, n_superfine):
                 P.dst_plan(n, device)
         # frozen statistics, PDEDataset's arithmetic on the calibration set (the one host read of the stream)
@@ -128,7 +165,19 @@ class SampleStream:
 
     # ---- generation -------------------------------------------------------------------------------------------
     def _solve(self, f, theta):
+        if self.form == "divergence":   # fixed mode: pcg_iters iterations, no host sync, nothing read back
+            return P.solve_div(f, theta, face_mean=self.face_mean, maxit=self.pcg_iters, check_every=0, check=False,
+                               device=self.device)
         return P.solve_batched(f, theta, device=self.device, method=self.solver)
+
+    def describe(self) -> dict:
+        """What the stream generates: the settings a run records about its data source."""
+        return {"seed": self.seed, "batch_size": self.batch_size, "sub_fraction": self.sub_fraction,
+                "k_std": list(self.k_std), "k_sub": list(self.k_sub),
+                "theta_range": None if self.theta_range is None else list(self.theta_range), "solver": self.solver,
+                "form": self.form, "face_mean": self.face_mean, "pcg_iters": self.pcg_iters,
+                "rank": self.rank, "world": self.world,
+                "n_coarse": self.n_coarse, "n_fine": self.n_fine, "n_superfine": self.n_superfine}
 
     def _fields(self, first_index: int, n: int, keep: bool = False) -> dict:
         """The fp32 training fields of samples first_index .. first_index + n - 1 (standard slots first).

@@ -15,6 +15,12 @@ non-Python caller binds the same way.
 2-D sine transform (csrc/poisson_dst.hip): L = (T (x) I + I (x) T) / h^2 is diagonalised by the symmetric
 orthogonal sine matrix S, so u = S ((S (f / theta) S) o h^2 / (lam_i + lam_j)) S -- four dense fp64 MFMA
 products per problem, no iteration, any n.  Opt-in: every default stays CG.
+
+All of the above solve the POINTWISE form diag(theta) L u = f, which is L u = f / theta.  ``apply_div`` /
+``solve_div`` / ``solve_batched(..., form="divergence")`` are the DIVERGENCE form div(theta grad u) = f
+(csrc/poisson_div.hip): the conservative variable-coefficient operator with arithmetic or harmonic face means, solved
+by CG preconditioned with the sine-transform solve of L, whose iteration count is bounded by theta_max / theta_min and
+does not grow with n.  Opt-in as well: every default stays pointwise.
 """
 from __future__ import annotations
 
@@ -121,12 +127,125 @@ def dst2(x, device="cuda"):
     return y[0] if single else y
 
 
-def residual_metrics(u, f, theta, interior_only: bool = False, inv_h2: float = None, device="cuda"):
+FORMS = ("pointwise", "divergence")
+FACE_MEANS = ("arithmetic", "harmonic")
+
+
+def check_form(form: str) -> str:
+    if form not in FORMS:
+        raise ValueError(f"unknown operator form {form!r}: one of {FORMS}")
+    return form
+
+
+def check_face_mean(face_mean: str) -> int:
+    """The C entries' face_mean argument: 0 arithmetic, 1 harmonic."""
+    if face_mean not in FACE_MEANS:
+        raise ValueError(f"unknown face mean {face_mean!r}: one of {FACE_MEANS}")
+    return FACE_MEANS.index(face_mean)
+
+
+class NotConverged(RuntimeError):
+    """solve_div left problems above their tolerance (maxit reached)."""
+
+
+def _div_fields(a, theta, device):
+    a, theta = _dev_f64(a, device), _dev_f64(theta, device)
+    if a.dim() == 2:
+        a = a.unsqueeze(0)
+        if theta.dim() == 2:
+            theta = theta.unsqueeze(0)
+    if theta.shape != a.shape:
+        theta = theta.expand_as(a).contiguous()
+    B, n, n2 = a.shape
+    if n != n2:
+        raise ValueError("square grids only")
+    return a, theta, B, n
+
+
+def apply_div(u, theta, face_mean: str = "harmonic", inv_h2: float = None, device="cuda"):
+    """y = div(theta grad u) on the project's grid (zero ghost ring, h = 1 / (n - 1)): a new [B, n, n] fp64 device
+    tensor.  The face coefficient between nodes a and b is 0.5 (ta + tb) (``"arithmetic"``) or 2 ta tb / (ta + tb)
+    (``"harmonic"``), theta_a towards the ghost ring; ``inv_h2`` defaults to (n - 1)^2.  One launch, stream-ordered,
+    no host sync (srpde_div_apply; include/srpde.h states the rounding order)."""
+    mean = check_face_mean(face_mean)
+    u, theta, B, n = _div_fields(u, theta, device)
+    y = torch.empty_like(u)
+    if B:
+        call("srpde_div_apply", u.data_ptr(), theta.data_ptr(), y.data_ptr(), B, n, mean,
+             float((n - 1) ** 2 if inv_h2 is None else inv_h2), stream_ptr(u.device))
+    return y
+
+
+def solve_div(f, theta, face_mean: str = "harmonic", rtol: float = DEFAULT_RTOL, maxit: int = None,
+              check_every: int = 8, check: bool = True, return_info: bool = False, device="cuda"):
+    """u[B, n, n] (float64, on device) with div(theta grad u) = f per problem, by CG preconditioned with the
+    sine-transform solve of the constant-coefficient operator (srpde_div_cg_*).  Convergence, |r| <= rtol |f|, is
+    decided per problem on the device, and a converged problem is frozen, so a problem's u / iters / resid are the
+    same bits whatever else is in the batch and however many further iterations run.
+
+    ``check_every`` > 0 (default): iterations run in chunks of that many and the done flags are read between chunks
+    (one small host sync each), until every problem is done or ``maxit`` (default 20 n^2) is reached.
+    ``check_every=0``: exactly ``maxit`` iterations and no host sync at all -- capturable in a graph once
+    ``dst_plan(n)`` exists.
+    ``check`` (not under stream capture): problems with resid > rtol raise NotConverged (one host sync).
+    ``return_info``: (u, iters [B] int32, resid [B] fp64 = |r| / |f|, 0 for f = 0)."""
+    mean = check_face_mean(face_mean)
+    f, theta, B, n = _div_fields(f, theta, device)
+    if maxit is None:
+        maxit = 20 * n * n
+    maxit, check_every = int(maxit), int(check_every)
+    if maxit < 0 or check_every < 0:
+        raise ValueError("solve_div: maxit and check_every must be >= 0")
+    u = torch.empty_like(f)
+    iters = torch.empty(B, dtype=torch.int32, device=f.device)
+    resid = torch.empty(B, dtype=torch.float64, device=f.device)
+    if B == 0:
+        return (u, iters, resid) if return_info else u
+    capturing = torch.cuda.is_current_stream_capturing()
+    if check_every and capturing:
+        raise RuntimeError("solve_div: reading the done flags synchronises the host; capture with check_every=0")
+    plan = dst_plan(n, f.device)
+    ws_bytes = int(query("srpde_div_cg_workspace_size", B, n))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=f.device)
+    sp = stream_ptr(f.device)
+    call("srpde_div_cg_init", f.data_ptr(), B, n, plan.data_ptr(), plan.numel(), ws.data_ptr(), ws_bytes, sp)
+    done_at = int(query("srpde_div_cg_done_offset", B, n))
+    done = ws[done_at:done_at + 4 * B].view(torch.int32)
+    k = 0
+    while k < maxit:
+        count = min(check_every, maxit - k) if check_every else maxit
+        call("srpde_div_cg_iterate", theta.data_ptr(), B, n, mean, float(rtol), k + 1, count, plan.data_ptr(),
+             plan.numel(), ws.data_ptr(), ws_bytes, sp)
+        k += count
+        if check_every and k < maxit and bool(done.all()):
+            break
+    call("srpde_div_cg_finish", u.data_ptr(), iters.data_ptr(), resid.data_ptr(), B, n, ws.data_ptr(), ws_bytes, sp)
+    if check and not capturing:
+        bad = resid > float(rtol)
+        nbad = int(bad.sum())
+        if nbad:
+            raise NotConverged(f"solve_div: {nbad} of {B} problems (n={n}) above rtol={rtol:g} after {maxit} "
+                               f"iterations; worst residual {float(resid.max()):.3e}")
+    return (u, iters, resid) if return_info else u
+
+
+def residual_metrics(u, f, theta, interior_only: bool = False, inv_h2: float = None, device="cuda",
+                     form: str = "pointwise", face_mean: str = "harmonic"):
     """How well raw fields satisfy the discrete equation: [E, 2] fp64 device tensor of (RMS, max abs) of
     theta * A u / h^2 - f per example (A the 5-point stencil with a zero ghost ring).  u [E, n, n] fp32 or fp64
     (a tensor keeps its precision), f and theta fp64.  ``inv_h2`` defaults to (n - 1)^2, the whole-domain operator
     solve_batched / solve_multi_resolution solve; ``interior_only`` leaves the boundary nodes out (a crop of a
-    larger solve, whose ring is not zero).  Stream-ordered, no host sync (srpde_pde_residual_metrics)."""
+    larger solve, whose ring is not zero).  Stream-ordered, no host sync (srpde_pde_residual_metrics).
+    ``form="divergence"``: (RMS, max abs) of div(theta grad u) - f with ``face_mean`` instead, through apply_div, in
+    fp64 whatever u's precision."""
+    if check_form(form) == "divergence":
+        f, theta, E, n = _div_fields(f, theta, device)
+        u = _dev_f64(u, device).reshape(f.shape)
+        res = apply_div(u, theta, face_mean, inv_h2, device) - f
+        if interior_only:
+            res = res[:, 1:-1, 1:-1]
+        res = res.reshape(E, -1)
+        return torch.stack([res.pow(2).mean(1).sqrt(), res.abs().amax(1)], dim=1)
     from . import hipops as H
     if isinstance(u, torch.Tensor) and u.dtype == torch.float32:
         u = u.to(device).contiguous()
@@ -168,8 +287,11 @@ def relax(u, f, theta, sweeps: int, omega: float = 0.8, interior_only: bool = Fa
 
 def solve_batched(f, theta, rtol: float = DEFAULT_RTOL, maxit: int = None, device="cuda",
                   return_iters: bool = False, check: bool = True, _start_aborted: bool = False,
-                  method: str = "cg"):
+                  method: str = "cg", form: str = "pointwise", face_mean: str = "harmonic"):
     """u[B, n, n] (float64, on device) with theta*Lap(u) = f per problem.
+
+    ``form="divergence"`` solves div(theta grad u) = f instead (solve_div, which has one solver: ``method`` and
+    ``_start_aborted`` are refused; ``return_iters`` gives its iteration counts).
 
     ``method="dst"`` solves directly (solve_direct): there is nothing to iterate, so ``return_iters`` gives
     zeros and non-default ``rtol`` / ``maxit`` / ``check`` / ``_start_aborted`` are refused.
@@ -179,6 +301,14 @@ def solve_batched(f, theta, rtol: float = DEFAULT_RTOL, maxit: int = None, devic
     leaves u unconverged).  ``check`` (default) reads the iteration counts back -- one host sync,
     only on that path, not under stream capture -- and raises GridBarrierAbort instead of returning
     such a u (every data-generation caller otherwise consumed it silently)."""
+    if check_form(form) == "divergence":
+        if method != "cg" or _start_aborted:
+            raise ValueError('form="divergence" has one solver (solve_div): method and _start_aborted do not apply')
+        u, iters, _ = solve_div(f, theta, face_mean=face_mean, rtol=rtol, maxit=maxit, check=check, return_info=True,
+                                device=device)
+        return (u, iters) if return_iters else u
+    if face_mean != "harmonic":
+        raise ValueError('face_mean belongs to form="divergence"')
     if check_solver(method) == "dst":
         if rtol != DEFAULT_RTOL or maxit is not None or check is not True or _start_aborted:
             raise ValueError('method="dst" is a direct solve: rtol, maxit, check and _start_aborted do not apply')

@@ -344,7 +344,26 @@ def arg_parser():
     ap.add_argument("--pde-weight", type=float, default=0.0, metavar="LAMBDA",
                     help="add LAMBDA x the mean squared residual of the discrete equation to the MSE loss "
                          "(functional.PhysicsMSELoss); 0 (default): plain MSE")
+    ap.add_argument("--operator", choices=("pointwise", "divergence"), default="pointwise",
+                    help="the equation behind the --online samples: theta * Lap(u) = f (default) or the conservative "
+                         "div(theta grad u) = f (poisson.solve_div; needs --online and --online-theta)")
+    ap.add_argument("--face-mean", choices=("arithmetic", "harmonic"), default="harmonic",
+                    help="with --operator divergence: the mean of the two nodal theta on a cell face")
     return ap
+
+
+def check_operator_args(args):
+    """The refusals of --operator / --face-mean, before any device work."""
+    if args.operator == "divergence":
+        if args.online is None or args.online_theta is None:
+            raise SystemExit("--operator divergence needs --online and --online-theta (with theta = 1 it is the "
+                             "pointwise operator, and the fixed dataset generators are pointwise)")
+        if args.pde_weight > 0:
+            raise SystemExit("--operator divergence cannot be combined with --pde-weight > 0: the physics loss "
+                             "(csrc/physics.hip) evaluates the pointwise residual theta * Lap(u) - f; teaching it the "
+                             "divergence form is a later change")
+    elif args.face_mean != "harmonic":
+        raise SystemExit("--face-mean belongs to --operator divergence")
 
 
 ONLINE_VAL_SAMPLES = 400   # the fixed validation set of --online (the default dataset's split: 20 % of 2000)
@@ -357,7 +376,7 @@ def online_loaders(args, config, rank, world, device):
     if args.online < 1:
         raise SystemExit("--online: at least one step per epoch")
     stream = SampleStream(42, config["batch_size"], theta_range=args.online_theta, solver=args.solver, rank=rank,
-                          world=world, device=device)
+                          world=world, device=device, form=args.operator, face_mean=args.face_mean)
     with_kind = args.pde_weight > 0
     return (OnlineBatchLoader(stream, args.online, with_kind=with_kind),
             stream.validation_loader(ONLINE_VAL_SAMPLES, config["batch_size"], with_kind=with_kind))
@@ -380,6 +399,7 @@ def main(argv=None):
         raise SystemExit("--online-theta needs --online")
     if args.pde_weight < 0:
         raise SystemExit("--pde-weight: a weight >= 0")
+    check_operator_args(args)
     with_kind = args.pde_weight > 0
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -402,8 +422,11 @@ def main(argv=None):
     save_dir = Path(args.results) / f"enhanced_run_{datetime.now().strftime('%Y%m%d_%H%M%S')}"
     if rank == 0:
         save_dir.mkdir(parents=True, exist_ok=True)
+        recorded = dict(config)
+        if args.operator != "pointwise":   # (the pointwise run's config.json keeps the reference's keys)
+            recorded.update(operator=args.operator, face_mean=args.face_mean)
         with open(save_dir / "config.json", "w") as f:
-            json.dump(config, f, indent=4)
+            json.dump(recorded, f, indent=4)
     writer = ScalarWriter(str(save_dir / "tensorboard")) if rank == 0 else None
 
     if args.online is not None:

@@ -36,7 +36,14 @@ constexpr int kErrWorkspace = -4;
     }                                                     \
   } while (0)
 
-#define SRPDE_LAUNCH_CHECK(name)                                            \
+// record the message and return `code` (kErrShape, kErrAlign, ...)
+#define SRPDE_FAIL(code, ...)        \
+  do {                               \
+    ::srpde::set_error(__VA_ARGS__); \
+    return code;                     \
+  } while (0)
+
+#define SRPDE_LAUNCH_CHECK(name)                                           \
   do {                                                                      \
     hipError_t e_ = hipGetLastError();                                      \
     if (e_ != hipSuccess) {                                                 \

@@ -19,6 +19,7 @@
 // (int)floor(u * max_start): both are what numpy computes from the same u, bit for bit.  u * max_start never
 // rounds up to max_start (max_start * 2^-53 is at least half an ulp below it), so the upper bound is exclusive.
 #include "common.h"
+#include "field_reduce.h"
 
 namespace srpde {
 
@@ -156,19 +157,9 @@ __global__ __launch_bounds__(256) void stream_window_kernel(const double* __rest
   }
 }
 
-static int stream_grid(long long total) {
-  return (int)std::min<long long>(std::max<long long>((total + 255) / 256, 1), 8192);
-}
-
 }  // namespace srpde
 
 using namespace srpde;
-
-#define STREAM_FAIL(code, ...)       \
-  do {                               \
-    ::srpde::set_error(__VA_ARGS__); \
-    return code;                     \
-  } while (0)
 
 extern "C" {
 
@@ -176,13 +167,13 @@ int srpde_stream_raw(long long seed, long long sample0, long long n_samples, lon
                      long long n_elements, unsigned* out, hipStream_t stream) {
   SRPDE_CHECK_ARG(out, "srpde_stream_raw: null pointer");
   if (n_samples <= 0 || n_elements <= 0 || n_samples > (1LL << 31) / n_elements)
-    STREAM_FAIL(kErrShape, "srpde_stream_raw: bad counts n_samples=%lld n_elements=%lld (product up to 2^31)", n_samples,
-                n_elements);
+    SRPDE_FAIL(kErrShape, "srpde_stream_raw: bad counts n_samples=%lld n_elements=%lld (product up to 2^31)", n_samples,
+               n_elements);
   if (field < 0 || field > 0xffffffffLL || element0 < 0 || element0 + n_elements > (1LL << 32))
-    STREAM_FAIL(kErrArg, "srpde_stream_raw: field %lld / elements %lld + %lld outside a 32-bit counter word", field,
-                element0, n_elements);
-  hipLaunchKernelGGL(stream_raw_kernel, dim3(stream_grid(n_samples * n_elements)), dim3(256), 0, stream, seed, sample0,
-                     n_samples, (uint32_t)field, (uint32_t)element0, n_elements, out);
+    SRPDE_FAIL(kErrArg, "srpde_stream_raw: field %lld / elements %lld + %lld outside a 32-bit counter word", field,
+               element0, n_elements);
+  hipLaunchKernelGGL(stream_raw_kernel, dim3(elementwise_grid(n_samples * n_elements)), dim3(256), 0, stream, seed,
+                     sample0, n_samples, (uint32_t)field, (uint32_t)element0, n_elements, out);
   SRPDE_LAUNCH_CHECK("srpde_stream_raw");
   return 0;
 }
@@ -192,17 +183,17 @@ int srpde_stream_draw(long long seed, long long sample0, int B, double k_lo, dou
                       double* theta_half, hipStream_t stream) {
   SRPDE_CHECK_ARG(k12, "srpde_stream_draw: null k12");
   SRPDE_CHECK_ARG(theta || !theta_half, "srpde_stream_draw: theta_half without theta");
-  if (B <= 0) STREAM_FAIL(kErrShape, "srpde_stream_draw: bad B=%d", B);
+  if (B <= 0) SRPDE_FAIL(kErrShape, "srpde_stream_draw: bad B=%d", B);
   if (theta_mode != 0 && theta_mode != 1)
-    STREAM_FAIL(kErrArg, "srpde_stream_draw: theta_mode %d (0: ones, 1: uniform)", theta_mode);
-  if (theta && (n < 1 || n > 16384)) STREAM_FAIL(kErrShape, "srpde_stream_draw: bad n=%d", n);
-  if (starts && max_start < 1) STREAM_FAIL(kErrArg, "srpde_stream_draw: max_start %d < 1", max_start);
+    SRPDE_FAIL(kErrArg, "srpde_stream_draw: theta_mode %d (0: ones, 1: uniform)", theta_mode);
+  if (theta && (n < 1 || n > 16384)) SRPDE_FAIL(kErrShape, "srpde_stream_draw: bad n=%d", n);
+  if (starts && max_start < 1) SRPDE_FAIL(kErrArg, "srpde_stream_draw: max_start %d < 1", max_start);
   if (!(k_lo <= k_hi) || (theta && theta_mode == 1 && !(theta_lo <= theta_hi)))
-    STREAM_FAIL(kErrArg, "srpde_stream_draw: empty range k [%g, %g] theta [%g, %g]", k_lo, k_hi, theta_lo, theta_hi);
+    SRPDE_FAIL(kErrArg, "srpde_stream_draw: empty range k [%g, %g] theta [%g, %g]", k_lo, k_hi, theta_lo, theta_hi);
   const long long n2 = theta ? (long long)n * n : 0;
-  hipLaunchKernelGGL(stream_draw_kernel, dim3(stream_grid((long long)B * ((n2 + 1) / 2 + 1))), dim3(256), 0, stream,
-                     seed, sample0, B, k_lo, k_hi, theta_mode, theta_lo, theta_hi, n, max_start, k12, starts, theta,
-                     theta_half);
+  hipLaunchKernelGGL(stream_draw_kernel, dim3(elementwise_grid((long long)B * ((n2 + 1) / 2 + 1))), dim3(256), 0,
+                     stream, seed, sample0, B, k_lo, k_hi, theta_mode, theta_lo, theta_hi, n, max_start, k12, starts,
+                     theta, theta_half);
   SRPDE_LAUNCH_CHECK("srpde_stream_draw");
   return 0;
 }
@@ -212,13 +203,13 @@ int srpde_stream_window(const double* u, const double* f, const double* theta, c
                         float* theta_fine, float* u_coarse, hipStream_t stream) {
   SRPDE_CHECK_ARG(u && f && theta && u_fine && f_fine && theta_fine && u_coarse, "srpde_stream_window: null pointer");
   if (B <= 0 || nf < 1 || ns < nf || ns > 16384)
-    STREAM_FAIL(kErrShape, "srpde_stream_window: bad shape B=%d ns=%d nf=%d", B, ns, nf);
+    SRPDE_FAIL(kErrShape, "srpde_stream_window: bad shape B=%d ns=%d nf=%d", B, ns, nf);
   if (!starts && ns != nf)
-    STREAM_FAIL(kErrShape, "srpde_stream_window: without starts the window is the field (ns=%d, nf=%d)", ns, nf);
+    SRPDE_FAIL(kErrShape, "srpde_stream_window: without starts the window is the field (ns=%d, nf=%d)", ns, nf);
   if (starts && u_coarse_in)
-    STREAM_FAIL(kErrArg, "srpde_stream_window: u_coarse_in belongs to the pass-through variant (starts == NULL)");
-  hipLaunchKernelGGL(stream_window_kernel, dim3(stream_grid((long long)B * nf * nf)), dim3(256), 0, stream, u, f, theta,
-                     starts, u_coarse_in, B, ns, nf, u_fine, f_fine, theta_fine, u_coarse);
+    SRPDE_FAIL(kErrArg, "srpde_stream_window: u_coarse_in belongs to the pass-through variant (starts == NULL)");
+  hipLaunchKernelGGL(stream_window_kernel, dim3(elementwise_grid((long long)B * nf * nf)), dim3(256), 0, stream, u, f,
+                     theta, starts, u_coarse_in, B, ns, nf, u_fine, f_fine, theta_fine, u_coarse);
   SRPDE_LAUNCH_CHECK("srpde_stream_window");
   return 0;
 }

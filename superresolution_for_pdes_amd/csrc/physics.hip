@@ -28,6 +28,7 @@
 // node -> thread -> workgroup assignment depends on the shape alone and there are no atomics: results are
 // bit-reproducible.
 #include "common.h"
+#include "field_reduce.h"
 
 namespace srpde {
 namespace {
@@ -44,21 +45,6 @@ inline int phys_spw(int n) {
   return (int)std::max<size_t>(1, std::min<size_t>(kPhysMaxSpw, kPhysLdsBudget / per));
 }
 inline int phys_blocks(int B, int n) { return ceil_div(B, phys_spw(n)); }
-
-// sum over the 256 threads, valid on thread 0; sh: 4 doubles
-__device__ __forceinline__ double phys_block_sum(double v, double* sh) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (sh[0] + sh[1]) + (sh[2] + sh[3]);
-}
-
-__device__ __forceinline__ double phys_wave_max(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-  return v;
-}
 
 // (a + b) + (c + d) - 4 e on a halo tile around p
 __device__ __forceinline__ float stencil5(const float* p, int pitch) {
@@ -97,7 +83,7 @@ __global__ __launch_bounds__(kPhysThreads) void physics_loss_kernel(
   if (dy != nullptr) {
     long long cnt = 0;
     for (int b = tid; b < B; b += kPhysThreads) cnt += kind[b] ? (long long)(n - 2) * (n - 2) : (long long)nn;
-    const double tot = phys_block_sum((double)cnt, sh);   // exact: integers far below 2^53
+    const double tot = block_sum((double)cnt, sh);   // exact: integers far below 2^53
     if (tid == 0) shM = (long long)tot;
   }
   __syncthreads();
@@ -148,9 +134,9 @@ __global__ __launch_bounds__(kPhysThreads) void physics_loss_kernel(
     }
   }
 
-  sse = phys_block_sum(sse, sh);
-  spr = phys_block_sum(spr, sh);
-  sm = phys_block_sum(sm, sh);
+  sse = block_sum(sse, sh);
+  spr = block_sum(spr, sh);
+  sm = block_sum(sm, sh);
   if (tid == 0) {
     double* o = part + (long long)blockIdx.x * 3;
     o[0] = sse;
@@ -170,9 +156,9 @@ __global__ __launch_bounds__(kPhysThreads) void physics_loss_final_kernel(const 
     b += part[3 * (long long)k + 1];
     c += part[3 * (long long)k + 2];
   }
-  a = phys_block_sum(a, sh);
-  b = phys_block_sum(b, sh);
-  c = phys_block_sum(c, sh);
+  a = block_sum(a, sh);
+  b = block_sum(b, sh);
+  c = block_sum(c, sh);
   if (threadIdx.x == 0) {
     const double mse = a / (double)N, pde = b / c;
     loss[0] = (float)(mse + (double)weight * pde);
@@ -189,19 +175,11 @@ __global__ void physics_scale_kernel(const float* __restrict__ unit, long long n
 }
 
 // ---- the residual metric ---------------------------------------------------------------------------------
-constexpr int kResThreads = 256;
-constexpr int kResChunk = 2048;
-constexpr int kResMaxBlocks = 256;
-
-inline int res_blocks(long long nn) {
-  return (int)std::min<long long>(std::max<long long>((nn + kResChunk - 1) / kResChunk, 1), kResMaxBlocks);
-}
-
-// grid (res_blocks, E): part[(e * nb + b) * 2] = {sum r^2, max |r|} over the counted nodes.  Every operation is
+// grid (red_blocks, E): part[(e * nb + b) * 2] = {sum r^2, max |r|} over the counted nodes.  Every operation is
 // rounded on its own (no contraction), in the order of the header's formula, so a host restatement in that order
 // reproduces r bit for bit.
 template <typename TU>
-__global__ __launch_bounds__(kResThreads) void pde_residual_partial_kernel(const TU* __restrict__ u,
+__global__ __launch_bounds__(kRedThreads) void pde_residual_partial_kernel(const TU* __restrict__ u,
                                                                            const double* __restrict__ f,
                                                                            const double* __restrict__ theta, int n,
                                                                            double inv_h2, int interior_only,
@@ -214,7 +192,7 @@ __global__ __launch_bounds__(kResThreads) void pde_residual_partial_kernel(const
   const double* fe = f + e * nn;
   const double* te = theta + e * nn;
   double sq = 0.0, mx = 0.0;
-  for (long long k = (long long)blockIdx.x * kResThreads + threadIdx.x; k < nn; k += (long long)gridDim.x * kResThreads) {
+  for (long long k = (long long)blockIdx.x * kRedThreads + threadIdx.x; k < nn; k += (long long)gridDim.x * kRedThreads) {
     const int i = (int)(k / n), j = (int)(k - (long long)i * n);
     const bool edge = i == 0 || i == n - 1 || j == 0 || j == n - 1;
     if (interior_only && edge) continue;
@@ -225,15 +203,12 @@ __global__ __launch_bounds__(kResThreads) void pde_residual_partial_kernel(const
     sq += r * r;
     mx = fmax(mx, fabs(r));
   }
-  sq = phys_block_sum(sq, sh);
-  mx = phys_wave_max(mx);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = mx;
-  __syncthreads();
+  sq = block_sum(sq, sh);
+  block_max_store(mx, sh);
   if (threadIdx.x == 0) {
     double* o = part + ((long long)e * gridDim.x + blockIdx.x) * 2;
     o[0] = sq;
-    o[1] = fmax(fmax(sh[0], sh[1]), fmax(sh[2], sh[3]));
+    o[1] = block_max_load(sh);
   }
 }
 
@@ -247,7 +222,7 @@ __global__ __launch_bounds__(64) void pde_residual_final_kernel(const double* __
     mx = fmax(mx, p[2 * j + 1]);
   }
   sq = wave_sum(sq);
-  mx = phys_wave_max(mx);
+  mx = wave_max(mx);
   if (lane == 0) {
     out[e * 2] = sqrt(sq / count);
     out[e * 2 + 1] = mx;
@@ -258,12 +233,6 @@ __global__ __launch_bounds__(64) void pde_residual_final_kernel(const double* __
 }  // namespace srpde
 
 using namespace srpde;
-
-#define PHYS_FAIL(code, ...)         \
-  do {                               \
-    ::srpde::set_error(__VA_ARGS__); \
-    return code;                     \
-  } while (0)
 
 extern "C" {
 
@@ -277,12 +246,12 @@ int srpde_physics_loss_fwd(const float* y, const float* t, const float* x, const
                            void* workspace, size_t ws_bytes, hipStream_t stream) {
   SRPDE_CHECK_ARG(y && t && x && kind && stats && loss && workspace, "srpde_physics_loss_fwd: null pointer");
   if (B <= 0 || n < kPhysMinN || n > kPhysMaxN)
-    PHYS_FAIL(kErrShape, "srpde_physics_loss_fwd: bad shape B=%d n=%d (B >= 1, %d <= n <= %d)", B, n, kPhysMinN,
-              kPhysMaxN);
+    SRPDE_FAIL(kErrShape, "srpde_physics_loss_fwd: bad shape B=%d n=%d (B >= 1, %d <= n <= %d)", B, n, kPhysMinN,
+               kPhysMaxN);
   if (reinterpret_cast<uintptr_t>(workspace) & 7u)
-    PHYS_FAIL(kErrAlign, "srpde_physics_loss_fwd: workspace not 8-byte aligned");
+    SRPDE_FAIL(kErrAlign, "srpde_physics_loss_fwd: workspace not 8-byte aligned");
   if (ws_bytes < srpde_physics_loss_workspace_size(B, n))
-    PHYS_FAIL(kErrWorkspace, "srpde_physics_loss_fwd: workspace too small");
+    SRPDE_FAIL(kErrWorkspace, "srpde_physics_loss_fwd: workspace too small");
   const int spw = phys_spw(n), nb = phys_blocks(B, n);
   const size_t lds = (size_t)spw * phys_lds_floats(n) * sizeof(float);
   double* part = static_cast<double*>(workspace);
@@ -297,16 +266,16 @@ int srpde_physics_loss_fwd(const float* y, const float* t, const float* x, const
 
 int srpde_physics_loss_bwd(const float* dy_unit, long long count, const float* gout, float* dy, hipStream_t stream) {
   SRPDE_CHECK_ARG(dy_unit && dy, "srpde_physics_loss_bwd: null pointer");
-  if (count <= 0) PHYS_FAIL(kErrShape, "srpde_physics_loss_bwd: bad count %lld", count);
-  const int nb = (int)std::min<long long>((count + 255) / 256, 8192);
-  hipLaunchKernelGGL(physics_scale_kernel, dim3(nb), dim3(256), 0, stream, dy_unit, count, gout, dy);
+  if (count <= 0) SRPDE_FAIL(kErrShape, "srpde_physics_loss_bwd: bad count %lld", count);
+  hipLaunchKernelGGL(physics_scale_kernel, dim3(elementwise_grid(count)), dim3(256), 0, stream, dy_unit, count, gout,
+                     dy);
   SRPDE_LAUNCH_CHECK("srpde_physics_loss_bwd");
   return 0;
 }
 
 size_t srpde_pde_residual_metrics_workspace_size(int E, int n) {
   if (E <= 0 || n <= 0) return 0;
-  return (size_t)E * res_blocks((long long)n * n) * 2 * sizeof(double);
+  return (size_t)E * red_blocks((long long)n * n) * 2 * sizeof(double);
 }
 
 int srpde_pde_residual_metrics(const void* u, int u_is_f32, const double* f, const double* theta, int E, int n,
@@ -314,20 +283,20 @@ int srpde_pde_residual_metrics(const void* u, int u_is_f32, const double* f, con
                                hipStream_t stream) {
   SRPDE_CHECK_ARG(u && f && theta && out && workspace, "srpde_pde_residual_metrics: null pointer");
   if (E <= 0 || n <= 0 || E > 65535 || n > 16384 || (interior_only && n < 3))
-    PHYS_FAIL(kErrShape, "srpde_pde_residual_metrics: bad shape E=%d n=%d (interior_only needs n >= 3)", E, n);
+    SRPDE_FAIL(kErrShape, "srpde_pde_residual_metrics: bad shape E=%d n=%d (interior_only needs n >= 3)", E, n);
   if (reinterpret_cast<uintptr_t>(workspace) & 7u)
-    PHYS_FAIL(kErrAlign, "srpde_pde_residual_metrics: workspace not 8-byte aligned");
+    SRPDE_FAIL(kErrAlign, "srpde_pde_residual_metrics: workspace not 8-byte aligned");
   if (ws_bytes < srpde_pde_residual_metrics_workspace_size(E, n))
-    PHYS_FAIL(kErrWorkspace, "srpde_pde_residual_metrics: workspace too small");
+    SRPDE_FAIL(kErrWorkspace, "srpde_pde_residual_metrics: workspace too small");
   const long long nn = (long long)n * n;
-  const int nb = res_blocks(nn);
+  const int nb = red_blocks(nn);
   const double count = interior_only ? (double)(n - 2) * (n - 2) : (double)nn;
   double* part = static_cast<double*>(workspace);
   if (u_is_f32)
-    hipLaunchKernelGGL(pde_residual_partial_kernel<float>, dim3(nb, E), dim3(kResThreads), 0, stream,
+    hipLaunchKernelGGL(pde_residual_partial_kernel<float>, dim3(nb, E), dim3(kRedThreads), 0, stream,
                        static_cast<const float*>(u), f, theta, n, inv_h2, interior_only, part);
   else
-    hipLaunchKernelGGL(pde_residual_partial_kernel<double>, dim3(nb, E), dim3(kResThreads), 0, stream,
+    hipLaunchKernelGGL(pde_residual_partial_kernel<double>, dim3(nb, E), dim3(kRedThreads), 0, stream,
                        static_cast<const double*>(u), f, theta, n, inv_h2, interior_only, part);
   SRPDE_LAUNCH_CHECK("srpde_pde_residual_metrics");
   hipLaunchKernelGGL(pde_residual_final_kernel, dim3(E), dim3(64), 0, stream, part, nb, count, out);

@@ -21,6 +21,7 @@
 #include <tuple>
 #include <atomic>
 #include "common.h"
+#include "field_reduce.h"
 
 #include <vector>
 
@@ -800,8 +801,7 @@ int srpde_poisson_lds_max_n(void) { return 128; }
 int srpde_forcing_batched(const double* k12, int B, int n, double* out, hipStream_t stream) {
   SRPDE_CHECK_ARG(k12 && out && B > 0 && n >= 2, "srpde_forcing_batched: bad args");
   const long long total = (long long)B * n * n;
-  const int blocks = (int)std::min<long long>((total + 255) / 256, 8192);
-  hipLaunchKernelGGL(forcing_kernel, dim3(blocks), dim3(256), 0, stream, k12, B, n, out);
+  hipLaunchKernelGGL(forcing_kernel, dim3(elementwise_grid(total)), dim3(256), 0, stream, k12, B, n, out);
   SRPDE_LAUNCH_CHECK("srpde_forcing_batched");
   return 0;
 }

@@ -38,6 +38,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "field_reduce.h"
 #include "poisson_dst.h"
 
 #pragma clang fp contract(off)
@@ -53,6 +54,7 @@ constexpr int kDivLX = kDivTX + 2, kDivLY = kDivTY + 2;
 constexpr int kDivMaxN = 16384;
 constexpr int kDivMaxB = 65535;
 static_assert(kDivR * (kDivThreads / 64) == kDivTY, "the waves' strips tile the tile");
+static_assert(kDivThreads == kRedThreads, "block_sum and resum (field_reduce.h) reduce over 256 threads");
 
 struct DivCG {
   double *x, *r, *z, *q, *p[2];            // [B][n][n]
@@ -103,22 +105,8 @@ __device__ __forceinline__ double face_mean(double ta, double tb) {
   return HARM ? (2.0 * (ta * tb)) / (ta + tb) : 0.5 * (ta + tb);
 }
 
-// the block's sum of v, the same bits in every thread; red: 4 doubles of LDS, free again on return
-__device__ __forceinline__ double block_sum(double v, double* red) {
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const double s = (red[0] + red[1]) + (red[2] + red[3]);
-  __syncthreads();
-  return s;
-}
-
-// the sum of a problem's nb partials in the one order every block uses
-__device__ __forceinline__ double resum(const double* part, int nb, double* red) {
-  double v = 0.0;
-  for (int i = threadIdx.x; i < nb; i += kDivThreads) v += part[i];
-  return block_sum(v, red);
-}
+// block_sum and resum (field_reduce.h) give the same bits in every thread.  red, their 4 doubles of LDS, is used for
+// nothing else in these kernels, and each call's first barrier comes before its write, so back-to-back calls are safe.
 
 __device__ __forceinline__ int block_id() { return (int)(blockIdx.y * gridDim.x + blockIdx.x); }
 
@@ -244,7 +232,7 @@ __global__ __launch_bounds__(kDivThreads) void div_rz_kernel(DivCG g, int k, dou
   const double s = block_sum(acc, red);
   if (tid == 0) g.prz[k & 1][(size_t)b * g.nb + block_id()] = s;
   if (block_id() != 0) return;
-  const bool was_done = k > 0 && g.done[b] != 0;     // read by every thread before resum's barrier, written after it
+  const bool was_done = k > 0 && g.done[b] != 0;     // read by every thread before resum's barriers, written after them
   if (was_done) return;
   const double rr = resum(g.prr + (size_t)b * g.nb, g.nb, red);
   if (tid == 0) {
@@ -299,35 +287,29 @@ inline dim3 div_grid(int B, int n) { return dim3(ceil_div(n, kDivTX), ceil_div(n
 
 using namespace srpde;
 
-#define DIV_FAIL(code, ...)          \
-  do {                               \
-    ::srpde::set_error(__VA_ARGS__); \
-    return code;                     \
-  } while (0)
-
 static int div_check(const char* name, int B, int n, int face_mean) {
   if (B <= 0 || B > kDivMaxB || n < 2 || n > kDivMaxN)
-    DIV_FAIL(kErrShape, "%s: bad shape B=%d n=%d (1 <= B <= %d, 2 <= n <= %d)", name, B, n, kDivMaxB, kDivMaxN);
+    SRPDE_FAIL(kErrShape, "%s: bad shape B=%d n=%d (1 <= B <= %d, 2 <= n <= %d)", name, B, n, kDivMaxB, kDivMaxN);
   if (face_mean != 0 && face_mean != 1)
-    DIV_FAIL(kErrArg, "%s: face_mean=%d (0 arithmetic, 1 harmonic)", name, face_mean);
+    SRPDE_FAIL(kErrArg, "%s: face_mean=%d (0 arithmetic, 1 harmonic)", name, face_mean);
   return 0;
 }
 
 static int div_check_ws(const char* name, int B, int n, const void* ws, size_t ws_bytes) {
-  if (!ws) DIV_FAIL(kErrArg, "%s: null workspace", name);
-  if (!aligned16(ws)) DIV_FAIL(kErrAlign, "%s: workspace not 16-byte aligned", name);
+  if (!ws) SRPDE_FAIL(kErrArg, "%s: null workspace", name);
+  if (!aligned16(ws)) SRPDE_FAIL(kErrAlign, "%s: workspace not 16-byte aligned", name);
   if (ws_bytes < srpde_div_cg_workspace_size(B, n))
-    DIV_FAIL(kErrWorkspace, "%s: workspace too small (%zu bytes, needs %zu)", name, ws_bytes,
-             srpde_div_cg_workspace_size(B, n));
+    SRPDE_FAIL(kErrWorkspace, "%s: workspace too small (%zu bytes, needs %zu)", name, ws_bytes,
+               srpde_div_cg_workspace_size(B, n));
   return 0;
 }
 
 static int div_check_plan(const char* name, int n, const void* plan, size_t plan_bytes) {
-  if (!plan) DIV_FAIL(kErrArg, "%s: null plan", name);
-  if (reinterpret_cast<uintptr_t>(plan) & 7u) DIV_FAIL(kErrAlign, "%s: plan not 8-byte aligned", name);
+  if (!plan) SRPDE_FAIL(kErrArg, "%s: null plan", name);
+  if (reinterpret_cast<uintptr_t>(plan) & 7u) SRPDE_FAIL(kErrAlign, "%s: plan not 8-byte aligned", name);
   if (plan_bytes != dst_plan_bytes_for(n))
-    DIV_FAIL(kErrWorkspace, "%s: a plan of %zu bytes is not a plan for n=%d (srpde_poisson_dst_plan_size: %zu)", name,
-             plan_bytes, n, dst_plan_bytes_for(n));
+    SRPDE_FAIL(kErrWorkspace, "%s: a plan of %zu bytes is not a plan for n=%d (srpde_poisson_dst_plan_size: %zu)", name,
+               plan_bytes, n, dst_plan_bytes_for(n));
   return 0;
 }
 
@@ -349,10 +331,10 @@ int srpde_div_apply(const double* u, const double* theta, double* y, int B, int 
   SRPDE_CHECK_ARG(u && theta && y, "srpde_div_apply: null pointer");
   if (int rc = div_check(name, B, n, face_mean)) return rc;
   if (!(inv_h2 > 0.0) || !std::isfinite(inv_h2))
-    DIV_FAIL(kErrArg, "srpde_div_apply: inv_h2=%g must be positive and finite", inv_h2);
+    SRPDE_FAIL(kErrArg, "srpde_div_apply: inv_h2=%g must be positive and finite", inv_h2);
   if ((reinterpret_cast<uintptr_t>(u) | reinterpret_cast<uintptr_t>(theta) | reinterpret_cast<uintptr_t>(y)) & 7u)
-    DIV_FAIL(kErrAlign, "srpde_div_apply: a pointer is not 8-byte aligned");
-  if (y == u || y == theta) DIV_FAIL(kErrArg, "srpde_div_apply: y aliases an input (a node reads its neighbours)");
+    SRPDE_FAIL(kErrAlign, "srpde_div_apply: a pointer is not 8-byte aligned");
+  if (y == u || y == theta) SRPDE_FAIL(kErrArg, "srpde_div_apply: y aliases an input (a node reads its neighbours)");
   DivCG none = {};
   if (face_mean)
     hipLaunchKernelGGL((div_apply_kernel<false, true>), div_grid(B, n), dim3(kDivThreads), 0, stream, u, theta, y, none,
@@ -369,7 +351,7 @@ int srpde_div_cg_init(const double* f, int B, int n, const void* plan, size_t pl
   const char* name = "srpde_div_cg_init";
   SRPDE_CHECK_ARG(f, "srpde_div_cg_init: null pointer");
   if (int rc = div_check(name, B, n, 0)) return rc;
-  if (reinterpret_cast<uintptr_t>(f) & 7u) DIV_FAIL(kErrAlign, "srpde_div_cg_init: f not 8-byte aligned");
+  if (reinterpret_cast<uintptr_t>(f) & 7u) SRPDE_FAIL(kErrAlign, "srpde_div_cg_init: f not 8-byte aligned");
   if (int rc = div_check_plan(name, n, plan, plan_bytes)) return rc;
   if (int rc = div_check_ws(name, B, n, ws, ws_bytes)) return rc;
   DivCG g = carve(ws, B, n);
@@ -387,10 +369,10 @@ int srpde_div_cg_iterate(const double* theta, int B, int n, int face_mean, doubl
   const char* name = "srpde_div_cg_iterate";
   SRPDE_CHECK_ARG(theta, "srpde_div_cg_iterate: null pointer");
   if (int rc = div_check(name, B, n, face_mean)) return rc;
-  if (reinterpret_cast<uintptr_t>(theta) & 7u) DIV_FAIL(kErrAlign, "srpde_div_cg_iterate: theta not 8-byte aligned");
-  if (!(rtol >= 0.0)) DIV_FAIL(kErrArg, "srpde_div_cg_iterate: rtol=%g must be >= 0", rtol);
+  if (reinterpret_cast<uintptr_t>(theta) & 7u) SRPDE_FAIL(kErrAlign, "srpde_div_cg_iterate: theta not 8-byte aligned");
+  if (!(rtol >= 0.0)) SRPDE_FAIL(kErrArg, "srpde_div_cg_iterate: rtol=%g must be >= 0", rtol);
   if (k_begin < 1 || k_count < 0 || k_count > INT32_MAX - k_begin)
-    DIV_FAIL(kErrArg, "srpde_div_cg_iterate: k_begin=%d k_count=%d (iterations count from 1)", k_begin, k_count);
+    SRPDE_FAIL(kErrArg, "srpde_div_cg_iterate: k_begin=%d k_count=%d (iterations count from 1)", k_begin, k_count);
   if (int rc = div_check_plan(name, n, plan, plan_bytes)) return rc;
   if (int rc = div_check_ws(name, B, n, ws, ws_bytes)) return rc;
   DivCG g = carve(ws, B, n);
@@ -416,12 +398,12 @@ int srpde_div_cg_finish(double* u, int* iters, double* resid, int B, int n, void
   SRPDE_CHECK_ARG(u, "srpde_div_cg_finish: null pointer");
   if (int rc = div_check(name, B, n, 0)) return rc;
   if ((reinterpret_cast<uintptr_t>(u) | reinterpret_cast<uintptr_t>(resid)) & 7u)
-    DIV_FAIL(kErrAlign, "srpde_div_cg_finish: a pointer is not 8-byte aligned");
+    SRPDE_FAIL(kErrAlign, "srpde_div_cg_finish: a pointer is not 8-byte aligned");
   if (int rc = div_check_ws(name, B, n, ws, ws_bytes)) return rc;
   DivCG g = carve(ws, B, n);
   const long long total = (long long)B * n * n;
-  const int blocks = (int)std::min<long long>((total + 255) / 256, 8192);
-  hipLaunchKernelGGL(div_finish_kernel, dim3(blocks), dim3(256), 0, stream, g, u, iters, resid, total, B);
+  hipLaunchKernelGGL(div_finish_kernel, dim3(elementwise_grid(total)), dim3(256), 0, stream, g, u, iters, resid, total,
+                     B);
   SRPDE_LAUNCH_CHECK(name);
   return 0;
 }

@@ -27,6 +27,7 @@
 // The k order of every sum is ascending and fixed by n alone, there are no atomics, and a problem's blocks
 // never see another problem: results are bit-reproducible and independent of B.
 #include "common.h"
+#include "field_reduce.h"
 #include "poisson_dst.h"
 
 namespace srpde {
@@ -292,12 +293,6 @@ size_t dst_plan_bytes_for(int n) { return dst_plan_bytes(n); }
 
 using namespace srpde;
 
-#define DST_FAIL(code, ...)          \
-  do {                               \
-    ::srpde::set_error(__VA_ARGS__); \
-    return code;                     \
-  } while (0)
-
 extern "C" {
 
 size_t srpde_poisson_dst_plan_size(int n) { return (n <= 0 || n > kDstMaxN) ? 0 : dst_plan_bytes(n); }
@@ -311,14 +306,14 @@ size_t srpde_poisson_dst_workspace_size(int B, int n) {
 
 int srpde_poisson_dst_plan(int n, void* plan, size_t plan_bytes, hipStream_t stream) {
   SRPDE_CHECK_ARG(plan, "srpde_poisson_dst_plan: null pointer");
-  if (n <= 0 || n > kDstMaxN) DST_FAIL(kErrShape, "srpde_poisson_dst_plan: bad shape n=%d (1 .. %d)", n, kDstMaxN);
-  if (reinterpret_cast<uintptr_t>(plan) & 7u) DST_FAIL(kErrAlign, "srpde_poisson_dst_plan: plan not 8-byte aligned");
+  if (n <= 0 || n > kDstMaxN) SRPDE_FAIL(kErrShape, "srpde_poisson_dst_plan: bad shape n=%d (1 .. %d)", n, kDstMaxN);
+  if (reinterpret_cast<uintptr_t>(plan) & 7u) SRPDE_FAIL(kErrAlign, "srpde_poisson_dst_plan: plan not 8-byte aligned");
   if (plan_bytes < dst_plan_bytes(n))
-    DST_FAIL(kErrWorkspace, "srpde_poisson_dst_plan: plan buffer too small (%zu bytes, n=%d needs %zu)", plan_bytes, n,
-             dst_plan_bytes(n));
+    SRPDE_FAIL(kErrWorkspace, "srpde_poisson_dst_plan: plan buffer too small (%zu bytes, n=%d needs %zu)", plan_bytes,
+               n, dst_plan_bytes(n));
   double* S = static_cast<double*>(plan);
-  const int blocks = (int)std::min<long long>(((long long)n * n + 255) / 256, 8192);
-  hipLaunchKernelGGL(dst_plan_kernel, dim3(blocks), dim3(256), 0, stream, n, S, S + (size_t)n * n);
+  hipLaunchKernelGGL(dst_plan_kernel, dim3(elementwise_grid((long long)n * n)), dim3(256), 0, stream, n, S,
+                     S + (size_t)n * n);
   SRPDE_LAUNCH_CHECK("srpde_poisson_dst_plan");
   return 0;
 }
@@ -327,17 +322,17 @@ int srpde_poisson_dst_plan(int n, void* plan, size_t plan_bytes, hipStream_t str
 static int dst_check(const char* name, int B, int n, int nmin, const void* plan, size_t plan_bytes, const void* ws,
                      size_t ws_bytes) {
   if (B <= 0 || n < nmin || n > kDstMaxN)
-    DST_FAIL(kErrShape, "%s: bad shape B=%d n=%d (B >= 1, n %d .. %d)", name, B, n, nmin, kDstMaxN);
-  if (reinterpret_cast<uintptr_t>(plan) & 7u) DST_FAIL(kErrAlign, "%s: plan not 8-byte aligned", name);
+    SRPDE_FAIL(kErrShape, "%s: bad shape B=%d n=%d (B >= 1, n %d .. %d)", name, B, n, nmin, kDstMaxN);
+  if (reinterpret_cast<uintptr_t>(plan) & 7u) SRPDE_FAIL(kErrAlign, "%s: plan not 8-byte aligned", name);
   if (plan_bytes != dst_plan_bytes(n))
-    DST_FAIL(kErrWorkspace, "%s: a plan of %zu bytes is not a plan for n=%d (srpde_poisson_dst_plan_size: %zu)", name,
-             plan_bytes, n, dst_plan_bytes(n));
+    SRPDE_FAIL(kErrWorkspace, "%s: a plan of %zu bytes is not a plan for n=%d (srpde_poisson_dst_plan_size: %zu)", name,
+               plan_bytes, n, dst_plan_bytes(n));
   if (n > kDstLdsMaxN) {
-    if (!ws) DST_FAIL(kErrArg, "%s: null workspace (n=%d > %d needs one)", name, n, kDstLdsMaxN);
-    if (!aligned16(ws)) DST_FAIL(kErrAlign, "%s: workspace not 16-byte aligned", name);
+    if (!ws) SRPDE_FAIL(kErrArg, "%s: null workspace (n=%d > %d needs one)", name, n, kDstLdsMaxN);
+    if (!aligned16(ws)) SRPDE_FAIL(kErrAlign, "%s: workspace not 16-byte aligned", name);
     if (ws_bytes < srpde_poisson_dst_workspace_size(B, n))
-      DST_FAIL(kErrWorkspace, "%s: workspace too small (%zu bytes, needs %zu)", name, ws_bytes,
-               srpde_poisson_dst_workspace_size(B, n));
+      SRPDE_FAIL(kErrWorkspace, "%s: workspace too small (%zu bytes, needs %zu)", name, ws_bytes,
+                 srpde_poisson_dst_workspace_size(B, n));
   }
   return 0;
 }

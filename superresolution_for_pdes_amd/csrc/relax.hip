@@ -122,12 +122,6 @@ inline bool relax_overlap(const void* a, const void* b, size_t bytes) {
 
 using namespace srpde;
 
-#define RELAX_FAIL(code, ...)        \
-  do {                               \
-    ::srpde::set_error(__VA_ARGS__); \
-    return code;                     \
-  } while (0)
-
 extern "C" {
 
 int srpde_pde_relax_sweeps_per_launch(void) { return kRelaxK; }
@@ -142,25 +136,25 @@ int srpde_pde_relax(const double* u_in, const double* f, const double* theta, do
                     hipStream_t stream) {
   SRPDE_CHECK_ARG(u_in && f && theta && u_out, "srpde_pde_relax: null pointer");
   if (E <= 0 || E > 65535 || n < 1 || n > kRelaxMaxN || (interior_only && n < 3))
-    RELAX_FAIL(kErrShape, "srpde_pde_relax: bad shape E=%d n=%d (1 <= E <= 65535, 1 <= n <= %d, interior_only needs n >= 3)",
+    SRPDE_FAIL(kErrShape, "srpde_pde_relax: bad shape E=%d n=%d (1 <= E <= 65535, 1 <= n <= %d, interior_only needs n >= 3)",
                E, n, kRelaxMaxN);
-  if (sweeps < 0) RELAX_FAIL(kErrArg, "srpde_pde_relax: sweeps=%d is negative", sweeps);
-  if (!(omega > 0.0 && omega <= 1.0)) RELAX_FAIL(kErrArg, "srpde_pde_relax: omega=%g outside (0, 1]", omega);
+  if (sweeps < 0) SRPDE_FAIL(kErrArg, "srpde_pde_relax: sweeps=%d is negative", sweeps);
+  if (!(omega > 0.0 && omega <= 1.0)) SRPDE_FAIL(kErrArg, "srpde_pde_relax: omega=%g outside (0, 1]", omega);
   if (!(inv_h2 > 0.0) || !std::isfinite(inv_h2))
-    RELAX_FAIL(kErrArg, "srpde_pde_relax: inv_h2=%g must be positive and finite", inv_h2);
+    SRPDE_FAIL(kErrArg, "srpde_pde_relax: inv_h2=%g must be positive and finite", inv_h2);
   const size_t bytes = (size_t)E * n * n * sizeof(double);
   const size_t need = srpde_pde_relax_workspace_size(E, n, sweeps);
   const uintptr_t bits = reinterpret_cast<uintptr_t>(u_in) | reinterpret_cast<uintptr_t>(f) |
                          reinterpret_cast<uintptr_t>(theta) | reinterpret_cast<uintptr_t>(u_out) |
                          (need ? reinterpret_cast<uintptr_t>(workspace) : 0);
-  if (bits & 7u) RELAX_FAIL(kErrAlign, "srpde_pde_relax: a pointer is not 8-byte aligned");
+  if (bits & 7u) SRPDE_FAIL(kErrAlign, "srpde_pde_relax: a pointer is not 8-byte aligned");
   if (relax_overlap(u_out, u_in, bytes) || relax_overlap(u_out, f, bytes) || relax_overlap(u_out, theta, bytes))
-    RELAX_FAIL(kErrArg, "srpde_pde_relax: u_out overlaps an input (a sweep reads its neighbours' old values)");
+    SRPDE_FAIL(kErrArg, "srpde_pde_relax: u_out overlaps an input (a sweep reads its neighbours' old values)");
   if (need) {
-    if (workspace == nullptr || ws_bytes < need) RELAX_FAIL(kErrWorkspace, "srpde_pde_relax: workspace too small");
+    if (workspace == nullptr || ws_bytes < need) SRPDE_FAIL(kErrWorkspace, "srpde_pde_relax: workspace too small");
     if (relax_overlap(workspace, u_out, bytes) || relax_overlap(workspace, u_in, bytes) ||
         relax_overlap(workspace, f, bytes) || relax_overlap(workspace, theta, bytes))
-      RELAX_FAIL(kErrArg, "srpde_pde_relax: the workspace overlaps a field");
+      SRPDE_FAIL(kErrArg, "srpde_pde_relax: the workspace overlaps a field");
   }
   const double c = 0.25 * omega;
   const int tiles = ceil_div(n, kRelaxT);

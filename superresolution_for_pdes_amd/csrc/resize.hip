@@ -11,6 +11,7 @@
 // Memory-bound and tiny (a 640^2 field is 1.6 MB): one thread per output pixel, the 16 taps
 // come from L2 (a row of the source is reused by the 2-3 output rows that map into it).
 #include "common.h"
+#include "field_reduce.h"
 
 namespace srpde {
 
@@ -93,9 +94,8 @@ int srpde_resize_bicubic_ac(const float* x, float* out, int planes, int h, int w
   const float sy = ho > 1 ? (float)(h - 1) / (float)(ho - 1) : 0.f;
   const float sx = wo > 1 ? (float)(w - 1) / (float)(wo - 1) : 0.f;
   const long long total = (long long)planes * ho * wo;
-  const int blocks = (int)std::min<long long>((total + 255) / 256, 8192);
-  hipLaunchKernelGGL(resize_bicubic_ac_kernel, dim3(blocks), dim3(256), 0, stream, x, out, planes, h, w, ho, wo, sy,
-                     sx);
+  hipLaunchKernelGGL(resize_bicubic_ac_kernel, dim3(elementwise_grid(total)), dim3(256), 0, stream, x, out, planes, h,
+                     w, ho, wo, sy, sx);
   SRPDE_LAUNCH_CHECK("srpde_resize_bicubic_ac");
   return 0;
 }

@@ -70,8 +70,10 @@ typedef struct ihipStream_t* hipStream_t;
  *      srpde_pde_relax_workspace_size, srpde_pde_relax
  *  18  the divergence-form operator div(theta grad u) and its sine-preconditioned CG: srpde_div_apply,
  *      srpde_div_cg_workspace_size, srpde_div_cg_done_offset, srpde_div_cg_init, srpde_div_cg_iterate,
- *      srpde_div_cg_finish */
-#define SRPDE_ABI_VERSION 18
+ *      srpde_div_cg_finish
+ *  19  the divergence-form operator in the smoother and the physics loss: srpde_div_relax_workspace_size,
+ *      srpde_div_relax, srpde_physics_loss_div_workspace_size, srpde_physics_loss_div_fwd */
+#define SRPDE_ABI_VERSION 19
 
 /* Kernel-family bits (per call; bit 0 of the same argument is the accumulate flag): the forward / dgrad
  * families compute the same outputs, statistics and stored splits bit for bit, so these only route a call to
@@ -588,6 +590,21 @@ int srpde_physics_loss_fwd(const float* y, const float* t, const float* x, const
                            int n, float weight, float inv_h2_std, float inv_h2_sub, float* loss, float* dy_unit,
                            void* workspace, size_t ws_bytes, hipStream_t stream);
 int srpde_physics_loss_bwd(const float* dy_unit, long long count, const float* gout, float* dy, hipStream_t stream);
+/* The same loss with the residual of the divergence-form equation div(theta grad u) = f (ABI 19; the operator of
+ * srpde_div_apply below, face_mean 0 arithmetic / 1 harmonic, in fp32).  Arguments, outputs, kinds and reductions as
+ * srpde_physics_loss_fwd.  With a(y) = (cE (yE - y) + cW (yW - y)) + (cS (yS - y) + cN (yN - y)) on y with a zero halo
+ * and the ghost coefficient theta_a, and k_miss the number of the node's neighbours outside the grid
+ * (D_theta 1 = -k_miss theta exactly: the interior faces cancel),
+ *     r = ((u_std a(y) + u_mean (-k_miss theta)) / h^2 - f) / f_std          (fp32, in this split form)
+ * dy_unit = 2 (y - t) / (B n^2) + weight (2 u_std / (M f_std h^2)) Dt(m r), Dt the same face sum (symmetric, the
+ * ghost faces on its diagonal).  On a kind-1 sample m r is zero on the ring, so the ghost coefficient there is
+ * immaterial.  3 <= n <= 64; the kernel's LDS (three halo tiles per sample, 51 KiB at n = 64) stays inside the 64 KiB
+ * a kernel may use without raising its limit.  Two launches; workspace: srpde_physics_loss_div_workspace_size bytes
+ * (0 for an unsupported shape), 8-byte aligned.  The gradient is scaled by srpde_physics_loss_bwd. */
+size_t srpde_physics_loss_div_workspace_size(int B, int n);
+int srpde_physics_loss_div_fwd(const float* y, const float* t, const float* x, const int* kind, const float* stats,
+                               int B, int n, int face_mean, float weight, float inv_h2_std, float inv_h2_sub,
+                               float* loss, float* dy_unit, void* workspace, size_t ws_bytes, hipStream_t stream);
 /* How well raw fields satisfy the discrete equation: out [E][2] fp64 = {sqrt(mean r^2), max |r|} per example over
  * the counted nodes (all, or the (n - 2)^2 interior ones with interior_only != 0), r = theta A u inv_h2 - f in fp64
  * with u [E][n][n] fp32 (u_is_f32 != 0) or fp64, f and theta fp64.  r is evaluated as
@@ -617,6 +634,22 @@ size_t srpde_pde_relax_workspace_size(int E, int n, int sweeps);
 int srpde_pde_relax(const double* u_in, const double* f, const double* theta, double* u_out, int E, int n,
                     double inv_h2, int sweeps, double omega, int interior_only, void* workspace, size_t ws_bytes,
                     hipStream_t stream);
+/* Weighted-Jacobi sweeps of div(theta grad u) = f (csrc/relax_div.hip, ABI 19): the same smoother for the operator of
+ * srpde_div_apply below (face coefficients cE, cW, cS, cN from face_mean 0 arithmetic / 1 harmonic, c = theta_a and
+ * u_b = 0 towards the ghost ring; E is x + 1, S is y + 1).  One sweep, every operation rounded once in this order (no
+ * contraction), from the previous sweep's u throughout:
+ *     once per node:  g = f / inv_h2
+ *                     w = omega / ((cE + cW) + (cS + cN))
+ *     per sweep:      a  = (cE*(uE - u) + cW*(uW - u)) + (cS*(uS - u) + cN*(uN - u))
+ *                     u' = u + w * (a - g)
+ * so a host restatement in that order reproduces the result bit for bit, whatever the tiling or the launch split.
+ * The error operator is I - omega diag(-D_theta)^-1 (-D_theta); -D_theta is a symmetric, weakly diagonally dominant
+ * M-matrix, so for 0 < omega <= 1 no error component grows.  interior_only, the workspace, the limits, the alignment
+ * and the overlap rules are those of srpde_pde_relax; srpde_pde_relax_sweeps_per_launch() answers for both. */
+size_t srpde_div_relax_workspace_size(int E, int n, int sweeps);
+int srpde_div_relax(const double* u_in, const double* f, const double* theta, double* u_out, int E, int n,
+                    int face_mean, double inv_h2, int sweeps, double omega, int interior_only, void* workspace,
+                    size_t ws_bytes, hipStream_t stream);
 
 /* ---- clip_grad_norm_ + AdamW on one flat buffer (src/train_enhanced.py:74-75,308) ---- */
 size_t srpde_grad_norm_workspace_size(void);

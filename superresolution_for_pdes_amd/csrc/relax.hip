@@ -31,19 +31,10 @@
 #include <cmath>
 
 #include "common.h"
+#include "relax_tile.h"
 
 namespace srpde {
 namespace {
-
-constexpr int kRelaxT = 48;                            // output tile
-constexpr int kRelaxK = 8;                             // sweeps per launch = halo width
-constexpr int kRelaxP = kRelaxT + 2 * kRelaxK;         // patch side
-constexpr int kRelaxWaves = 8;
-constexpr int kRelaxThreads = 64 * kRelaxWaves;
-constexpr int kRelaxR = kRelaxP / kRelaxWaves;         // rows per thread
-static_assert(kRelaxP == 64, "one patch column per lane");
-static_assert(kRelaxR * kRelaxWaves == kRelaxP && kRelaxR <= 32, "the waves' strips tile the patch");
-constexpr int kRelaxMaxN = 16384;
 
 // grid (tiles, tiles, E); ks <= K sweeps from u_in to u_out (ks = 0: a copy)
 __global__ __launch_bounds__(kRelaxThreads) void pde_relax_kernel(const double* __restrict__ u_in,
@@ -110,11 +101,6 @@ __global__ __launch_bounds__(kRelaxThreads) void pde_relax_kernel(const double* 
       if (y >= K && y < K + T && gy < n) u_out[base + (long long)gy * n + gx] = uc[r];
     }
   }
-}
-
-inline bool relax_overlap(const void* a, const void* b, size_t bytes) {
-  const uintptr_t p = reinterpret_cast<uintptr_t>(a), q = reinterpret_cast<uintptr_t>(b);
-  return p < q + bytes && q < p + bytes;
 }
 
 }  // namespace

@@ -50,8 +50,8 @@ class _PhysicsMSEFn(torch.autograd.Function):
     pass emits the gradient for grad_out = 1 (when one is wanted), the backward pass scales it."""
 
     @staticmethod
-    def forward(ctx, y, t, x, kind, stats, weight, inv_h2, want_grad):
-        terms, unit = H.physics_loss_fwd(y, t, x, kind, stats, weight, inv_h2, want_grad)
+    def forward(ctx, y, t, x, kind, stats, weight, inv_h2, want_grad, face_mean=None):
+        terms, unit = H.physics_loss_fwd(y, t, x, kind, stats, weight, inv_h2, want_grad, face_mean)
         ctx.unit = unit
         return terms
 
@@ -60,12 +60,25 @@ class _PhysicsMSEFn(torch.autograd.Function):
         if ctx.unit is None:
             raise RuntimeError("physics_mse_loss: backward through a loss evaluated without a gradient")
         dy = H.physics_loss_bwd(ctx.unit, gterms.contiguous())   # reads gterms[0], the total's grad_out
-        return dy, None, None, None, None, None, None, None
+        return dy, None, None, None, None, None, None, None, None
 
 
-def physics_loss_terms(y, t, x, kind, stats, weight, inv_h2=DEFAULT_INV_H2):
+def _form_arg(form, face_mean):
+    """The face_mean argument of hipops.physics_loss_fwd: None for the pointwise residual, 0 / 1 for the divergence
+    form's arithmetic / harmonic mean."""
+    from .poisson import check_face_mean, check_form
+    mean = check_face_mean(face_mean)
+    if check_form(form) == "divergence":
+        return mean
+    if face_mean != "harmonic":
+        raise ValueError('face_mean belongs to form="divergence"')
+    return None
+
+
+def physics_loss_terms(y, t, x, kind, stats, weight, inv_h2=DEFAULT_INV_H2, form="pointwise", face_mean="harmonic"):
     """The device tensor (mse + weight * pde, mse, pde) behind ``physics_mse_loss``; differentiable through its
     first element only (the other two are reports of the same pass)."""
+    mean = _form_arg(form, face_mean)
     if y.shape != t.shape:
         raise ValueError(f"physics_mse_loss: shape mismatch {tuple(y.shape)} vs {tuple(t.shape)}")
     if y.dim() != 4 or y.shape[1] != 1 or y.shape[2] != y.shape[3]:
@@ -88,15 +101,19 @@ def physics_loss_terms(y, t, x, kind, stats, weight, inv_h2=DEFAULT_INV_H2):
         raise RuntimeError("physics_mse_loss: HIP path needs float32 ROCm tensors (no CPU fallback)")
     want_grad = torch.is_grad_enabled() and y.requires_grad
     return _PhysicsMSEFn.apply(y.contiguous(), t.contiguous(), x.contiguous(), kind.contiguous(),
-                               stats.contiguous(), float(weight), (float(inv_h2[0]), float(inv_h2[1])), want_grad)
+                               stats.contiguous(), float(weight), (float(inv_h2[0]), float(inv_h2[1])), want_grad,
+                               mean)
 
 
-def physics_mse_loss(y, t, x, kind, stats, weight, inv_h2=DEFAULT_INV_H2) -> torch.Tensor:
+def physics_mse_loss(y, t, x, kind, stats, weight, inv_h2=DEFAULT_INV_H2, form="pointwise",
+                     face_mean="harmonic") -> torch.Tensor:
     """mean((y - t)^2) + weight * L_pde: the MSE plus the mean squared residual of the discrete equation
     theta * L u = f that the samples solve, evaluated from the normalised fields (include/srpde.h,
     srpde_physics_loss_fwd).  x: the model input (theta and f are its channels 1 and 2), kind [B] int32: 0 for a
-    whole-domain sample, 1 for a crop; stats: the dataset's six statistics on the device."""
-    return physics_loss_terms(y, t, x, kind, stats, weight, inv_h2)[0]
+    whole-domain sample, 1 for a crop; stats: the dataset's six statistics on the device.
+    ``form="divergence"``: the residual of div(theta grad u) = f with ``face_mean`` on the faces instead
+    (srpde_physics_loss_div_fwd), for samples that solve the conservative problem."""
+    return physics_loss_terms(y, t, x, kind, stats, weight, inv_h2, form, face_mean)[0]
 
 
 class PhysicsMSELoss(nn.Module):
@@ -106,16 +123,20 @@ class PhysicsMSELoss(nn.Module):
 
     needs_inputs = True
 
-    def __init__(self, weight: float, stats: torch.Tensor, inv_h2=DEFAULT_INV_H2):
+    def __init__(self, weight: float, stats: torch.Tensor, inv_h2=DEFAULT_INV_H2, form: str = "pointwise",
+                 face_mean: str = "harmonic"):
         super().__init__()
         if weight < 0:
             raise ValueError("PhysicsMSELoss: weight >= 0")
+        _form_arg(form, face_mean)
+        self.form, self.face_mean = form, face_mean
         self.weight = float(weight)
         self.inv_h2 = (float(inv_h2[0]), float(inv_h2[1]))
         self.register_buffer("stats", stats.detach().float().contiguous().clone(), persistent=False)
         self.last_terms = None
 
     def forward(self, input, target, x, kind):  # noqa: A002
-        terms = physics_loss_terms(input, target, x, kind, self.stats, self.weight, self.inv_h2)
+        terms = physics_loss_terms(input, target, x, kind, self.stats, self.weight, self.inv_h2, self.form,
+                                   self.face_mean)
         self.last_terms = terms.detach()
         return terms[0]

@@ -1214,10 +1214,12 @@ def mse_bwd(y, t, gout):
 
 
 # ------------------------------ MSE + PDE residual ---------------------------------
-def physics_loss_fwd(y, t, x, kind, stats, weight, inv_h2, want_grad=True):
+def physics_loss_fwd(y, t, x, kind, stats, weight, inv_h2, want_grad=True, face_mean=None):
     """srpde_physics_loss_fwd: y, t [B, 1, n, n] and x [B, 3, n, n] fp32, kind [B] int32, stats 6 floats, all on one
     device -> (loss [3] = (mse + weight * pde, mse, pde), the gradient for grad_out = 1 or None).  ``inv_h2``: the
-    1 / h^2 of (kind 0, kind 1).  Without ``want_grad`` no gradient is computed or written."""
+    1 / h^2 of (kind 0, kind 1).  Without ``want_grad`` no gradient is computed or written.  ``face_mean`` None: the
+    pointwise residual theta * L u - f; 0 (arithmetic) or 1 (harmonic): the divergence-form residual
+    div(theta grad u) - f through srpde_physics_loss_div_fwd."""
     _fields("physics_loss_fwd", F32, y, t, x, stats)
     _fields("physics_loss_fwd", torch.int32, kind)
     if y.dim() != 4 or y.shape[1] != 1 or y.shape[2] != y.shape[3] or t.shape != y.shape:
@@ -1227,10 +1229,16 @@ def physics_loss_fwd(y, t, x, kind, stats, weight, inv_h2, want_grad=True):
     if x.shape != (B, 3, n, n) or kind.shape != (B,) or stats.numel() != 6:
         raise ValueError(f"physics_loss_fwd: x must be [{B}, 3, {n}, {n}], kind [{B}], stats 6 values; got "
                          f"{tuple(x.shape)}, {tuple(kind.shape)}, {stats.numel()}")
-    nbytes = int(query("srpde_physics_loss_workspace_size", B, n))
+    div = face_mean is not None
+    nbytes = int(query("srpde_physics_loss_div_workspace_size" if div else "srpde_physics_loss_workspace_size", B, n))
     ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=y.device)
     loss = torch.empty(3, dtype=F32, device=y.device)
     unit = torch.empty_like(y) if want_grad else None
+    if div:
+        call("srpde_physics_loss_div_fwd", y.data_ptr(), t.data_ptr(), x.data_ptr(), kind.data_ptr(),
+             stats.data_ptr(), B, n, int(face_mean), float(weight), float(inv_h2[0]), float(inv_h2[1]),
+             loss.data_ptr(), _p(unit), ws.data_ptr(), nbytes, stream_ptr())
+        return loss, unit
     call("srpde_physics_loss_fwd", y.data_ptr(), t.data_ptr(), x.data_ptr(), kind.data_ptr(), stats.data_ptr(), B, n,
          float(weight), float(inv_h2[0]), float(inv_h2[1]), loss.data_ptr(), _p(unit), ws.data_ptr(), nbytes,
          stream_ptr())
@@ -1284,6 +1292,23 @@ def pde_relax(u, f, theta, inv_h2, sweeps, omega=0.8, interior_only=False):
     ws = torch.empty(nbytes // 8, dtype=torch.float64, device=f.device) if nbytes else None
     call("srpde_pde_relax", u.data_ptr(), f.data_ptr(), theta.data_ptr(), out.data_ptr(), E, n, float(inv_h2), sweeps,
          float(omega), int(bool(interior_only)), _p(ws), nbytes, stream_ptr())
+    return out
+
+
+def pde_relax_div(u, f, theta, inv_h2, sweeps, omega=0.8, interior_only=False, face_mean=1):
+    """srpde_div_relax: ``sweeps`` weighted-Jacobi sweeps of div(theta grad u) * inv_h2 = f on fp64 fields [E, n, n]
+    -> a new [E, n, n] fp64 tensor (the inputs are left alone); ``face_mean`` 0 arithmetic, 1 harmonic; over all nodes
+    against a zero ghost ring, or with the ring of the fields held (``interior_only``)."""
+    _fields("pde_relax_div", torch.float64, u, f, theta)
+    if f.dim() != 3 or f.shape[1] != f.shape[2] or u.shape != f.shape or theta.shape != f.shape:
+        raise ValueError("pde_relax_div: u, f and theta must share one [E, n, n] shape")
+    E, n, _ = f.shape
+    sweeps = int(sweeps)
+    out = torch.empty_like(u)
+    nbytes = int(query("srpde_div_relax_workspace_size", E, n, sweeps))
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=f.device) if nbytes else None
+    call("srpde_div_relax", u.data_ptr(), f.data_ptr(), theta.data_ptr(), out.data_ptr(), E, n, int(face_mean),
+         float(inv_h2), sweeps, float(omega), int(bool(interior_only)), _p(ws), nbytes, stream_ptr())
     return out
 
 

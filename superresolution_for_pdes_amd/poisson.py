@@ -261,7 +261,7 @@ def residual_metrics(u, f, theta, interior_only: bool = False, inv_h2: float = N
 
 
 def relax(u, f, theta, sweeps: int, omega: float = 0.8, interior_only: bool = False, inv_h2: float = None,
-          device="cuda"):
+          device="cuda", form: str = "pointwise", face_mean: str = "harmonic"):
     """``sweeps`` weighted-Jacobi sweeps of theta * A u / h^2 = f (A the 5-point stencil with a zero ghost ring):
     u <- u + (omega / 4) (A u - h^2 f / theta), each from the previous sweep's u.  It damps the error at the grid
     scale (for omega = 0.8 every component with a wavenumber >= pi / 2 shrinks by at least 0.6 per sweep) and, for
@@ -269,8 +269,14 @@ def relax(u, f, theta, sweeps: int, omega: float = 0.8, interior_only: bool = Fa
     u, f [n, n] or [E, n, n], numpy or tensors; theta is broadcast.  ``inv_h2`` defaults to (n - 1)^2, the whole-domain
     operator that solve_batched solves and residual_metrics scores; ``interior_only`` holds the boundary nodes at
     their values (a crop of a larger solve, whose ring is not zero).  -> a new [E, n, n] fp64 device tensor.
-    Stream-ordered, no host sync (srpde_pde_relax)."""
+    Stream-ordered, no host sync (srpde_pde_relax).
+    ``form="divergence"``: the sweeps of div(theta grad u) = f with ``face_mean`` on the faces instead,
+    u <- u + omega (D_theta u - f) / sum of the node's four face coefficients (srpde_div_relax; include/srpde.h states
+    the rounding order); the same guarantee for 0 < omega <= 1.  ``face_mean`` belongs to that form."""
     from . import hipops as H
+    mean = check_face_mean(face_mean)
+    if check_form(form) == "pointwise" and face_mean != "harmonic":
+        raise ValueError('face_mean belongs to form="divergence"')
     if int(sweeps) < 0:
         raise ValueError(f"relax: sweeps must be >= 0, got {sweeps}")
     if not 0.0 < float(omega) <= 1.0:
@@ -281,8 +287,10 @@ def relax(u, f, theta, sweeps: int, omega: float = 0.8, interior_only: bool = Fa
     if theta.shape != f.shape:
         theta = theta.expand_as(f).contiguous()
     n = u.shape[-1]
-    return H.pde_relax(u, f, theta, float((n - 1) ** 2 if inv_h2 is None else inv_h2), int(sweeps), float(omega),
-                       interior_only)
+    inv_h2 = float((n - 1) ** 2 if inv_h2 is None else inv_h2)
+    if form == "divergence":
+        return H.pde_relax_div(u, f, theta, inv_h2, int(sweeps), float(omega), interior_only, mean)
+    return H.pde_relax(u, f, theta, inv_h2, int(sweeps), float(omega), interior_only)
 
 
 def solve_batched(f, theta, rtol: float = DEFAULT_RTOL, maxit: int = None, device="cuda",

@@ -344,6 +344,10 @@ def arg_parser():
     ap.add_argument("--pde-weight", type=float, default=0.0, metavar="LAMBDA",
                     help="add LAMBDA x the mean squared residual of the discrete equation to the MSE loss "
                          "(functional.PhysicsMSELoss); 0 (default): plain MSE")
+    ap.add_argument("--pde-div-weight", type=float, default=0.0, metavar="LAMBDA",
+                    help="add LAMBDA x the mean squared residual of div(theta grad u) = f to the MSE loss "
+                         "(functional.PhysicsMSELoss(form='divergence')); needs --operator divergence and uses its "
+                         "--face-mean; not together with --pde-weight")
     ap.add_argument("--operator", choices=("pointwise", "divergence"), default="pointwise",
                     help="the equation behind the --online samples: theta * Lap(u) = f (default) or the conservative "
                          "div(theta grad u) = f (poisson.solve_div; needs --online and --online-theta)")
@@ -353,15 +357,24 @@ def arg_parser():
 
 
 def check_operator_args(args):
-    """The refusals of --operator / --face-mean, before any device work."""
+    """The refusals of --operator / --face-mean / --pde-div-weight, before any device work."""
+    if args.pde_div_weight < 0:
+        raise SystemExit("--pde-div-weight: a weight >= 0")
+    if args.pde_div_weight > 0:
+        if args.operator != "divergence":
+            raise SystemExit("--pde-div-weight weighs the residual of div(theta grad u) = f: it needs --operator "
+                             "divergence (--pde-weight is the pointwise residual's weight)")
+        if args.pde_weight > 0:
+            raise SystemExit("--pde-div-weight cannot be combined with --pde-weight > 0: a run's samples solve one "
+                             "equation")
     if args.operator == "divergence":
         if args.online is None or args.online_theta is None:
             raise SystemExit("--operator divergence needs --online and --online-theta (with theta = 1 it is the "
                              "pointwise operator, and the fixed dataset generators are pointwise)")
         if args.pde_weight > 0:
-            raise SystemExit("--operator divergence cannot be combined with --pde-weight > 0: the physics loss "
-                             "(csrc/physics.hip) evaluates the pointwise residual theta * Lap(u) - f; teaching it the "
-                             "divergence form is a later change")
+            raise SystemExit("--operator divergence cannot be combined with --pde-weight > 0: that flag weighs the "
+                             "pointwise residual theta * Lap(u) - f, which these samples do not satisfy; "
+                             "--pde-div-weight weighs the residual of div(theta grad u) = f")
     elif args.face_mean != "harmonic":
         raise SystemExit("--face-mean belongs to --operator divergence")
 
@@ -377,19 +390,21 @@ def online_loaders(args, config, rank, world, device):
         raise SystemExit("--online: at least one step per epoch")
     stream = SampleStream(42, config["batch_size"], theta_range=args.online_theta, solver=args.solver, rank=rank,
                           world=world, device=device, form=args.operator, face_mean=args.face_mean)
-    with_kind = args.pde_weight > 0
+    with_kind = args.pde_weight > 0 or args.pde_div_weight > 0
     return (OnlineBatchLoader(stream, args.online, with_kind=with_kind),
             stream.validation_loader(ONLINE_VAL_SAMPLES, config["batch_size"], with_kind=with_kind))
 
 
-def physics_criterion(weight, stats, save_dir=None):
-    """The criterion of --pde-weight; with ``save_dir`` its settings go to physics_loss.json beside config.json."""
+def physics_criterion(weight, stats, save_dir=None, form="pointwise", face_mean="harmonic"):
+    """The criterion of --pde-weight (``form="pointwise"``) or --pde-div-weight (``"divergence"``, with the run's
+    ``face_mean``); with ``save_dir`` its settings go to physics_loss.json beside config.json."""
     from .functional import PhysicsMSELoss
-    criterion = PhysicsMSELoss(weight, stats)
+    criterion = PhysicsMSELoss(weight, stats, form=form, face_mean=face_mean)
     if save_dir is not None:
         with open(Path(save_dir) / "physics_loss.json", "w") as f:
             json.dump({"weight": criterion.weight, "inv_h2": list(criterion.inv_h2),
-                       "stats": [float(v) for v in stats.detach().cpu()]}, f, indent=4)
+                       "stats": [float(v) for v in stats.detach().cpu()], "form": criterion.form,
+                       "face_mean": criterion.face_mean if form == "divergence" else None}, f, indent=4)
     return criterion
 
 
@@ -400,7 +415,7 @@ def main(argv=None):
     if args.pde_weight < 0:
         raise SystemExit("--pde-weight: a weight >= 0")
     check_operator_args(args)
-    with_kind = args.pde_weight > 0
+    with_kind = args.pde_weight > 0 or args.pde_div_weight > 0
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world > 1 and not dist.is_initialized():
@@ -452,7 +467,13 @@ def main(argv=None):
     if world > 1:
         from .distributed import DataParallel
         net = DataParallel(model)
-    criterion = physics_criterion(args.pde_weight, stats, save_dir if rank == 0 else None) if with_kind else MSELoss()
+    if args.pde_div_weight > 0:
+        criterion = physics_criterion(args.pde_div_weight, stats, save_dir if rank == 0 else None, "divergence",
+                                      args.face_mean)
+    elif with_kind:
+        criterion = physics_criterion(args.pde_weight, stats, save_dir if rank == 0 else None)
+    else:
+        criterion = MSELoss()
     optimizer = FusedAdamW(model.parameters(), lr=config["learning_rate"], weight_decay=1e-4)
     scheduler = optim.lr_scheduler.ReduceLROnPlateau(optimizer, mode="min", factor=0.5, patience=config["patience"],
                                                      min_lr=config["min_lr"])

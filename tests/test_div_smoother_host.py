@@ -1,0 +1,378 @@
+"""CPU: the divergence-form operator in the smoother and in the physics loss (csrc/relax_div.hip, csrc/physics.hip,
+ABI 19; poisson.relax(form="divergence"), functional.PhysicsMSELoss(form="divergence"), tiled_inference's
+``polish_form``, train_enhanced --pde-div-weight).
+
+``relax_div_np`` restates srpde_div_relax with one numpy pass per sweep in the header's order of operations, on the
+face coefficients of tests/poisson_div_ref.py; tests/test_gpu_relax_div.py compares the kernel with it by equality of
+bits.  ``restatement_div`` is the loss of srpde_physics_loss_div_fwd in torch (fp64 by default), differentiable in y;
+tests/test_gpu_physics_div.py measures the kernel against it.  Here both are established on their own: the dense error
+operator's spectrum, the sine modes at theta = 1, the sparse direct solver's solutions as fixed points and as zeros of
+the loss term.  Then the host side: every argument check of the two new C entries (each fails before a launch), the
+workspace queries, the Python keyword refusals and the command line."""
+import numpy as np
+import pytest
+import torch
+
+import poisson_div_ref as D
+from test_relax_host import mode_factor, sine_mode
+
+INV_H2 = (39.0 ** 2, 79.0 ** 2)
+
+
+def relax_div_np(u, f, theta, mean, inv_h2, sweeps, omega=0.8, interior_only=False):
+    """srpde_div_relax restated: fields [E, n, n] fp64, every operation one rounded numpy pass, Jacobi (each sweep
+    reads the previous one's u throughout)."""
+    u = np.array(u, dtype=np.float64)
+    f, theta = np.asarray(f, np.float64), np.asarray(theta, np.float64)
+    cE, cW, cS, cN = D._faces(theta, mean)
+    g = f / np.float64(inv_h2)
+    w = np.float64(omega) / ((cE + cW) + (cS + cN))
+    for _ in range(sweeps):
+        p = np.pad(u, ((0, 0), (1, 1), (1, 1)))                       # a neighbour outside the grid is 0
+        uE, uW, uS, uN = p[:, 1:-1, 2:], p[:, 1:-1, :-2], p[:, 2:, 1:-1], p[:, :-2, 1:-1]
+        a = (cE * (uE - u) + cW * (uW - u)) + (cS * (uS - u) + cN * (uN - u))
+        new = u + w * (a - g)
+        if interior_only:                                             # the ring keeps its value in every sweep
+            new[:, 0, :], new[:, -1, :], new[:, :, 0], new[:, :, -1] = u[:, 0, :], u[:, -1, :], u[:, :, 0], u[:, :, -1]
+        u = new
+    return u
+
+
+def restatement_div(y, t, x, kind, stats, weight, inv_h2=INV_H2, mean="harmonic", dtype=torch.float64):
+    """y, t [B, 1, n, n], x [B, 3, n, n], kind [B], stats 6 values -> dict(total, mse, pde, r, m, theta, q, M), in
+    ``dtype`` throughout (fp64: the reference; fp32: what a kernel in that precision can reach).  Differentiable in
+    y."""
+    y, t, x = y.to(dtype), t.to(dtype), x.to(dtype)
+    mu_u, sg_u, mu_f, sg_f, mu_t, sg_t = [float(torch.as_tensor(v).to(dtype)) for v in stats]
+    n = y.shape[-1]
+    theta = sg_t * x[:, 1:2] + mu_t
+    f = sg_f * x[:, 2:3] + mu_f
+    sub = (torch.as_tensor(kind).reshape(-1, 1, 1, 1) != 0)
+    ih2 = torch.where(sub, torch.tensor(float(inv_h2[1]), dtype=dtype), torch.tensor(float(inv_h2[0]), dtype=dtype))
+    inner = torch.zeros(1, 1, n, n, dtype=torch.bool)
+    inner[..., 1:-1, 1:-1] = True
+    m = (~sub | inner).to(dtype)                      # kind 0: every node; kind 1: the interior
+    cE, cW, cS, cN = (torch.from_numpy(c) for c in D._faces(theta.detach().numpy(), mean))
+    assert cE.dtype == dtype
+    p = torch.nn.functional.pad(y, (1, 1, 1, 1))
+    a = (cE * (p[..., 1:-1, 2:] - y) + cW * (p[..., 1:-1, :-2] - y)) + \
+        (cS * (p[..., 2:, 1:-1] - y) + cN * (p[..., :-2, 1:-1] - y))
+    edge = torch.zeros(n, dtype=dtype)
+    edge[0] += 1
+    edge[-1] += 1
+    k_miss = (edge[:, None] + edge[None, :]).reshape(1, 1, n, n)      # D_theta 1 = -k_miss theta: the ghost faces
+    r = ((sg_u * a + mu_u * (-k_miss * theta)) * ih2 - f) / sg_f
+    M = m.sum()
+    pde = (m * r * r).sum() / M
+    mse = ((y - t) ** 2).mean()
+    return {"total": mse + weight * pde, "mse": mse, "pde": pde, "r": r, "m": m, "theta": theta, "q": m * r,
+            "M": float(M)}
+
+
+def normalised(u, f, theta):
+    """(y, x, stats) fp64 from raw [B, n, n] fields with the dataset's statistics (mean, unbiased std over the set)."""
+    u, f, theta = (torch.as_tensor(np.asarray(v), dtype=torch.float64) for v in (u, f, theta))
+    mu_u, sg_u, mu_f, sg_f, mu_t, sg_t = u.mean(), u.std(), f.mean(), f.std(), theta.mean(), theta.std()
+    x = torch.stack([torch.zeros_like(u), (theta - mu_t) / sg_t, (f - mu_f) / sg_f], dim=1)
+    stats = torch.tensor([float(v) for v in (mu_u, sg_u, mu_f, sg_f, mu_t, sg_t)], dtype=torch.float64)
+    return ((u - mu_u) / sg_u).unsqueeze(1), x, stats
+
+
+CROP = (17, 23)     # (row, column) of the 40^2 crop's first node in the 80^2 solve
+
+
+@pytest.fixture(scope="module")
+def solutions():
+    """{mean: dict(whole=(u, f, theta) at 40^2, crop=(u, f, theta) 40^2 out of an 80^2 solve)}: theta ~ U(0.5, 2),
+    solved by the sparse direct solver of poisson_div_ref (rtol of a direct solve)."""
+    out = {}
+    for mean in D.MEANS:
+        th40, th80 = D.field_theta(40, 7, 0.5, 2.0), D.field_theta(80, 8, 0.5, 2.0)
+        f40, f80 = D.forcing(40), D.forcing(80, 2.3, 4.1)
+        u40, u80 = D.solve_sparse(f40, th40, mean), D.solve_sparse(f80, th80, mean)
+        i, j = CROP
+        out[mean] = {"whole": (u40, f40, th40),
+                     "crop": tuple(a[i:i + 40, j:j + 40].copy() for a in (u80, f80, th80))}
+    return out
+
+
+@pytest.fixture(scope="module")
+def lib():
+    from superresolution_for_pdes_amd import build
+    build.build()
+    from superresolution_for_pdes_amd import _lib
+    return _lib
+
+
+# ---- the smoother's restatement --------------------------------------------------------------------------------
+@pytest.mark.parametrize("omega", [0.8, 1.0])
+@pytest.mark.parametrize("lo,hi", [(0.5, 2.0), (0.1, 10.0)])
+@pytest.mark.parametrize("mean", D.MEANS)
+def test_error_operator_spectrum(mean, lo, hi, omega):
+    """n = 12: the dense error operator I - omega diag(-D)^-1 (-D), column j = one sweep of e_j with f = 0.  It is
+    similar to a symmetric matrix, so its eigenvalues are real, and they lie in [-1, 1]."""
+    n = 12
+    theta = D.field_theta(n, 3, lo, hi)
+    eye = np.eye(n * n).reshape(n * n, n, n)
+    G = relax_div_np(eye, np.zeros_like(eye), np.broadcast_to(theta, eye.shape), mean, (n - 1) ** 2, 1,
+                     omega).reshape(n * n, n * n).T
+    ev = np.linalg.eigvals(G)
+    print(f"{mean} U({lo},{hi}) omega={omega}: eigenvalues in [{ev.real.min():.4f}, {ev.real.max():.4f}], "
+          f"max |imag| {np.abs(ev.imag).max():.1e}")
+    assert np.abs(ev.imag).max() <= 1e-9
+    assert ev.real.min() >= -1.0 and ev.real.max() <= 1.0
+    # and it is what the theory says: I + omega diag(-D)^-1 D
+    Dm = D.dense(theta, mean)
+    want = np.eye(n * n) + omega * (Dm / -np.diag(Dm)[:, None])
+    assert np.abs(G - want).max() <= 1e-14
+
+
+@pytest.mark.parametrize("omega", [0.8, 1.0])
+@pytest.mark.parametrize("mean", D.MEANS)
+def test_sine_modes_are_eigenvectors_at_theta_one(mean, omega):
+    """theta = 1: every face coefficient is exactly 1 and the sweep is the pointwise one: mode (p, q) times
+    lambda^8 after eight sweeps, to 1e-14."""
+    for n in (7, 33):
+        one, zero = np.ones((1, n, n)), np.zeros((1, n, n))
+        for p, q in ((1, 1), (n, n), (n // 2 + 1, 2)):
+            v = sine_mode(n, p, q)
+            lam = mode_factor(n, p, q, omega)
+            got = relax_div_np(v[None], zero, one, mean, (n - 1) ** 2, 8, omega)[0]
+            err = np.abs(got - lam ** 8 * v).max()
+            print(f"{mean} n={n} omega={omega} mode=({p},{q}) lambda={lam:.6f} err={err:.2e}")
+            assert err <= 1e-14
+
+
+@pytest.mark.parametrize("mean", D.MEANS)
+def test_solutions_are_fixed_points(solutions, mean):
+    """Eight sweeps move a solution by <= 1e-13 max|u| (8e-16 max|u| was measured when this was written): the
+    whole-domain solve at n = 40 and, with the ring held, the interior of a 40^2 crop of an 80^2 solve."""
+    u, f, th = solutions[mean]["whole"]
+    moved = np.abs(relax_div_np(u[None], f[None], th[None], mean, 39.0 ** 2, 8)[0] - u).max() / np.abs(u).max()
+    uc, fc, tc = solutions[mean]["crop"]
+    got = relax_div_np(uc[None], fc[None], tc[None], mean, 79.0 ** 2, 8, interior_only=True)[0]
+    moved_c = np.abs(got - uc).max() / np.abs(uc).max()
+    print(f"{mean}: moved {moved:.2e} (whole), {moved_c:.2e} (crop) of max|u|")
+    assert moved <= 1e-13 and moved_c <= 1e-13
+    ring = np.ones((40, 40), bool)
+    ring[1:-1, 1:-1] = False
+    assert np.array_equal(got[ring], uc[ring])
+    # without the held ring the crop is no fixed point: the ghost ring is wrong for it
+    free = relax_div_np(uc[None], fc[None], tc[None], mean, 79.0 ** 2, 8)[0]
+    assert np.abs(free - uc).max() / np.abs(uc).max() > 1e-3
+
+
+# ---- the loss restatement --------------------------------------------------------------------------------------
+def loss_batch(solutions, mean, noise=0.0, seed=0):
+    """(y, t, x, kind, stats): the whole-domain solution (kind 0) and the crop (kind 1), y = t + noise * randn."""
+    (u0, f0, t0), (u1, f1, t1) = solutions[mean]["whole"], solutions[mean]["crop"]
+    t, x, stats = normalised(np.stack([u0, u1]), np.stack([f0, f1]), np.stack([t0, t1]))
+    g = torch.Generator().manual_seed(seed)
+    y = t + noise * torch.randn(t.shape, generator=g, dtype=torch.float64)
+    return y, t, x, torch.tensor([0, 1], dtype=torch.int32), stats
+
+
+@pytest.mark.parametrize("mean", D.MEANS)
+def test_loss_restatement_is_the_operator_residual(solutions, mean):
+    """fp64, y = truth + 1e-2 noise: r equals (D_theta u - f) / f_std of poisson_div_ref.apply on the denormalised
+    field on the counted nodes, to 1e-12 of max|r|."""
+    y, t, x, kind, stats = loss_batch(solutions, mean, 1e-2)
+    out = restatement_div(y, t, x, kind, stats, 1.0, mean=mean)
+    mu_u, sg_u, mu_f, sg_f, mu_t, sg_t = [float(v) for v in stats]
+    u = (sg_u * y[:, 0] + mu_u).numpy()
+    theta = (sg_t * x[:, 1] + mu_t).numpy()
+    f = (sg_f * x[:, 2] + mu_f).numpy()
+    for b in range(2):
+        want = (D.apply(u[b], theta[b], mean, INV_H2[b]) - f[b]) / sg_f
+        mask = out["m"][b, 0].numpy().astype(bool) if b else np.ones((40, 40), bool)
+        assert mask.sum() == (38 * 38 if b else 1600)
+        got = out["r"][b, 0].numpy()
+        err = np.abs(got - want)[mask].max() / np.abs(want[mask]).max()
+        print(f"{mean} kind {b}: max|r| {np.abs(want[mask]).max():.3e} rel err {err:.2e}")
+        assert err <= 1e-12
+    assert out["M"] == 1600 + 38 * 38
+    print(f"{mean}: pde with 1e-2 noise {float(out['pde']):.4f}")
+    assert float(out["pde"]) > 1e-3
+
+
+@pytest.mark.parametrize("mean", D.MEANS)
+def test_loss_term_vanishes_on_solutions(solutions, mean):
+    """On exact solutions the term is <= 1e-25 in fp64 and <= 5e-11 in fp32 (1.2e-13 .. 1.65e-12 were measured for
+    this formulation; the margin allows another operation order and fused multiply-adds)."""
+    y, t, x, kind, stats = loss_batch(solutions, mean)
+    for b in range(2):
+        sel = slice(b, b + 1)
+        p64 = float(restatement_div(y[sel], t[sel], x[sel], kind[sel], stats, 1.0, mean=mean)["pde"])
+        o32 = restatement_div(y[sel].float(), t[sel].float(), x[sel].float(), kind[sel], stats.float(), 1.0,
+                              mean=mean, dtype=torch.float32)
+        p32 = float(o32["pde"])
+        print(f"{mean} kind {b}: pde fp64 {p64:.2e} fp32 {p32:.2e}")
+        assert o32["r"].dtype == torch.float32
+        assert p64 <= 1e-25 and p32 <= 5e-11
+
+
+def test_loss_gradient_is_the_symmetric_face_operator(solutions):
+    """autograd of the restatement = the closed form of include/srpde.h: weight (2 sigma_u / (M sigma_f)) ih2 Dt(q),
+    Dt the face sum on q = m r with a zero halo."""
+    mean = "harmonic"
+    y, t, x, kind, stats = loss_batch(solutions, mean, 1e-2)
+    yd = y.clone().requires_grad_(True)
+    out = restatement_div(yd, y, x, kind, stats, 1.0, mean=mean)       # t = y: no MSE part
+    out["total"].backward()
+    sg_u, sg_f = float(stats[1]), float(stats[3])
+    q = out["q"].detach()[:, 0].numpy()
+    theta = out["theta"].detach()[:, 0].numpy()
+    for b in range(2):
+        want = (2.0 * sg_u / (out["M"] * sg_f)) * D.apply(q[b], theta[b], mean, INV_H2[b])
+        got = yd.grad[b, 0].numpy()
+        assert np.abs(got - want).max() <= 1e-12 * np.abs(want).max()
+
+
+# ---- the C entries ---------------------------------------------------------------------------------------------
+def test_div_relax_argument_checks(lib):
+    """Every refusal of srpde_div_relax comes before a launch (the pointers are never dereferenced on the host)."""
+    cd = lib.lib()
+    K = lib.query("srpde_pde_relax_sweeps_per_launch")
+    n, E = 40, 2
+    field = E * n * n * 8
+    A, B, C, O, W = (1 << 20) + 0 * field, (1 << 20) + 2 * field, (1 << 20) + 4 * field, (1 << 20) + 6 * field, \
+        (1 << 20) + 8 * field
+
+    def run(u=A, f=B, th=C, out=O, E=E, n=n, mean=1, inv_h2=1521.0, sweeps=K, omega=0.8, interior=0, ws=0, ws_bytes=0):
+        return cd.srpde_div_relax(u, f, th, out, E, n, mean, inv_h2, sweeps, omega, interior, ws, ws_bytes, 0)
+    for kw in ({"u": 0}, {"f": 0}, {"th": 0}, {"out": 0}):
+        assert run(**kw) < 0 and "null" in lib.last_error()
+    for kw, word in (({"E": 0}, "E=0"), ({"E": 65536}, "E=65536"), ({"n": 0}, "n=0"), ({"n": 16385}, "n=16385"),
+                     ({"n": 2, "interior": 1}, "interior_only")):
+        assert run(**kw) < 0 and word in lib.last_error(), (kw, lib.last_error())
+    for mean in (-1, 2):
+        assert run(mean=mean) < 0 and "face_mean" in lib.last_error()
+    assert run(sweeps=-1) < 0 and "negative" in lib.last_error()
+    for omega in (0.0, -0.5, 1.0001, float("nan")):
+        assert run(omega=omega) < 0 and "omega" in lib.last_error()
+    for h in (0.0, -1.0, float("inf"), float("nan")):
+        assert run(inv_h2=h) < 0 and "inv_h2" in lib.last_error()
+    for kw in ({"u": A + 4}, {"f": B + 4}, {"th": C + 4}, {"out": O + 4}):
+        assert run(**kw) < 0 and "aligned" in lib.last_error()
+    for kw in ({"out": A}, {"out": B + 8}, {"out": C + field - 8}):
+        assert run(**kw) < 0 and "overlaps an input" in lib.last_error()
+    need = lib.query("srpde_div_relax_workspace_size", E, n, K + 1)
+    assert need == field
+    assert run(sweeps=K + 1) < 0 and "workspace too small" in lib.last_error()
+    assert run(sweeps=K + 1, ws=W, ws_bytes=need - 1) < 0 and "workspace too small" in lib.last_error()
+    assert run(sweeps=K + 1, ws=W + 4, ws_bytes=need) < 0 and "aligned" in lib.last_error()
+    for ws in (A, B, C, O):
+        assert run(sweeps=K + 1, ws=ws, ws_bytes=need) < 0 and "workspace overlaps" in lib.last_error()
+
+
+def test_div_relax_queries(lib):
+    q = lib.query
+    K = q("srpde_pde_relax_sweeps_per_launch")
+    assert K == 8
+    for sweeps in (0, 1, K):
+        assert q("srpde_div_relax_workspace_size", 3, 40, sweeps) == 0
+    for sweeps in (K + 1, 5 * K):
+        assert q("srpde_div_relax_workspace_size", 3, 40, sweeps) == 3 * 40 * 40 * 8
+    assert q("srpde_div_relax_workspace_size", 0, 40, 2 * K) == 0 and q("srpde_div_relax_workspace_size", 3, 0, 2 * K) == 0
+    assert q("srpde_div_relax_workspace_size", 3, 40, 2 * K) == q("srpde_pde_relax_workspace_size", 3, 40, 2 * K)
+
+
+def test_physics_div_argument_checks_and_queries(lib):
+    cd = lib.lib()
+    ok = (16, 16, 16, 16, 16)          # y, t, x, kind, stats: non-null, never dereferenced on the host
+
+    def fwd(ptrs=ok, B=2, n=40, mean=1, loss=16, ws=16, ws_bytes=1 << 20):
+        return cd.srpde_physics_loss_div_fwd(*ptrs, B, n, mean, 0.1, INV_H2[0], INV_H2[1], loss, 0, ws, ws_bytes, 0)
+    for k in range(5):
+        assert fwd(ptrs=ok[:k] + (0,) + ok[k + 1:]) < 0 and "null" in lib.last_error()
+    assert fwd(loss=0) < 0 and "null" in lib.last_error()
+    assert fwd(ws=0) < 0 and "null" in lib.last_error()
+    for n in (2, 65):
+        assert fwd(n=n) < 0 and f"n={n}" in lib.last_error()
+    assert fwd(B=0) < 0 and "B=0" in lib.last_error()
+    for mean in (-1, 2):
+        assert fwd(mean=mean) < 0 and "face_mean" in lib.last_error()
+    assert fwd(ws=20) < 0 and "aligned" in lib.last_error()
+    q = lib.query
+    need = q("srpde_physics_loss_div_workspace_size", 2, 40)
+    assert fwd(ws_bytes=need - 1) < 0 and "workspace too small" in lib.last_error()
+    one = q("srpde_physics_loss_div_workspace_size", 1, 40)
+    assert one > 0 and one % 8 == 0
+    sizes = [q("srpde_physics_loss_div_workspace_size", B, 40) for B in (1, 2, 3, 1024)]
+    assert sizes == sorted(sizes) and sizes[-1] <= 1024 * one
+    assert q("srpde_physics_loss_div_workspace_size", 4, 3) > 0 and q("srpde_physics_loss_div_workspace_size", 4, 64) > 0
+    for B, n in ((0, 40), (4, 2), (4, 65), (-1, 40)):
+        assert q("srpde_physics_loss_div_workspace_size", B, n) == 0
+
+
+# ---- Python keywords and the command line ------------------------------------------------------------------------
+def test_python_keyword_refusals_need_no_device():
+    from superresolution_for_pdes_amd import functional as F
+    from superresolution_for_pdes_amd import poisson as P
+    from superresolution_for_pdes_amd.tiled_inference import upscale_cascade, upscale_level
+    z = np.zeros((4, 4))
+    with pytest.raises(ValueError, match='face_mean belongs to form="divergence"'):
+        P.relax(z, z, z, 1, face_mean="arithmetic")
+    with pytest.raises(ValueError, match="unknown operator form"):
+        P.relax(z, z, z, 1, form="conservative")
+    with pytest.raises(ValueError, match="unknown face mean"):
+        P.relax(z, z, z, 1, form="divergence", face_mean="geometric")
+    with pytest.raises(ValueError, match="sweeps"):
+        P.relax(z, z, z, -1, form="divergence")
+    with pytest.raises(ValueError, match="omega"):
+        P.relax(z, z, z, 1, 1.5, form="divergence")
+    y = torch.zeros(1, 1, 4, 4)
+    x = torch.zeros(1, 3, 4, 4)
+    kind, stats = torch.zeros(1, dtype=torch.int32), torch.ones(6)
+    with pytest.raises(ValueError, match='face_mean belongs to form="divergence"'):
+        F.physics_loss_terms(y, y, x, kind, stats, 0.1, face_mean="arithmetic")
+    with pytest.raises(ValueError, match="unknown operator form"):
+        F.physics_mse_loss(y, y, x, kind, stats, 0.1, form="conservative")
+    with pytest.raises(ValueError, match="unknown face mean"):
+        F.PhysicsMSELoss(0.1, stats, form="divergence", face_mean="geometric")
+    with pytest.raises(ValueError, match='face_mean belongs to form="divergence"'):
+        F.PhysicsMSELoss(0.1, stats, face_mean="arithmetic")
+    with pytest.raises(RuntimeError, match="no CPU fallback"):          # accepted keywords reach the device check
+        F.physics_loss_terms(y, y, x, kind, stats, 0.1, form="divergence", face_mean="arithmetic")
+    crit = F.PhysicsMSELoss(0.1, stats, form="divergence", face_mean="arithmetic")
+    assert (crit.form, crit.face_mean) == ("divergence", "arithmetic")
+    assert (F.PhysicsMSELoss(0.1, stats).form, F.PhysicsMSELoss(0.1, stats).face_mean) == ("pointwise", "harmonic")
+    for fn in (upscale_level, upscale_cascade):
+        args = (None, z, z, z) if fn is upscale_level else (None, z, {}, {}, 8)
+        with pytest.raises(ValueError, match="polish_face_mean belongs"):
+            fn(*args, polish=1, polish_face_mean="arithmetic")
+        with pytest.raises(ValueError, match="unknown operator form"):
+            fn(*args, polish=1, polish_form="conservative")
+        with pytest.raises(ValueError, match="unknown face mean"):
+            fn(*args, polish=1, polish_form="divergence", polish_face_mean="geometric")
+
+
+DIV = ["--operator", "divergence", "--online", "2", "--online-theta", "0.5", "2.0"]
+
+
+@pytest.mark.parametrize("argv,word", [
+    (["--pde-div-weight", "0.01"], "--operator divergence"),
+    (["--online", "2", "--pde-div-weight", "0.01"], "--operator divergence"),
+    (DIV + ["--pde-div-weight", "0.01", "--pde-weight", "0.1"], "--pde-weight"),
+    (DIV + ["--pde-div-weight", "-1"], "--pde-div-weight"),
+    (DIV + ["--pde-weight", "0.1"], "--pde-div-weight"),               # the old refusal now names the new flag
+])
+def test_cli_refusals_need_no_device(argv, word, monkeypatch):
+    from superresolution_for_pdes_amd import train_enhanced as TE
+
+    def no_device(*a, **k):
+        raise AssertionError("device work before the argument checks")
+    monkeypatch.setattr(torch.cuda, "manual_seed", no_device)
+    with pytest.raises(SystemExit) as e:
+        TE.main(argv)
+    assert word in str(e.value)
+
+
+def test_cli_accepts_the_divergence_weight():
+    from superresolution_for_pdes_amd import train_enhanced as TE
+    args = TE.arg_parser().parse_args([])
+    assert args.pde_div_weight == 0.0
+    TE.check_operator_args(args)
+    args = TE.arg_parser().parse_args(DIV + ["--face-mean", "arithmetic", "--pde-div-weight", "0.01"])
+    assert args.pde_div_weight == 0.01 and args.pde_weight == 0.0
+    TE.check_operator_args(args)

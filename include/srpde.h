@@ -615,9 +615,10 @@ size_t srpde_pde_residual_metrics_workspace_size(int E, int n);
 int srpde_pde_residual_metrics(const void* u, int u_is_f32, const double* f, const double* theta, int E, int n,
                                double inv_h2, int interior_only, double* out, void* workspace, size_t ws_bytes,
                                hipStream_t stream);
-/* Weighted-Jacobi sweeps of theta * L u = f (csrc/relax.hip): the smoother that takes the grid-scale error out of a
- * field that is right at low frequencies (a cascade level's output).  u_in, f, theta, u_out [E][n][n] fp64.  One
- * sweep, every operation rounded once in this order (no contraction), from the previous sweep's u throughout:
+/* Weighted-Jacobi sweeps of theta * L u = f (csrc/relax.hip, relax_kernel<PointwiseOp>): the smoother that takes the
+ * grid-scale error out of a field that is right at low frequencies (a cascade level's output).  u_in, f, theta, u_out
+ * [E][n][n] fp64.  One sweep, every operation rounded once in this order (no contraction), from the previous sweep's u
+ * throughout:
  *     g  = f / (theta * inv_h2)
  *     s  = (u[y-1][x] + u[y+1][x]) + (u[y][x-1] + u[y][x+1])        a neighbour outside the grid is 0
  *     r  = (s - 4.0 * u) - g
@@ -634,10 +635,10 @@ size_t srpde_pde_relax_workspace_size(int E, int n, int sweeps);
 int srpde_pde_relax(const double* u_in, const double* f, const double* theta, double* u_out, int E, int n,
                     double inv_h2, int sweeps, double omega, int interior_only, void* workspace, size_t ws_bytes,
                     hipStream_t stream);
-/* Weighted-Jacobi sweeps of div(theta grad u) = f (csrc/relax_div.hip, ABI 19): the same smoother for the operator of
- * srpde_div_apply below (face coefficients cE, cW, cS, cN from face_mean 0 arithmetic / 1 harmonic, c = theta_a and
- * u_b = 0 towards the ghost ring; E is x + 1, S is y + 1).  One sweep, every operation rounded once in this order (no
- * contraction), from the previous sweep's u throughout:
+/* Weighted-Jacobi sweeps of div(theta grad u) = f (csrc/relax.hip, relax_kernel<DivOp>, ABI 19): the same kernel for
+ * the operator of srpde_div_apply below (face coefficients cE, cW, cS, cN from face_mean 0 arithmetic / 1 harmonic,
+ * c = theta_a and u_b = 0 towards the ghost ring; E is x + 1, S is y + 1).  One sweep, every operation rounded once in
+ * this order (no contraction), from the previous sweep's u throughout:
  *     once per node:  g = f / inv_h2
  *                     w = omega / ((cE + cW) + (cS + cN))
  *     per sweep:      a  = (cE*(uE - u) + cW*(uW - u)) + (cS*(uS - u) + cN*(uN - u))

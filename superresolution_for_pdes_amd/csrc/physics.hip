@@ -28,6 +28,7 @@
 // node -> thread -> workgroup assignment depends on the shape alone and there are no atomics: results are
 // bit-reproducible.
 #include "common.h"
+#include "div_stencil.h"
 #include "field_reduce.h"
 
 namespace srpde {
@@ -38,20 +39,56 @@ constexpr int kPhysMaxSpw = 2;            // samples per workgroup, LDS permitti
 constexpr int kPhysLdsBudget = 48 * 1024;
 constexpr int kPhysMinN = 3, kPhysMaxN = 64;
 
-// LDS floats per sample: the y and q halo tiles and the y - t plane
-inline size_t phys_lds_floats(int n) { return 2 * (size_t)(n + 2) * (n + 2) + (size_t)n * n; }
-inline int phys_spw(int n) {
-  const size_t per = phys_lds_floats(n) * sizeof(float);
+inline int phys_spw(size_t lds_floats) {
+  const size_t per = lds_floats * sizeof(float);
   return (int)std::max<size_t>(1, std::min<size_t>(kPhysMaxSpw, kPhysLdsBudget / per));
 }
-inline int phys_blocks(int B, int n) { return ceil_div(B, phys_spw(n)); }
+inline int phys_blocks(int B, size_t lds_floats) { return ceil_div(B, phys_spw(lds_floats)); }
 
 // (a + b) + (c + d) - 4 e on a halo tile around p
 __device__ __forceinline__ float stencil5(const float* p, int pitch) {
   return fmaf(-4.f, p[0], (p[-pitch] + p[pitch]) + (p[-1] + p[1]));
 }
 
-// grid: ceil(B / spw) workgroups; dynamic LDS: spw * phys_lds_floats(n) floats
+// ---- the two operators of the loss term ----------------------------------------------------------------------------
+// physics_loss_kernel<Op> owns the sample-to-workgroup mapping, the two passes over the nodes, the count of M, the fp64
+// accumulation, the gradient's scale constants and the partials.  What an operator does differently -- its LDS layout,
+// what it stages beside y, its residual at a node, what the node leaves in LDS for the gradient pass and its adjoint
+// stencil -- stands in the kernel under `if constexpr (Op::kDiv)`, each operator's statements in the order and with the
+// index forms its own kernel had, so that each instance compiles as that kernel did.
+//
+// theta * L (the header's formulas): q = m r theta, the adjoint is A on q.  LDS per sample: the y and q halo tiles and
+// the y - t plane.
+struct PointwiseLoss {
+  static constexpr bool kDiv = false;
+  static size_t lds_floats(int n) { return 2 * (size_t)(n + 2) * (n + 2) + (size_t)n * n; }
+};
+
+// div(theta grad u) - f: D_theta (sigma_u y + mu_u) = sigma_u a(y) + mu_u D_theta 1, with a(y) the face sum of
+// div_stencil.h on y (zero halo, ghost coefficient theta_a) and D_theta 1 = -(sum of the node's ghost-face
+// coefficients) = -k_miss theta, because the interior faces cancel: the same split as above, nothing of the size of
+// mu_u / h^2 enters an fp32 sum.
+//     r  = ((sigma_u a(y) + mu_u (-k_miss theta)) ih2 - f) / sigma_f
+//     dy = 2 (y - t) / N + weight (2 sigma_u / (M sigma_f)) ih2 Dt(q),   q = m r
+// Dt is the face operator with the ghost faces on the diagonal; it is symmetric, so the adjoint is the same face sum
+// on q (q, not q theta: theta sits in the faces).  LDS per sample: the y, theta and q halo tiles, 3 (n + 2)^2 floats
+// -- 51 KiB at n = 64, one sample per workgroup there, inside the 64 KiB that a kernel gets without raising its limit.
+// The y - t plane is not kept: the gradient pass reads t again (the workgroup's own lines, just read).  theta's halo
+// is 1: every face towards it is replaced by the ghost rule, so the mean never divides by 0.
+template <bool HARM>
+struct DivLoss {
+  static constexpr bool kDiv = true, kHarm = HARM;
+  static size_t lds_floats(int n) { return 3 * (size_t)(n + 2) * (n + 2); }
+};
+
+// the face sum of node (i, j) on halo tiles around v and th
+template <bool HARM>
+__device__ __forceinline__ float loss_face_sum(const float* v, const float* th, int pitch, int i, int j, int n) {
+  return face_sum<HARM>(v, th, pitch, j > 0, j < n - 1, i > 0, i < n - 1);
+}
+
+// grid: ceil(B / spw) workgroups; dynamic LDS: spw * Op::lds_floats(n) floats
+template <class Op>
 __global__ __launch_bounds__(kPhysThreads) void physics_loss_kernel(
     const float* __restrict__ y, const float* __restrict__ t, const float* __restrict__ x,
     const int* __restrict__ kind, const float* __restrict__ stats, int B, int n, int spw, float weight, float ih2_std,
@@ -64,19 +101,33 @@ __global__ __launch_bounds__(kPhysThreads) void physics_loss_kernel(
   const int b0 = blockIdx.x * spw;
   const int ns = min(spw, B - b0);            // samples of this workgroup (>= 1)
   float* ytile = lds;                         // [spw][P][P]
-  float* qtile = lds + (size_t)spw * T2;      // [spw][P][P]
-  float* dpl = qtile + (size_t)spw * T2;      // [spw][n][n]
+  float* tile2 = lds + (size_t)spw * T2;      // [spw][P][P]: q (pointwise), theta (divergence)
+  float* tile3 = tile2 + (size_t)spw * T2;    // [spw][n][n] y - t (pointwise), [spw][P][P] q (divergence)
+  float* ttile = tile2;
+  float* qtile = Op::kDiv ? tile3 : tile2;
+  float* dpl = tile3;
 
   const float mu_u = stats[0], sg_u = stats[1], mu_f = stats[2], sg_f = stats[3], mu_t = stats[4], sg_t = stats[5];
 
-  // stage y with its zero halo; zero q's halo
+  // stage y with its zero halo (divergence: and theta with a halo of 1); zero q's halo
   for (int k = tid; k < ns * T2; k += kPhysThreads) {
     const int s = k / T2, rem = k - s * T2;
     const int ii = rem / P, jj = rem - ii * P;
     const bool inner = ii >= 1 && ii <= n && jj >= 1 && jj <= n;
-    float v = 0.f;
-    if (inner) v = y[(long long)(b0 + s) * nn + (ii - 1) * n + (jj - 1)];
-    ytile[k] = v;
+    if constexpr (Op::kDiv) {
+      float v = 0.f, th = 1.f;
+      if (inner) {
+        const long long at = (long long)(ii - 1) * n + (jj - 1);
+        v = y[(long long)(b0 + s) * nn + at];
+        th = fmaf(sg_t, x[((long long)(b0 + s) * 3 + 1) * nn + at], mu_t);
+      }
+      ytile[k] = v;
+      ttile[k] = th;
+    } else {
+      float v = 0.f;
+      if (inner) v = y[(long long)(b0 + s) * nn + (ii - 1) * n + (jj - 1)];
+      ytile[k] = v;
+    }
     if (!inner) qtile[k] = 0.f;
   }
   // M = sum of the masks of the whole batch, from the kinds (only the gradient's scale needs it here)
@@ -93,29 +144,48 @@ __global__ __launch_bounds__(kPhysThreads) void physics_loss_kernel(
     const int s = k / nn, rem = k - s * nn;
     const int i = rem / n, j = rem - i * n;
     const long long b = b0 + s;
-    const long long g = b * nn + rem;
-    const float* xb = x + b * 3 * nn + rem;
-    const float th = fmaf(sg_t, xb[nn], mu_t);
-    const float f = fmaf(sg_f, xb[2 * nn], mu_f);
-    const float tv = t[g];
-    const int kd = kind[b];
-    const float ih2 = kd ? ih2_sub : ih2_std;
-    const float* yc = ytile + s * T2 + (i + 1) * P + (j + 1);
-    const float ay = stencil5(yc, P);
-    const int edge_i = (i == 0) + (i == n - 1), edge_j = (j == 0) + (j == n - 1);
-    const float a1 = -(float)(edge_i + edge_j);
-    const bool m = !kd || (edge_i + edge_j == 0);
-    const float lap = fmaf(sg_u, ay, mu_u * a1);
-    const float r = (th * lap * ih2 - f) / sg_f;
-    const float d = yc[0] - tv;
+    float r, d, qv;                           // the residual, y - t and what goes into q if the node is counted
+    bool m;
+    if constexpr (Op::kDiv) {
+      const int c = s * T2 + (i + 1) * P + (j + 1);
+      const float f = fmaf(sg_f, x[(b * 3 + 2) * nn + rem], mu_f);
+      const float tv = t[b * nn + rem];
+      const int kd = kind[b];
+      const float ih2 = kd ? ih2_sub : ih2_std;
+      const float ay = loss_face_sum<Op::kHarm>(ytile + c, ttile + c, P, i, j, n);
+      const int miss = (i == 0) + (i == n - 1) + (j == 0) + (j == n - 1);
+      m = !kd || miss == 0;
+      const float d1 = -(float)miss * ttile[c];
+      const float lap = fmaf(sg_u, ay, mu_u * d1);
+      r = (lap * ih2 - f) / sg_f;
+      d = ytile[c] - tv;
+      qv = r;
+    } else {
+      const long long g = b * nn + rem;
+      const float* xb = x + b * 3 * nn + rem;
+      const float th = fmaf(sg_t, xb[nn], mu_t);
+      const float f = fmaf(sg_f, xb[2 * nn], mu_f);
+      const float tv = t[g];
+      const int kd = kind[b];
+      const float ih2 = kd ? ih2_sub : ih2_std;
+      const float* yc = ytile + s * T2 + (i + 1) * P + (j + 1);
+      const float ay = stencil5(yc, P);
+      const int edge_i = (i == 0) + (i == n - 1), edge_j = (j == 0) + (j == n - 1);
+      const float a1 = -(float)(edge_i + edge_j);
+      m = !kd || (edge_i + edge_j == 0);
+      const float lap = fmaf(sg_u, ay, mu_u * a1);
+      r = (th * lap * ih2 - f) / sg_f;
+      d = yc[0] - tv;
+      qv = r * th;
+    }
     sse += (double)(d * d);
     if (m) {
       spr += (double)r * (double)r;
       sm += 1.0;
     }
     if (dy != nullptr) {
-      qtile[s * T2 + (i + 1) * P + (j + 1)] = m ? r * th : 0.f;
-      dpl[k] = d;
+      qtile[s * T2 + (i + 1) * P + (j + 1)] = m ? qv : 0.f;
+      if constexpr (!Op::kDiv) dpl[k] = d;
     }
   }
 
@@ -129,137 +199,15 @@ __global__ __launch_bounds__(kPhysThreads) void physics_loss_kernel(
       const int s = k / nn, rem = k - s * nn;
       const int i = rem / n, j = rem - i * n;
       const long long b = b0 + s;
-      const float aq = stencil5(qtile + s * T2 + (i + 1) * P + (j + 1), P);
-      dy[b * nn + rem] = fmaf(kind[b] ? c_sub : c_std, aq, c_mse * dpl[k]);
-    }
-  }
-
-  sse = block_sum(sse, sh);
-  spr = block_sum(spr, sh);
-  sm = block_sum(sm, sh);
-  if (tid == 0) {
-    double* o = part + (long long)blockIdx.x * 3;
-    o[0] = sse;
-    o[1] = spr;
-    o[2] = sm;
-  }
-}
-
-// ---- the divergence-form residual  div(theta grad u) - f  as the loss term ---------------------------------------
-// D_theta (sigma_u y + mu_u) = sigma_u a(y) + mu_u D_theta 1, with a(y) the face sum on y (zero halo, ghost
-// coefficient theta_a) and D_theta 1 = -(sum of the node's ghost-face coefficients) = -k_miss theta, because the
-// interior faces cancel: the same split as above, nothing of the size of mu_u / h^2 enters an fp32 sum.
-//     r  = ((sigma_u a(y) + mu_u (-k_miss theta)) ih2 - f) / sigma_f
-//     dy = 2 (y - t) / N + weight (2 sigma_u / (M sigma_f)) ih2 Dt(q),   q = m r
-// Dt is the face operator with the ghost faces on the diagonal; it is symmetric, so the adjoint is the same face sum
-// on q (q, not q theta: theta sits in the faces).  LDS per sample: the y, theta and q halo tiles, 3 (n + 2)^2 floats
-// -- 51 KiB at n = 64, one sample per workgroup there, inside the 64 KiB that a kernel gets without raising its limit.
-// The y - t plane of the pointwise kernel is not kept: the gradient pass reads t again (the workgroup's own lines, just
-// read).  theta's halo is 1: every face towards it is replaced by the ghost rule, so the mean never divides by 0.
-inline size_t phys_div_lds_floats(int n) { return 3 * (size_t)(n + 2) * (n + 2); }
-inline int phys_div_spw(int n) {
-  const size_t per = phys_div_lds_floats(n) * sizeof(float);
-  return (int)std::max<size_t>(1, std::min<size_t>(kPhysMaxSpw, kPhysLdsBudget / per));
-}
-inline int phys_div_blocks(int B, int n) { return ceil_div(B, phys_div_spw(n)); }
-
-template <bool HARM>
-__device__ __forceinline__ float face_mean_f(float ta, float tb) {
-  return HARM ? (2.f * (ta * tb)) / (ta + tb) : 0.5f * (ta + tb);
-}
-
-// (cE (vE - v) + cW (vW - v)) + (cS (vS - v) + cN (vN - v)) on halo tiles around v and th; i, j the node's row / column
-template <bool HARM>
-__device__ __forceinline__ float face_sum(const float* v, const float* th, int pitch, int i, int j, int n) {
-  const float ta = th[0], vc = v[0];
-  const float cE = j < n - 1 ? face_mean_f<HARM>(ta, th[1]) : ta;
-  const float cW = j > 0 ? face_mean_f<HARM>(ta, th[-1]) : ta;
-  const float cS = i < n - 1 ? face_mean_f<HARM>(ta, th[pitch]) : ta;
-  const float cN = i > 0 ? face_mean_f<HARM>(ta, th[-pitch]) : ta;
-  return (cE * (v[1] - vc) + cW * (v[-1] - vc)) + (cS * (v[pitch] - vc) + cN * (v[-pitch] - vc));
-}
-
-// grid: ceil(B / spw) workgroups; dynamic LDS: spw * phys_div_lds_floats(n) floats
-template <bool HARM>
-__global__ __launch_bounds__(kPhysThreads) void physics_loss_div_kernel(
-    const float* __restrict__ y, const float* __restrict__ t, const float* __restrict__ x,
-    const int* __restrict__ kind, const float* __restrict__ stats, int B, int n, int spw, float weight, float ih2_std,
-    float ih2_sub, float* __restrict__ dy, double* __restrict__ part) {
-  extern __shared__ float lds[];
-  __shared__ double sh[4];
-  __shared__ long long shM;
-  const int tid = threadIdx.x;
-  const int P = n + 2, T2 = P * P, nn = n * n;
-  const int b0 = blockIdx.x * spw;
-  const int ns = min(spw, B - b0);            // samples of this workgroup (>= 1)
-  float* ytile = lds;                         // [spw][P][P]
-  float* ttile = lds + (size_t)spw * T2;      // [spw][P][P] theta
-  float* qtile = ttile + (size_t)spw * T2;    // [spw][P][P]
-
-  const float mu_u = stats[0], sg_u = stats[1], mu_f = stats[2], sg_f = stats[3], mu_t = stats[4], sg_t = stats[5];
-
-  // stage y with its zero halo and theta with a halo of 1; zero q's halo
-  for (int k = tid; k < ns * T2; k += kPhysThreads) {
-    const int s = k / T2, rem = k - s * T2;
-    const int ii = rem / P, jj = rem - ii * P;
-    const bool inner = ii >= 1 && ii <= n && jj >= 1 && jj <= n;
-    float v = 0.f, th = 1.f;
-    if (inner) {
-      const long long at = (long long)(ii - 1) * n + (jj - 1);
-      v = y[(long long)(b0 + s) * nn + at];
-      th = fmaf(sg_t, x[((long long)(b0 + s) * 3 + 1) * nn + at], mu_t);
-    }
-    ytile[k] = v;
-    ttile[k] = th;
-    if (!inner) qtile[k] = 0.f;
-  }
-  if (dy != nullptr) {
-    long long cnt = 0;
-    for (int b = tid; b < B; b += kPhysThreads) cnt += kind[b] ? (long long)(n - 2) * (n - 2) : (long long)nn;
-    const double tot = block_sum((double)cnt, sh);   // exact: integers far below 2^53
-    if (tid == 0) shM = (long long)tot;
-  }
-  __syncthreads();
-
-  double sse = 0.0, spr = 0.0, sm = 0.0;
-  for (int k = tid; k < ns * nn; k += kPhysThreads) {
-    const int s = k / nn, rem = k - s * nn;
-    const int i = rem / n, j = rem - i * n;
-    const long long b = b0 + s;
-    const int c = s * T2 + (i + 1) * P + (j + 1);
-    const float f = fmaf(sg_f, x[(b * 3 + 2) * nn + rem], mu_f);
-    const float tv = t[b * nn + rem];
-    const int kd = kind[b];
-    const float ih2 = kd ? ih2_sub : ih2_std;
-    const float ay = face_sum<HARM>(ytile + c, ttile + c, P, i, j, n);
-    const int miss = (i == 0) + (i == n - 1) + (j == 0) + (j == n - 1);
-    const bool m = !kd || miss == 0;
-    const float d1 = -(float)miss * ttile[c];
-    const float lap = fmaf(sg_u, ay, mu_u * d1);
-    const float r = (lap * ih2 - f) / sg_f;
-    const float d = ytile[c] - tv;
-    sse += (double)(d * d);
-    if (m) {
-      spr += (double)r * (double)r;
-      sm += 1.0;
-    }
-    if (dy != nullptr) qtile[c] = m ? r : 0.f;
-  }
-
-  if (dy != nullptr) {
-    __syncthreads();
-    const double M = (double)shM;
-    const double base = 2.0 * (double)weight * (double)sg_u / (M * (double)sg_f);
-    const float c_std = (float)(base * (double)ih2_std), c_sub = (float)(base * (double)ih2_sub);
-    const float c_mse = (float)(2.0 / ((double)B * (double)nn));
-    for (int k = tid; k < ns * nn; k += kPhysThreads) {
-      const int s = k / nn, rem = k - s * nn;
-      const int i = rem / n, j = rem - i * n;
-      const long long b = b0 + s;
-      const int c = s * T2 + (i + 1) * P + (j + 1);
-      const float aq = face_sum<HARM>(qtile + c, ttile + c, P, i, j, n);
-      const float d = ytile[c] - t[b * nn + rem];
-      dy[b * nn + rem] = fmaf(kind[b] ? c_sub : c_std, aq, c_mse * d);
+      if constexpr (Op::kDiv) {
+        const int c = s * T2 + (i + 1) * P + (j + 1);
+        const float aq = loss_face_sum<Op::kHarm>(qtile + c, ttile + c, P, i, j, n);
+        const float d = ytile[c] - t[b * nn + rem];
+        dy[b * nn + rem] = fmaf(kind[b] ? c_sub : c_std, aq, c_mse * d);
+      } else {
+        const float aq = stencil5(qtile + s * T2 + (i + 1) * P + (j + 1), P);
+        dy[b * nn + rem] = fmaf(kind[b] ? c_sub : c_std, aq, c_mse * dpl[k]);
+      }
     }
   }
 
@@ -363,68 +311,62 @@ __global__ __launch_bounds__(64) void pde_residual_final_kernel(const double* __
 
 using namespace srpde;
 
+using PhysLossKernel = decltype(&srpde::physics_loss_kernel<srpde::PointwiseLoss>);
+
+static size_t phys_workspace_size(int B, int n, size_t lds_floats) {
+  if (B <= 0 || n < kPhysMinN || n > kPhysMaxN) return 0;
+  return (size_t)phys_blocks(B, lds_floats) * 3 * sizeof(double);
+}
+
+// the checks and the two launches of both loss entries; name: the entry's, kernel and lds_floats: its operator's,
+// face_mean: the divergence entry's argument (checked in its place among the others), null for the pointwise entry
+static int phys_loss_launch(const char* name, PhysLossKernel kernel, size_t lds_floats, const int* face_mean,
+                            const float* y, const float* t, const float* x, const int* kind, const float* stats, int B,
+                            int n, float weight, float inv_h2_std, float inv_h2_sub, float* loss, float* dy_unit,
+                            void* workspace, size_t ws_bytes, hipStream_t stream) {
+  SRPDE_CHECK_ARG(y && t && x && kind && stats && loss && workspace, "%s: null pointer", name);
+  if (B <= 0 || n < kPhysMinN || n > kPhysMaxN)
+    SRPDE_FAIL(kErrShape, "%s: bad shape B=%d n=%d (B >= 1, %d <= n <= %d)", name, B, n, kPhysMinN, kPhysMaxN);
+  if (face_mean && *face_mean != 0 && *face_mean != 1)
+    SRPDE_FAIL(kErrArg, "%s: face_mean=%d (0 arithmetic, 1 harmonic)", name, *face_mean);
+  if (reinterpret_cast<uintptr_t>(workspace) & 7u) SRPDE_FAIL(kErrAlign, "%s: workspace not 8-byte aligned", name);
+  if (ws_bytes < phys_workspace_size(B, n, lds_floats)) SRPDE_FAIL(kErrWorkspace, "%s: workspace too small", name);
+  const int spw = phys_spw(lds_floats), nb = phys_blocks(B, lds_floats);
+  double* part = static_cast<double*>(workspace);
+  hipLaunchKernelGGL(kernel, dim3(nb), dim3(kPhysThreads), (size_t)spw * lds_floats * sizeof(float), stream, y, t, x,
+                     kind, stats, B, n, spw, weight, inv_h2_std, inv_h2_sub, dy_unit, part);
+  SRPDE_LAUNCH_CHECK(name);
+  hipLaunchKernelGGL(physics_loss_final_kernel, dim3(1), dim3(kPhysThreads), 0, stream, part, nb,
+                     (long long)B * n * n, weight, loss);
+  SRPDE_LAUNCH_CHECK(name);
+  return 0;
+}
+
 extern "C" {
 
 size_t srpde_physics_loss_workspace_size(int B, int n) {
-  if (B <= 0 || n < kPhysMinN || n > kPhysMaxN) return 0;
-  return (size_t)phys_blocks(B, n) * 3 * sizeof(double);
+  return phys_workspace_size(B, n, PointwiseLoss::lds_floats(n));
+}
+
+size_t srpde_physics_loss_div_workspace_size(int B, int n) {
+  return phys_workspace_size(B, n, DivLoss<false>::lds_floats(n));
 }
 
 int srpde_physics_loss_fwd(const float* y, const float* t, const float* x, const int* kind, const float* stats, int B,
                            int n, float weight, float inv_h2_std, float inv_h2_sub, float* loss, float* dy_unit,
                            void* workspace, size_t ws_bytes, hipStream_t stream) {
-  SRPDE_CHECK_ARG(y && t && x && kind && stats && loss && workspace, "srpde_physics_loss_fwd: null pointer");
-  if (B <= 0 || n < kPhysMinN || n > kPhysMaxN)
-    SRPDE_FAIL(kErrShape, "srpde_physics_loss_fwd: bad shape B=%d n=%d (B >= 1, %d <= n <= %d)", B, n, kPhysMinN,
-               kPhysMaxN);
-  if (reinterpret_cast<uintptr_t>(workspace) & 7u)
-    SRPDE_FAIL(kErrAlign, "srpde_physics_loss_fwd: workspace not 8-byte aligned");
-  if (ws_bytes < srpde_physics_loss_workspace_size(B, n))
-    SRPDE_FAIL(kErrWorkspace, "srpde_physics_loss_fwd: workspace too small");
-  const int spw = phys_spw(n), nb = phys_blocks(B, n);
-  const size_t lds = (size_t)spw * phys_lds_floats(n) * sizeof(float);
-  double* part = static_cast<double*>(workspace);
-  hipLaunchKernelGGL(physics_loss_kernel, dim3(nb), dim3(kPhysThreads), lds, stream, y, t, x, kind, stats, B, n, spw,
-                     weight, inv_h2_std, inv_h2_sub, dy_unit, part);
-  SRPDE_LAUNCH_CHECK("srpde_physics_loss_fwd");
-  hipLaunchKernelGGL(physics_loss_final_kernel, dim3(1), dim3(kPhysThreads), 0, stream, part, nb,
-                     (long long)B * n * n, weight, loss);
-  SRPDE_LAUNCH_CHECK("srpde_physics_loss_fwd");
-  return 0;
-}
-
-size_t srpde_physics_loss_div_workspace_size(int B, int n) {
-  if (B <= 0 || n < kPhysMinN || n > kPhysMaxN) return 0;
-  return (size_t)phys_div_blocks(B, n) * 3 * sizeof(double);
+  return phys_loss_launch("srpde_physics_loss_fwd", physics_loss_kernel<PointwiseLoss>, PointwiseLoss::lds_floats(n),
+                          nullptr, y, t, x, kind, stats, B, n, weight, inv_h2_std, inv_h2_sub, loss, dy_unit, workspace,
+                          ws_bytes, stream);
 }
 
 int srpde_physics_loss_div_fwd(const float* y, const float* t, const float* x, const int* kind, const float* stats,
                                int B, int n, int face_mean, float weight, float inv_h2_std, float inv_h2_sub,
                                float* loss, float* dy_unit, void* workspace, size_t ws_bytes, hipStream_t stream) {
-  SRPDE_CHECK_ARG(y && t && x && kind && stats && loss && workspace, "srpde_physics_loss_div_fwd: null pointer");
-  if (B <= 0 || n < kPhysMinN || n > kPhysMaxN)
-    SRPDE_FAIL(kErrShape, "srpde_physics_loss_div_fwd: bad shape B=%d n=%d (B >= 1, %d <= n <= %d)", B, n, kPhysMinN,
-               kPhysMaxN);
-  if (face_mean != 0 && face_mean != 1)
-    SRPDE_FAIL(kErrArg, "srpde_physics_loss_div_fwd: face_mean=%d (0 arithmetic, 1 harmonic)", face_mean);
-  if (reinterpret_cast<uintptr_t>(workspace) & 7u)
-    SRPDE_FAIL(kErrAlign, "srpde_physics_loss_div_fwd: workspace not 8-byte aligned");
-  if (ws_bytes < srpde_physics_loss_div_workspace_size(B, n))
-    SRPDE_FAIL(kErrWorkspace, "srpde_physics_loss_div_fwd: workspace too small");
-  const int spw = phys_div_spw(n), nb = phys_div_blocks(B, n);
-  const size_t lds = (size_t)spw * phys_div_lds_floats(n) * sizeof(float);
-  double* part = static_cast<double*>(workspace);
-  if (face_mean)
-    hipLaunchKernelGGL(physics_loss_div_kernel<true>, dim3(nb), dim3(kPhysThreads), lds, stream, y, t, x, kind, stats,
-                       B, n, spw, weight, inv_h2_std, inv_h2_sub, dy_unit, part);
-  else
-    hipLaunchKernelGGL(physics_loss_div_kernel<false>, dim3(nb), dim3(kPhysThreads), lds, stream, y, t, x, kind, stats,
-                       B, n, spw, weight, inv_h2_std, inv_h2_sub, dy_unit, part);
-  SRPDE_LAUNCH_CHECK("srpde_physics_loss_div_fwd");
-  hipLaunchKernelGGL(physics_loss_final_kernel, dim3(1), dim3(kPhysThreads), 0, stream, part, nb,
-                     (long long)B * n * n, weight, loss);
-  SRPDE_LAUNCH_CHECK("srpde_physics_loss_div_fwd");
-  return 0;
+  return phys_loss_launch("srpde_physics_loss_div_fwd",
+                          face_mean == 1 ? physics_loss_kernel<DivLoss<true>> : physics_loss_kernel<DivLoss<false>>,
+                          DivLoss<false>::lds_floats(n), &face_mean, y, t, x, kind, stats, B, n, weight, inv_h2_std,
+                          inv_h2_sub, loss, dy_unit, workspace, ws_bytes, stream);
 }
 
 int srpde_physics_loss_bwd(const float* dy_unit, long long count, const float* gout, float* dy, hipStream_t stream) {

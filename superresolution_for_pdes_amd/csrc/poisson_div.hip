@@ -42,6 +42,7 @@
 #include "poisson_dst.h"
 
 #pragma clang fp contract(off)
+#include "div_stencil.h"                   // after the pragma: its functions take the mode of this file
 
 namespace srpde {
 namespace {
@@ -100,11 +101,6 @@ DivCG carve(void* ws, int B, int n) {
   return g;
 }
 
-template <bool HARM>
-__device__ __forceinline__ double face_mean(double ta, double tb) {
-  return HARM ? (2.0 * (ta * tb)) / (ta + tb) : 0.5 * (ta + tb);
-}
-
 // block_sum and resum (field_reduce.h) give the same bits in every thread.  red, their 4 doubles of LDS, is used for
 // nothing else in these kernels, and each call's first barrier comes before its write, so back-to-back calls are safe.
 
@@ -159,13 +155,8 @@ __global__ __launch_bounds__(kDivThreads) void div_apply_kernel(const double* __
       const int ly = ly0 + r, gy = y0 + ly - 1;
       if (gy < n) {
         const int c = ly * kDivLX + lx;
-        const double uc = us[c], ta = ts[c];
-        const double cE = gx + 1 < n ? face_mean<HARM>(ta, ts[c + 1]) : ta;
-        const double cW = gx > 0 ? face_mean<HARM>(ta, ts[c - 1]) : ta;
-        const double cS = gy + 1 < n ? face_mean<HARM>(ta, ts[c + kDivLX]) : ta;
-        const double cN = gy > 0 ? face_mean<HARM>(ta, ts[c - kDivLX]) : ta;
-        const double yv = ((cE * (us[c + 1] - uc) + cW * (us[c - 1] - uc)) +
-                           (cS * (us[c + kDivLX] - uc) + cN * (us[c - kDivLX] - uc))) * inv_h2;
+        const double uc = us[c];
+        const double yv = face_sum<HARM>(us + c, ts + c, kDivLX, gx > 0, gx + 1 < n, gy > 0, gy + 1 < n) * inv_h2;
         const long long at = base + (long long)gy * n + gx;
         y[at] = yv;
         if (PCG) {

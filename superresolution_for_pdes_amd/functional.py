@@ -9,6 +9,7 @@ import torch
 import torch.nn as nn
 
 from . import hipops as H
+from .poisson import face_mean_arg
 
 
 class _MSEFn(torch.autograd.Function):
@@ -63,22 +64,10 @@ class _PhysicsMSEFn(torch.autograd.Function):
         return dy, None, None, None, None, None, None, None, None
 
 
-def _form_arg(form, face_mean):
-    """The face_mean argument of hipops.physics_loss_fwd: None for the pointwise residual, 0 / 1 for the divergence
-    form's arithmetic / harmonic mean."""
-    from .poisson import check_face_mean, check_form
-    mean = check_face_mean(face_mean)
-    if check_form(form) == "divergence":
-        return mean
-    if face_mean != "harmonic":
-        raise ValueError('face_mean belongs to form="divergence"')
-    return None
-
-
 def physics_loss_terms(y, t, x, kind, stats, weight, inv_h2=DEFAULT_INV_H2, form="pointwise", face_mean="harmonic"):
     """The device tensor (mse + weight * pde, mse, pde) behind ``physics_mse_loss``; differentiable through its
     first element only (the other two are reports of the same pass)."""
-    mean = _form_arg(form, face_mean)
+    mean = face_mean_arg(form, face_mean)
     if y.shape != t.shape:
         raise ValueError(f"physics_mse_loss: shape mismatch {tuple(y.shape)} vs {tuple(t.shape)}")
     if y.dim() != 4 or y.shape[1] != 1 or y.shape[2] != y.shape[3]:
@@ -128,7 +117,7 @@ class PhysicsMSELoss(nn.Module):
         super().__init__()
         if weight < 0:
             raise ValueError("PhysicsMSELoss: weight >= 0")
-        _form_arg(form, face_mean)
+        face_mean_arg(form, face_mean)
         self.form, self.face_mean = form, face_mean
         self.weight = float(weight)
         self.inv_h2 = (float(inv_h2[0]), float(inv_h2[1]))

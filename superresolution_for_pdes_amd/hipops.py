@@ -1270,7 +1270,7 @@ def pde_residual_metrics(u, f, theta, inv_h2, interior_only=False):
     return out
 
 
-RELAX_TILE = 48   # the output tile of pde_relax_kernel (csrc/relax.hip kRelaxT): tests place their sizes around it
+RELAX_TILE = 48   # the output tile of relax_kernel (csrc/relax.hip kRelaxT): tests place their sizes around it
 
 
 def pde_relax_sweeps_per_launch():
@@ -1278,38 +1278,29 @@ def pde_relax_sweeps_per_launch():
     return int(query("srpde_pde_relax_sweeps_per_launch"))
 
 
-def pde_relax(u, f, theta, inv_h2, sweeps, omega=0.8, interior_only=False):
-    """srpde_pde_relax: ``sweeps`` weighted-Jacobi sweeps of theta * A u * inv_h2 = f on fp64 fields [E, n, n] -> a new
-    [E, n, n] fp64 tensor (the inputs are left alone); over all nodes against a zero ghost ring, or with the ring of
-    the fields held (``interior_only``)."""
+def pde_relax(u, f, theta, inv_h2, sweeps, omega=0.8, interior_only=False, face_mean=None):
+    """``sweeps`` weighted-Jacobi sweeps on fp64 fields [E, n, n] -> a new [E, n, n] fp64 tensor (the inputs are left
+    alone); over all nodes against a zero ghost ring, or with the ring of the fields held (``interior_only``).
+    ``face_mean`` None: srpde_pde_relax, the sweeps of theta * A u * inv_h2 = f; 0 arithmetic / 1 harmonic:
+    srpde_div_relax, the sweeps of div(theta grad u) * inv_h2 = f with that mean on the faces."""
     _fields("pde_relax", torch.float64, u, f, theta)
     if f.dim() != 3 or f.shape[1] != f.shape[2] or u.shape != f.shape or theta.shape != f.shape:
         raise ValueError("pde_relax: u, f and theta must share one [E, n, n] shape")
     E, n, _ = f.shape
     sweeps = int(sweeps)
+    div = face_mean is not None
     out = torch.empty_like(u)
-    nbytes = int(query("srpde_pde_relax_workspace_size", E, n, sweeps))
+    nbytes = int(query("srpde_div_relax_workspace_size" if div else "srpde_pde_relax_workspace_size", E, n, sweeps))
     ws = torch.empty(nbytes // 8, dtype=torch.float64, device=f.device) if nbytes else None
-    call("srpde_pde_relax", u.data_ptr(), f.data_ptr(), theta.data_ptr(), out.data_ptr(), E, n, float(inv_h2), sweeps,
-         float(omega), int(bool(interior_only)), _p(ws), nbytes, stream_ptr())
+    call("srpde_div_relax" if div else "srpde_pde_relax", u.data_ptr(), f.data_ptr(), theta.data_ptr(), out.data_ptr(),
+         E, n, *((int(face_mean),) if div else ()), float(inv_h2), sweeps, float(omega), int(bool(interior_only)),
+         _p(ws), nbytes, stream_ptr())
     return out
 
 
 def pde_relax_div(u, f, theta, inv_h2, sweeps, omega=0.8, interior_only=False, face_mean=1):
-    """srpde_div_relax: ``sweeps`` weighted-Jacobi sweeps of div(theta grad u) * inv_h2 = f on fp64 fields [E, n, n]
-    -> a new [E, n, n] fp64 tensor (the inputs are left alone); ``face_mean`` 0 arithmetic, 1 harmonic; over all nodes
-    against a zero ghost ring, or with the ring of the fields held (``interior_only``)."""
-    _fields("pde_relax_div", torch.float64, u, f, theta)
-    if f.dim() != 3 or f.shape[1] != f.shape[2] or u.shape != f.shape or theta.shape != f.shape:
-        raise ValueError("pde_relax_div: u, f and theta must share one [E, n, n] shape")
-    E, n, _ = f.shape
-    sweeps = int(sweeps)
-    out = torch.empty_like(u)
-    nbytes = int(query("srpde_div_relax_workspace_size", E, n, sweeps))
-    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=f.device) if nbytes else None
-    call("srpde_div_relax", u.data_ptr(), f.data_ptr(), theta.data_ptr(), out.data_ptr(), E, n, int(face_mean),
-         float(inv_h2), sweeps, float(omega), int(bool(interior_only)), _p(ws), nbytes, stream_ptr())
-    return out
+    """The earlier name of ``pde_relax(..., face_mean=0 / 1)``: code written against it before the two were merged."""
+    return pde_relax(u, f, theta, inv_h2, sweeps, omega, interior_only, int(face_mean))
 
 
 # ----------------------------------- optimizer -------------------------------------

@@ -144,6 +144,17 @@ def check_face_mean(face_mean: str) -> int:
     return FACE_MEANS.index(face_mean)
 
 
+def face_mean_arg(form: str, face_mean: str):
+    """The face_mean argument of hipops.pde_relax / hipops.physics_loss_fwd: None for the pointwise form (which takes
+    no mean: anything but the default is refused), 0 / 1 for the divergence form's arithmetic / harmonic mean."""
+    mean = check_face_mean(face_mean)
+    if check_form(form) == "divergence":
+        return mean
+    if face_mean != "harmonic":
+        raise ValueError('face_mean belongs to form="divergence"')
+    return None
+
+
 class NotConverged(RuntimeError):
     """solve_div left problems above their tolerance (maxit reached)."""
 
@@ -274,9 +285,7 @@ def relax(u, f, theta, sweeps: int, omega: float = 0.8, interior_only: bool = Fa
     u <- u + omega (D_theta u - f) / sum of the node's four face coefficients (srpde_div_relax; include/srpde.h states
     the rounding order); the same guarantee for 0 < omega <= 1.  ``face_mean`` belongs to that form."""
     from . import hipops as H
-    mean = check_face_mean(face_mean)
-    if check_form(form) == "pointwise" and face_mean != "harmonic":
-        raise ValueError('face_mean belongs to form="divergence"')
+    mean = face_mean_arg(form, face_mean)
     if int(sweeps) < 0:
         raise ValueError(f"relax: sweeps must be >= 0, got {sweeps}")
     if not 0.0 < float(omega) <= 1.0:
@@ -288,9 +297,7 @@ def relax(u, f, theta, sweeps: int, omega: float = 0.8, interior_only: bool = Fa
         theta = theta.expand_as(f).contiguous()
     n = u.shape[-1]
     inv_h2 = float((n - 1) ** 2 if inv_h2 is None else inv_h2)
-    if form == "divergence":
-        return H.pde_relax_div(u, f, theta, inv_h2, int(sweeps), float(omega), interior_only, mean)
-    return H.pde_relax(u, f, theta, inv_h2, int(sweeps), float(omega), interior_only)
+    return H.pde_relax(u, f, theta, inv_h2, int(sweeps), float(omega), interior_only, mean)
 
 
 def solve_batched(f, theta, rtol: float = DEFAULT_RTOL, maxit: int = None, device="cuda",
@@ -309,14 +316,12 @@ def solve_batched(f, theta, rtol: float = DEFAULT_RTOL, maxit: int = None, devic
     leaves u unconverged).  ``check`` (default) reads the iteration counts back -- one host sync,
     only on that path, not under stream capture -- and raises GridBarrierAbort instead of returning
     such a u (every data-generation caller otherwise consumed it silently)."""
-    if check_form(form) == "divergence":
+    if face_mean_arg(form, face_mean) is not None:
         if method != "cg" or _start_aborted:
             raise ValueError('form="divergence" has one solver (solve_div): method and _start_aborted do not apply')
         u, iters, _ = solve_div(f, theta, face_mean=face_mean, rtol=rtol, maxit=maxit, check=check, return_info=True,
                                 device=device)
         return (u, iters) if return_iters else u
-    if face_mean != "harmonic":
-        raise ValueError('face_mean belongs to form="divergence"')
     if check_solver(method) == "dst":
         if rtol != DEFAULT_RTOL or maxit is not None or check is not True or _start_aborted:
             raise ValueError('method="dst" is a direct solve: rtol, maxit, check and _start_aborted do not apply')

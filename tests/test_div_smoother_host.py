@@ -1,6 +1,6 @@
-"""CPU: the divergence-form operator in the smoother and in the physics loss (csrc/relax_div.hip, csrc/physics.hip,
-ABI 19; poisson.relax(form="divergence"), functional.PhysicsMSELoss(form="divergence"), tiled_inference's
-``polish_form``, train_enhanced --pde-div-weight).
+"""CPU: the divergence-form operator in the smoother and in the physics loss (DivOp of csrc/relax.hip, DivLoss of
+csrc/physics.hip, ABI 19; poisson.relax(form="divergence"), functional.PhysicsMSELoss(form="divergence"),
+tiled_inference's ``polish_form``, train_enhanced --pde-div-weight).
 
 ``relax_div_np`` restates srpde_div_relax with one numpy pass per sweep in the header's order of operations, on the
 face coefficients of tests/poisson_div_ref.py; tests/test_gpu_relax_div.py compares the kernel with it by equality of
@@ -306,6 +306,22 @@ def test_physics_div_argument_checks_and_queries(lib):
 
 
 # ---- Python keywords and the command line ------------------------------------------------------------------------
+def test_face_mean_arg():
+    """poisson.face_mean_arg: what hipops.pde_relax / hipops.physics_loss_fwd take for (form, face_mean)."""
+    from superresolution_for_pdes_amd.poisson import face_mean_arg
+    assert face_mean_arg("pointwise", "harmonic") is None
+    assert face_mean_arg("divergence", "arithmetic") == 0
+    assert face_mean_arg("divergence", "harmonic") == 1
+    for mean in ("arithmetic", "harmonic"):
+        with pytest.raises(ValueError, match="unknown operator form"):
+            face_mean_arg("conservative", mean)
+    for form in ("pointwise", "divergence"):
+        with pytest.raises(ValueError, match="unknown face mean"):
+            face_mean_arg(form, "geometric")
+    with pytest.raises(ValueError, match='face_mean belongs to form="divergence"'):
+        face_mean_arg("pointwise", "arithmetic")
+
+
 def test_python_keyword_refusals_need_no_device():
     from superresolution_for_pdes_amd import functional as F
     from superresolution_for_pdes_amd import poisson as P

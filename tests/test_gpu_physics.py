@@ -1,5 +1,6 @@
-"""The PDE-residual loss term and metric on the GPU (csrc/physics.hip, ABI 15) against the fp64 restatements of
-tests/test_physics_host.py, evaluated on the CPU from the kernel's own fp32 inputs (gradient: torch autograd in fp64).
+"""The PDE-residual loss term and metric on the GPU (csrc/physics.hip, physics_loss_kernel<PointwiseLoss>, ABI 15)
+against the fp64 restatements of tests/test_physics_host.py, evaluated on the CPU from the kernel's own fp32 inputs
+(gradient: torch autograd in fp64).
 
 Tolerances are computed from the inputs.  With c = u_std * inv_h2 / f_std (the largest inv_h2 in the batch) and
 eps = 2^-23, the residual of one node is off by at most

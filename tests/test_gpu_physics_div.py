@@ -1,6 +1,6 @@
-"""The divergence-form residual as a loss term on the GPU (csrc/physics.hip physics_loss_div_kernel, ABI 19) against
-restatement_div of tests/test_div_smoother_host.py in fp64, evaluated on the CPU from the kernel's own fp32 inputs
-(gradient: torch autograd in fp64).
+"""The divergence-form residual as a loss term on the GPU (csrc/physics.hip physics_loss_kernel<DivLoss>, ABI 19)
+against restatement_div of tests/test_div_smoother_host.py in fp64, evaluated on the CPU from the kernel's own fp32
+inputs (gradient: torch autograd in fp64).
 
 Tolerances are computed from the inputs, as in tests/test_gpu_physics.py.  With c = u_std * inv_h2 / f_std (the largest
 inv_h2 in the batch) and eps = 2^-23, the residual of one node is off by at most

@@ -1,6 +1,7 @@
-"""The weighted-Jacobi smoother on the GPU (csrc/relax.hip, ABI 17; hipops.pde_relax, poisson.relax, the cascade's
-``polish``) against relax_np, the one-pass-per-sweep numpy restatement established in test_relax_host.py.  The kernel
-rounds every operation once in the header's order, so the comparison is by equality of bits, whatever the tiling.
+"""The weighted-Jacobi smoother on the GPU (relax_kernel<PointwiseOp> of csrc/relax.hip, ABI 17; hipops.pde_relax,
+poisson.relax, the cascade's ``polish``) against relax_np, the one-pass-per-sweep numpy restatement established in
+test_relax_host.py.  The kernel rounds every operation once in the header's order, so the comparison is by equality of
+bits, whatever the tiling.
 
 E = 3.  Sizes n: 1, 2, 3, 5 (grids smaller than the halo, the smallest with an interior), T - 1, T, T + 1 (one tile
 with and without a ragged edge, the first two-tile grid) and 2T + K + 3 (three tiles per axis: a tile with neighbours

@@ -1,7 +1,7 @@
-"""The divergence-form weighted-Jacobi smoother on the GPU (csrc/relax_div.hip, ABI 19; hipops.pde_relax_div,
-poisson.relax(form="divergence"), the cascade's ``polish_form``) against relax_div_np, the one-pass-per-sweep numpy
-restatement established in test_div_smoother_host.py.  The kernel rounds every operation once in the header's order, so
-the comparison is by equality of bits, whatever the tiling.
+"""The divergence-form weighted-Jacobi smoother on the GPU (relax_kernel<DivOp> of csrc/relax.hip, ABI 19;
+hipops.pde_relax(face_mean=...), poisson.relax(form="divergence"), the cascade's ``polish_form``) against
+relax_div_np, the one-pass-per-sweep numpy restatement established in test_div_smoother_host.py.  The kernel rounds
+every operation once in the header's order, so the comparison is by equality of bits, whatever the tiling.
 
 E = 3.  Sizes n: 1, 2, 3, 5 (grids smaller than the halo, the smallest with an interior), T - 1, T, T + 1 (one tile
 with and without a ragged edge, the first two-tile grid: a seam inside the halo) and 2T + K + 3 (three tiles per axis,
@@ -59,7 +59,7 @@ def test_bit_equal_to_the_numpy_restatement(n, mean, interior_only):
     code = D.MEANS.index(mean)
     if interior_only and n < 3:
         with pytest.raises(RuntimeError, match="srpde_div_relax"):      # refused, not computed
-            H.pde_relax_div(*(_dev(a) for a in _fields(n, n)), 1.0, 1, 0.8, True, code)
+            H.pde_relax(*(_dev(a) for a in _fields(n, n)), 1.0, 1, 0.8, True, face_mean=code)
         return
     K, _ = _KT()
     u, f, th = _fields(n, 100 + n)
@@ -69,7 +69,7 @@ def test_bit_equal_to_the_numpy_restatement(n, mean, interior_only):
     ring[1:-1, 1:-1] = False
     for omega in (0.8, 1.0):
         for sweeps in (0, 1, K - 1, K, K + 1, 2 * K + 1):
-            got = H.pde_relax_div(ud, fd, td, inv_h2, sweeps, omega, interior_only, code)
+            got = H.pde_relax(ud, fd, td, inv_h2, sweeps, omega, interior_only, face_mean=code)
             want = relax_div_np(u, f, th, mean, inv_h2, sweeps, omega, interior_only)
             assert got.shape == (E, n, n) and got.dtype == torch.float64
             assert _same_bits(got, want), (n, mean, interior_only, omega, sweeps,

@@ -1,4 +1,5 @@
-"""What polishing a cascade level with weighted-Jacobi sweeps does and costs (poisson.relax, csrc/relax.hip).
+"""What polishing a cascade level with weighted-Jacobi sweeps does and costs (poisson.relax,
+relax_kernel<PointwiseOp> of csrc/relax.hip).
 
     python tools/relax_bench.py [--model_path best_model.pth] [--out profiles/relax_bench.json]
 

@@ -1,5 +1,5 @@
-"""What the divergence-form smoother and loss term cost (poisson.relax(form="divergence"), csrc/relax_div.hip;
-functional.physics_mse_loss(form="divergence"), csrc/physics.hip).
+"""What the divergence-form smoother and loss term cost (poisson.relax(form="divergence"), relax_kernel<DivOp> of
+csrc/relax.hip; functional.physics_mse_loss(form="divergence"), physics_loss_kernel<DivLoss> of csrc/physics.hip).
 
     python tools/relax_div_bench.py [--out profiles/relax_div_bench.json]
 

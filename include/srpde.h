@@ -72,8 +72,10 @@ typedef struct ihipStream_t* hipStream_t;
  *      srpde_div_cg_workspace_size, srpde_div_cg_done_offset, srpde_div_cg_init, srpde_div_cg_iterate,
  *      srpde_div_cg_finish
  *  19  the divergence-form operator in the smoother and the physics loss: srpde_div_relax_workspace_size,
- *      srpde_div_relax, srpde_physics_loss_div_workspace_size, srpde_physics_loss_div_fwd */
-#define SRPDE_ABI_VERSION 19
+ *      srpde_div_relax, srpde_physics_loss_div_workspace_size, srpde_physics_loss_div_fwd
+ *  20  the adjoint of the divergence-form operator and a warm-started CG: srpde_div_theta_grad,
+ *      srpde_div_cg_init_from */
+#define SRPDE_ABI_VERSION 20
 
 /* Kernel-family bits (per call; bit 0 of the same argument is the accumulate flag): the forward / dgrad
  * families compute the same outputs, statistics and stored splits bit for bit, so these only route a call to
@@ -762,6 +764,34 @@ int srpde_div_cg_iterate(const double* theta, int B, int n, int face_mean, doubl
                          const void* plan, size_t plan_bytes, void* ws, size_t ws_bytes, hipStream_t stream);
 int srpde_div_cg_finish(double* u, int* iters, double* resid, int B, int n, void* ws, size_t ws_bytes,
                         hipStream_t stream);
+/* The same CG from an initial guess (ABI 20), in place of srpde_div_cg_init and on the same workspace: x = u0,
+ * r = f - D_theta u0 (D_theta u0 in the rounding order of srpde_div_apply with inv_h2 = (n - 1)^2, then one
+ * subtraction), z = L^-1 r; |f| and |r0| are kept apart, so resid stays |r| / |f| and a problem whose u0 already has
+ * |r0| <= rtol |f| is done with iters = 0 and u = u0.  |f| = 0: u = 0, iters = 0, resid = 0, whatever u0 is.
+ * srpde_div_cg_iterate (k_begin = 1, the same theta, face_mean and rtol) and srpde_div_cg_finish follow unchanged;
+ * freezing, batch independence and the absence of host syncs are theirs.  For u0 = 0 and rtol < 1 every bit of u,
+ * iters and resid is the zero start's (D 0 = +0, f - 0 = f).  f, u0, theta [B][n][n] fp64, 8-byte aligned; rtol >= 0.
+ * One fused launch, the sine-transform solve, one small launch. */
+int srpde_div_cg_init_from(const double* f, const double* u0, const double* theta, int B, int n, int face_mean,
+                           double rtol, const void* plan, size_t plan_bytes, void* ws, size_t ws_bytes,
+                           hipStream_t stream);
+/* The pair gradient of D_theta (ABI 20): g_out = scale * G(u, lam; theta) with
+ *     G_a = inv_h2 * sum over b in E, W, S, N of a of  d_ab * (u_b - u_a) * (lam_b - lam_a)
+ * where d_ab = dc_ab / dtheta_a is
+ *     face_mean 0 (arithmetic):  0.5
+ *     face_mean 1 (harmonic):    (2.0 * (tb * tb)) / ((ta + tb) * (ta + tb))
+ *     b outside the grid:        1, u_b = lam_b = 0
+ * Summing <lam, D_theta u> by parts gives -inv_h2 * (sum over faces of c (u_b - u_a) (lam_b - lam_a)), so
+ * d<lam, D_theta u> / dtheta = -G, and with D_theta symmetric
+ *     y = D_theta u, upstream gy:      grad_u = D_theta gy,                 grad_theta = -G(u, gy)    (scale -1)
+ *     u = D_theta^-1 f, upstream gu:   lam = D_theta^-1 gu,  grad_f = lam,  grad_theta = +G(u, lam)   (scale +1)
+ * Every operation is rounded once, in this order (no contraction): a face term is (d_ab * (u_b - u_a)) *
+ * (lam_b - lam_a), the four are summed as (E + W) + (S + N), then * inv_h2, then * scale -- a host restatement in
+ * that order reproduces g_out bit for bit, whatever the tiling and whatever B.  A gather (no atomics), one launch for
+ * all of B.  u, lam, theta, g_out [B][n][n] fp64, shapes and alignment as srpde_div_apply; lam may be u; g_out must
+ * not alias an input; inv_h2 > 0 and scale finite. */
+int srpde_div_theta_grad(const double* u, const double* lam, const double* theta, double* g_out, int B, int n,
+                         int face_mean, double inv_h2, double scale, hipStream_t stream);
 
 /* ---- Row-sharded CG for ONE n x n problem over `world` ranks (the 640^2 ground
  *      truth of solve_multi_resolution, src/resolution_comparison.py:62-73).  Rank `rank` owns the

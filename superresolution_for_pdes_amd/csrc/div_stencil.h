@@ -1,5 +1,6 @@
 // The face coefficients of the divergence-form operator  D_theta u = div(theta grad u)  and its face sum, float or
-// double (poisson_div.hip: the operator and its CG; relax.hip: its smoother; physics.hip: its loss term).
+// double (poisson_div.hip: the operator and its CG; relax.hip: its smoother; physics.hip: its loss term), and the
+// coefficients' derivative in theta_a with its face sum, the operator's gradient in theta (poisson_div.hip).
 //
 // For node a with nodal theta_a and neighbour b the face coefficient is
 //     arithmetic (HARM false):  c = 0.5 * (ta + tb)
@@ -28,6 +29,27 @@ __device__ __forceinline__ T face_sum(const T* v, const T* th, int pitch, bool h
   const T cS = has_s ? face_mean<HARM>(ta, th[pitch]) : ta;
   const T cN = has_n ? face_mean<HARM>(ta, th[-pitch]) : ta;
   return (cE * (v[1] - vc) + cW * (v[-1] - vc)) + (cS * (v[pitch] - vc) + cN * (v[-pitch] - vc));
+}
+
+// d face_mean(ta, tb) / d ta: 0.5, or 2 tb^2 / (ta + tb)^2 (towards the ghost ring c = ta and the derivative is 1)
+template <bool HARM, typename T>
+__device__ __forceinline__ T face_mean_da(T ta, T tb) {
+  return HARM ? (T(2) * (tb * tb)) / ((ta + tb) * (ta + tb)) : T(0.5);
+}
+
+// The pair gradient of the operator in theta_a, sum over the node's faces of dc/dta (vb - va) (wb - wa), as
+// (gE + gW) + (gS + gN) with a face term g = (d * (vb - va)) * (wb - wa); tiles and has_* as for face_sum.  The halo
+// holds 0 for v and w outside the grid, so a ghost face gives (1 * (0 - va)) * (0 - wa) = va * wa exactly.
+template <bool HARM, typename T>
+__device__ __forceinline__ T face_grad_sum(const T* v, const T* w, const T* th, int pitch, bool has_w, bool has_e,
+                                           bool has_n, bool has_s) {
+  const T ta = th[0], vc = v[0], wc = w[0];
+  const T dE = has_e ? face_mean_da<HARM>(ta, th[1]) : T(1);
+  const T dW = has_w ? face_mean_da<HARM>(ta, th[-1]) : T(1);
+  const T dS = has_s ? face_mean_da<HARM>(ta, th[pitch]) : T(1);
+  const T dN = has_n ? face_mean_da<HARM>(ta, th[-pitch]) : T(1);
+  return ((dE * (v[1] - vc)) * (w[1] - wc) + (dW * (v[-1] - vc)) * (w[-1] - wc)) +
+         ((dS * (v[pitch] - vc)) * (w[pitch] - wc) + (dN * (v[-pitch] - vc)) * (w[-pitch] - wc));
 }
 
 }  // namespace srpde

@@ -35,6 +35,13 @@
 // Freeze rule.  done[b] is written only by (d) and read only by the (a) and (b) after it.  Once set, (a) and (b)
 // return at once for that problem: x, r, p, iters and resid stay as they are, no 0/0 is formed, and further
 // iterations are harmless.  |f| = 0 sets done in init's (d): x = 0 exactly, iters = 0, resid = 0.
+//
+// Warm start (srpde_div_cg_init_from).  x = u0, r = f - D u0 in one fused pass (div_init_from_kernel), z = M^-1 r,
+// then div_rz_from_kernel, the k = 0 pass that keeps |f| apart from |r0| and decides done at the real rtol.  The
+// iterations above run unchanged on that state; the zero-start kernels are not touched.
+//
+// Adjoint (srpde_div_theta_grad).  D_theta is symmetric, so the adjoint of the solve is the same solve, and the
+// gradient in theta of <lam, D_theta u> is the local pair gradient G(u, lam; theta) of div_theta_grad_kernel.
 #include <cmath>
 
 #include "common.h"
@@ -260,6 +267,149 @@ __global__ __launch_bounds__(kDivThreads) void div_init_kernel(const double* __r
   if (tid == 0) g.prr[(size_t)b * g.nb + block_id()] = s;
 }
 
+// warm-started init: x = u0, r = f - D_theta u0 (D_theta u0 as div_apply_kernel forms it, then one subtraction) from
+// the halo tiles of u0 and theta; the block's partials of f.f (into the p.q partials, free until iteration 1) and of
+// r.r.  The walk and the sums are div_init_kernel's, so for u0 = 0 (D 0 = +0, f - 0 = f) both partials are its bits.
+template <bool HARM>
+__global__ __launch_bounds__(kDivThreads) void div_init_from_kernel(const double* __restrict__ f,
+                                                                    const double* __restrict__ u0,
+                                                                    const double* __restrict__ theta, DivCG g,
+                                                                    double inv_h2) {
+  __shared__ double us[kDivLY * kDivLX];
+  __shared__ double ts[kDivLY * kDivLX];
+  __shared__ double red[4];
+  const int tid = threadIdx.x, b = blockIdx.z, n = g.n;
+  const long long base = (long long)b * n * n;
+  const int x0 = (int)blockIdx.x * kDivTX, y0 = (int)blockIdx.y * kDivTY;
+  for (int i = tid; i < kDivLY * kDivLX; i += kDivThreads) {
+    const int ly = i / kDivLX, lx = i - ly * kDivLX;
+    const int gy = y0 - 1 + ly, gx = x0 - 1 + lx;
+    double uv = 0.0, tv = 1.0;
+    if (gy >= 0 && gy < n && gx >= 0 && gx < n) {
+      const long long at = base + (long long)gy * n + gx;
+      uv = u0[at];
+      tv = theta[at];
+    }
+    us[i] = uv;
+    ts[i] = tv;
+  }
+  __syncthreads();
+
+  const int lx = (tid & 63) + 1, gx = x0 + (tid & 63);
+  const int ly0 = (tid >> 6) * kDivR + 1;
+  double accf = 0.0, accr = 0.0;
+  if (gx < n) {
+#pragma unroll
+    for (int r = 0; r < kDivR; ++r) {
+      const int ly = ly0 + r, gy = y0 + ly - 1;
+      if (gy < n) {
+        const int c = ly * kDivLX + lx;
+        const double du = face_sum<HARM>(us + c, ts + c, kDivLX, gx > 0, gx + 1 < n, gy > 0, gy + 1 < n) * inv_h2;
+        const long long at = base + (long long)gy * n + gx;
+        const double fv = f[at];
+        const double rv = fv - du;
+        g.x[at] = us[c];
+        g.r[at] = rv;
+        accf = accf + fv * fv;
+        accr = accr + rv * rv;
+      }
+    }
+  }
+  const double sf = block_sum(accf, red);
+  const double sr = block_sum(accr, red);
+  if (tid == 0) {
+    g.ppq[(size_t)b * g.nb + block_id()] = sf;
+    g.prr[(size_t)b * g.nb + block_id()] = sr;
+  }
+}
+
+// the k = 0 pass after div_init_from_kernel and the sine solve: the block's partial of r.z where iteration 1 reads
+// it; |f|^2 from the p.q partials, |r0|^2 from the r.r partials; done at the caller's rtol, so a u0 that already
+// satisfies it costs no iteration.  |f| = 0: every block zeroes its tile of x (u = 0 exactly, as the zero start).
+__global__ __launch_bounds__(kDivThreads) void div_rz_from_kernel(DivCG g, double rtol) {
+  __shared__ double red[4];
+  const int tid = threadIdx.x, b = blockIdx.z, n = g.n;
+  const long long base = (long long)b * n * n;
+  const int gx = (int)blockIdx.x * kDivTX + (tid & 63);
+  const int gy0 = (int)blockIdx.y * kDivTY + (tid >> 6) * kDivR;
+  double acc = 0.0;
+  if (gx < n) {
+#pragma unroll
+    for (int r = 0; r < kDivR; ++r) {
+      const int gy = gy0 + r;
+      if (gy < n) {
+        const long long at = base + (long long)gy * n + gx;
+        acc = acc + g.r[at] * g.z[at];
+      }
+    }
+  }
+  const double s = block_sum(acc, red);
+  if (tid == 0) g.prz[0][(size_t)b * g.nb + block_id()] = s;
+  const double ff = resum(g.ppq + (size_t)b * g.nb, g.nb, red);
+  if (ff == 0.0 && gx < n) {
+#pragma unroll
+    for (int r = 0; r < kDivR; ++r) {
+      const int gy = gy0 + r;
+      if (gy < n) g.x[base + (long long)gy * n + gx] = 0.0;
+    }
+  }
+  if (block_id() != 0) return;
+  const double rr = resum(g.prr + (size_t)b * g.nb, g.nb, red);
+  if (tid == 0) {
+    const double nf = sqrt(ff), nr = sqrt(rr);
+    g.ff[b] = ff;
+    g.iters[b] = 0;
+    g.resid[b] = nf > 0.0 ? nr / nf : 0.0;
+    g.done[b] = (ff == 0.0 || nr <= rtol * nf) ? 1 : 0;
+  }
+}
+
+// g = scale * G(u, lam; theta), G_a = inv_h2 * sum over a's faces of dc/dtheta_a (u_b - u_a) (lam_b - lam_a): the
+// gradient in theta of <lam, D_theta u>.  A gather over the halo tiles of u, lam and theta (3 x 34 x 66 doubles of
+// LDS, under the 64 KiB static limit): each node reads its own four faces, nothing is accumulated across nodes.
+template <bool HARM>
+__global__ __launch_bounds__(kDivThreads) void div_theta_grad_kernel(const double* __restrict__ u,
+                                                                     const double* __restrict__ lam,
+                                                                     const double* __restrict__ theta,
+                                                                     double* __restrict__ gout, double inv_h2,
+                                                                     double scale, int n) {
+  __shared__ double us[kDivLY * kDivLX];
+  __shared__ double ls[kDivLY * kDivLX];
+  __shared__ double ts[kDivLY * kDivLX];
+  const int tid = threadIdx.x, b = blockIdx.z;
+  const long long base = (long long)b * n * n;
+  const int x0 = (int)blockIdx.x * kDivTX, y0 = (int)blockIdx.y * kDivTY;
+  for (int i = tid; i < kDivLY * kDivLX; i += kDivThreads) {
+    const int ly = i / kDivLX, lx = i - ly * kDivLX;
+    const int gy = y0 - 1 + ly, gx = x0 - 1 + lx;
+    double uv = 0.0, lv = 0.0, tv = 1.0;
+    if (gy >= 0 && gy < n && gx >= 0 && gx < n) {
+      const long long at = base + (long long)gy * n + gx;
+      uv = u[at];
+      lv = lam[at];
+      tv = theta[at];
+    }
+    us[i] = uv;
+    ls[i] = lv;
+    ts[i] = tv;
+  }
+  __syncthreads();
+
+  const int lx = (tid & 63) + 1, gx = x0 + (tid & 63);
+  const int ly0 = (tid >> 6) * kDivR + 1;
+  if (gx >= n) return;
+#pragma unroll
+  for (int r = 0; r < kDivR; ++r) {
+    const int ly = ly0 + r, gy = y0 + ly - 1;
+    if (gy < n) {
+      const int c = ly * kDivLX + lx;
+      const double gv =
+          face_grad_sum<HARM>(us + c, ls + c, ts + c, kDivLX, gx > 0, gx + 1 < n, gy > 0, gy + 1 < n) * inv_h2;
+      gout[base + (long long)gy * n + gx] = gv * scale;
+    }
+  }
+}
+
 __global__ __launch_bounds__(256) void div_finish_kernel(DivCG g, double* __restrict__ u, int* __restrict__ iters,
                                                          double* __restrict__ resid, long long total, int B) {
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
@@ -351,6 +501,54 @@ int srpde_div_cg_init(const double* f, int B, int n, const void* plan, size_t pl
   if (int rc = dst_solve_launch(name, g.r, nullptr, g.z, B, n, plan, g.dst_ws, stream)) return rc;
   // rtol 0: only |f| = 0 is done before the first iteration
   hipLaunchKernelGGL(div_rz_kernel, div_grid(B, n), dim3(kDivThreads), 0, stream, g, 0, 0.0);
+  SRPDE_LAUNCH_CHECK(name);
+  return 0;
+}
+
+int srpde_div_cg_init_from(const double* f, const double* u0, const double* theta, int B, int n, int face_mean,
+                           double rtol, const void* plan, size_t plan_bytes, void* ws, size_t ws_bytes,
+                           hipStream_t stream) {
+  const char* name = "srpde_div_cg_init_from";
+  SRPDE_CHECK_ARG(f && u0 && theta, "srpde_div_cg_init_from: null pointer");
+  if (int rc = div_check(name, B, n, face_mean)) return rc;
+  if ((reinterpret_cast<uintptr_t>(f) | reinterpret_cast<uintptr_t>(u0) | reinterpret_cast<uintptr_t>(theta)) & 7u)
+    SRPDE_FAIL(kErrAlign, "srpde_div_cg_init_from: a pointer is not 8-byte aligned");
+  if (!(rtol >= 0.0)) SRPDE_FAIL(kErrArg, "srpde_div_cg_init_from: rtol=%g must be >= 0", rtol);
+  if (int rc = div_check_plan(name, n, plan, plan_bytes)) return rc;
+  if (int rc = div_check_ws(name, B, n, ws, ws_bytes)) return rc;
+  DivCG g = carve(ws, B, n);
+  const double inv_h2 = (double)(n - 1) * (double)(n - 1);
+  const dim3 grid = div_grid(B, n), block(kDivThreads);
+  if (face_mean)
+    hipLaunchKernelGGL(div_init_from_kernel<true>, grid, block, 0, stream, f, u0, theta, g, inv_h2);
+  else
+    hipLaunchKernelGGL(div_init_from_kernel<false>, grid, block, 0, stream, f, u0, theta, g, inv_h2);
+  SRPDE_LAUNCH_CHECK(name);
+  if (int rc = dst_solve_launch(name, g.r, nullptr, g.z, B, n, plan, g.dst_ws, stream)) return rc;
+  hipLaunchKernelGGL(div_rz_from_kernel, grid, block, 0, stream, g, rtol);
+  SRPDE_LAUNCH_CHECK(name);
+  return 0;
+}
+
+int srpde_div_theta_grad(const double* u, const double* lam, const double* theta, double* g_out, int B, int n,
+                         int face_mean, double inv_h2, double scale, hipStream_t stream) {
+  const char* name = "srpde_div_theta_grad";
+  SRPDE_CHECK_ARG(u && lam && theta && g_out, "srpde_div_theta_grad: null pointer");
+  if (int rc = div_check(name, B, n, face_mean)) return rc;
+  if (!(inv_h2 > 0.0) || !std::isfinite(inv_h2))
+    SRPDE_FAIL(kErrArg, "srpde_div_theta_grad: inv_h2=%g must be positive and finite", inv_h2);
+  if (!std::isfinite(scale)) SRPDE_FAIL(kErrArg, "srpde_div_theta_grad: scale=%g must be finite", scale);
+  if ((reinterpret_cast<uintptr_t>(u) | reinterpret_cast<uintptr_t>(lam) | reinterpret_cast<uintptr_t>(theta) |
+       reinterpret_cast<uintptr_t>(g_out)) & 7u)
+    SRPDE_FAIL(kErrAlign, "srpde_div_theta_grad: a pointer is not 8-byte aligned");
+  if (g_out == u || g_out == lam || g_out == theta)
+    SRPDE_FAIL(kErrArg, "srpde_div_theta_grad: g_out aliases an input (a node reads its neighbours)");
+  if (face_mean)
+    hipLaunchKernelGGL(div_theta_grad_kernel<true>, div_grid(B, n), dim3(kDivThreads), 0, stream, u, lam, theta, g_out,
+                       inv_h2, scale, n);
+  else
+    hipLaunchKernelGGL(div_theta_grad_kernel<false>, div_grid(B, n), dim3(kDivThreads), 0, stream, u, lam, theta,
+                       g_out, inv_h2, scale, n);
   SRPDE_LAUNCH_CHECK(name);
   return 0;
 }

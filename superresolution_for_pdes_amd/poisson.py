@@ -20,7 +20,10 @@ All of the above solve the POINTWISE form diag(theta) L u = f, which is L u = f 
 ``solve_div`` / ``solve_batched(..., form="divergence")`` are the DIVERGENCE form div(theta grad u) = f
 (csrc/poisson_div.hip): the conservative variable-coefficient operator with arithmetic or harmonic face means, solved
 by CG preconditioned with the sine-transform solve of L, whose iteration count is bounded by theta_max / theta_min and
-does not grow with n.  Opt-in as well: every default stays pointwise.
+does not grow with n.  Opt-in as well: every default stays pointwise.  ``apply_div`` and ``solve_div`` are
+differentiable in their fields and in theta (the operator is symmetric, so the solve's adjoint is the same solve;
+``div_theta_grad`` is the one local pass the theta gradient needs), and ``solve_div(..., u0=)`` starts the iteration
+from a guess.
 """
 from __future__ import annotations
 
@@ -173,22 +176,107 @@ def _div_fields(a, theta, device):
     return a, theta, B, n
 
 
+def _wants_grad(*tensors) -> bool:
+    return torch.is_grad_enabled() and any(t.requires_grad for t in tensors)
+
+
+def _apply_div(u, theta, mean: int, inv_h2: float):
+    """srpde_div_apply on prepared fields (_div_fields)."""
+    y = torch.empty_like(u)
+    if u.shape[0]:
+        call("srpde_div_apply", u.data_ptr(), theta.data_ptr(), y.data_ptr(), u.shape[0], u.shape[-1], mean,
+             inv_h2, stream_ptr(u.device))
+    return y
+
+
+def _div_theta_grad(u, lam, theta, mean: int, inv_h2: float, scale: float):
+    """srpde_div_theta_grad on prepared fields."""
+    g = torch.empty_like(u)
+    if u.shape[0]:
+        call("srpde_div_theta_grad", u.data_ptr(), lam.data_ptr(), theta.data_ptr(), g.data_ptr(), u.shape[0],
+             u.shape[-1], mean, inv_h2, scale, stream_ptr(u.device))
+    return g
+
+
+def div_theta_grad(u, lam, theta, face_mean: str = "harmonic", inv_h2: float = None, scale: float = 1.0,
+                   device="cuda"):
+    """scale * G(u, lam; theta), the pair gradient of the divergence-form operator: a new [B, n, n] fp64 device tensor
+    with G_a = inv_h2 * (sum over the four faces of node a of dc_ab/dtheta_a (u_b - u_a) (lam_b - lam_a)), where
+    dc/dtheta_a is 0.5 (``"arithmetic"``), 2 tb^2 / (ta + tb)^2 (``"harmonic"``) and 1 towards the ghost ring (u and
+    lam are 0 there).  d<lam, D_theta u>/dtheta = -G: the theta gradient of apply_div is -G(u, grad_y), that of
+    solve_div +G(u, lam) with lam the adjoint solve.  u, lam [n, n] or [B, n, n]; theta is broadcast; ``inv_h2``
+    defaults to (n - 1)^2.  One launch, stream-ordered, no host sync, not itself differentiable
+    (srpde_div_theta_grad; include/srpde.h states the rounding order)."""
+    mean = check_face_mean(face_mean)
+    with torch.no_grad():
+        u, theta, B, n = _div_fields(u, theta, device)
+        lam = _dev_f64(lam, device).reshape(u.shape)
+        return _div_theta_grad(u, lam, theta, mean, float((n - 1) ** 2 if inv_h2 is None else inv_h2), float(scale))
+
+
+class _ApplyDiv(torch.autograd.Function):
+    """y = D_theta u.  D_theta is symmetric: grad_u = D_theta grad_y; grad_theta = -G(u, grad_y; theta)."""
+
+    @staticmethod
+    def forward(ctx, u, theta, mean, inv_h2):
+        u, theta = u.detach().contiguous(), theta.detach().contiguous()
+        ctx.save_for_backward(u, theta)
+        ctx.mean, ctx.inv_h2 = mean, inv_h2
+        return _apply_div(u, theta, mean, inv_h2)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        u, theta = ctx.saved_tensors
+        gy = gy.contiguous()
+        gu = _apply_div(gy, theta, ctx.mean, ctx.inv_h2) if ctx.needs_input_grad[0] else None
+        gth = _div_theta_grad(u, gy, theta, ctx.mean, ctx.inv_h2, -1.0) if ctx.needs_input_grad[1] else None
+        return gu, gth, None, None
+
+
+class _SolveDiv(torch.autograd.Function):
+    """u = D_theta^-1 f.  The adjoint solve is the same solve: lam = D_theta^-1 grad_u with the forward's face mean,
+    tolerance and limits, from a zero start; grad_f = lam; grad_theta = +G(u, lam; theta).  Nothing depends on u0."""
+
+    @staticmethod
+    def forward(ctx, f, theta, u0, mean, rtol, maxit, check_every, check):
+        f, theta = f.detach().contiguous(), theta.detach().contiguous()
+        u, iters, resid = _solve_div(f, theta, u0, mean, rtol, maxit, check_every, check)
+        ctx.save_for_backward(u, theta)
+        ctx.args = (mean, rtol, maxit, check_every, check)
+        ctx.mark_non_differentiable(iters, resid)
+        return u, iters, resid
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gu, _giters, _gresid):
+        u, theta = ctx.saved_tensors
+        mean = ctx.args[0]
+        lam = _solve_div(gu.contiguous(), theta, None, *ctx.args)[0]     # NotConverged propagates
+        gth = None
+        if ctx.needs_input_grad[1]:
+            gth = _div_theta_grad(u, lam, theta, mean, float((u.shape[-1] - 1) ** 2), 1.0)
+        return (lam if ctx.needs_input_grad[0] else None), gth, None, None, None, None, None, None
+
+
 def apply_div(u, theta, face_mean: str = "harmonic", inv_h2: float = None, device="cuda"):
     """y = div(theta grad u) on the project's grid (zero ghost ring, h = 1 / (n - 1)): a new [B, n, n] fp64 device
     tensor.  The face coefficient between nodes a and b is 0.5 (ta + tb) (``"arithmetic"``) or 2 ta tb / (ta + tb)
     (``"harmonic"``), theta_a towards the ghost ring; ``inv_h2`` defaults to (n - 1)^2.  One launch, stream-ordered,
-    no host sync (srpde_div_apply; include/srpde.h states the rounding order)."""
+    no host sync (srpde_div_apply; include/srpde.h states the rounding order).
+
+    Differentiable in u and theta when grad mode is on and one of them requires grad (one more srpde_div_apply for
+    u, one srpde_div_theta_grad for theta; once differentiable); otherwise exactly the call above."""
     mean = check_face_mean(face_mean)
     u, theta, B, n = _div_fields(u, theta, device)
-    y = torch.empty_like(u)
-    if B:
-        call("srpde_div_apply", u.data_ptr(), theta.data_ptr(), y.data_ptr(), B, n, mean,
-             float((n - 1) ** 2 if inv_h2 is None else inv_h2), stream_ptr(u.device))
-    return y
+    inv_h2 = float((n - 1) ** 2 if inv_h2 is None else inv_h2)
+    if _wants_grad(u, theta):
+        return _ApplyDiv.apply(u, theta, mean, inv_h2)
+    return _apply_div(u, theta, mean, inv_h2)
 
 
 def solve_div(f, theta, face_mean: str = "harmonic", rtol: float = DEFAULT_RTOL, maxit: int = None,
-              check_every: int = 8, check: bool = True, return_info: bool = False, device="cuda"):
+              check_every: int = 8, check: bool = True, return_info: bool = False, device="cuda", u0=None):
     """u[B, n, n] (float64, on device) with div(theta grad u) = f per problem, by CG preconditioned with the
     sine-transform solve of the constant-coefficient operator (srpde_div_cg_*).  Convergence, |r| <= rtol |f|, is
     decided per problem on the device, and a converged problem is frozen, so a problem's u / iters / resid are the
@@ -199,19 +287,46 @@ def solve_div(f, theta, face_mean: str = "harmonic", rtol: float = DEFAULT_RTOL,
     ``check_every=0``: exactly ``maxit`` iterations and no host sync at all -- capturable in a graph once
     ``dst_plan(n)`` exists.
     ``check`` (not under stream capture): problems with resid > rtol raise NotConverged (one host sync).
-    ``return_info``: (u, iters [B] int32, resid [B] fp64 = |r| / |f|, 0 for f = 0)."""
+    ``return_info``: (u, iters [B] int32, resid [B] fp64 = |r| / |f|, 0 for f = 0).
+    ``u0`` ([B, n, n] or [n, n], broadcast like f): the iteration starts from it instead of from 0
+    (srpde_div_cg_init_from): a u0 with |f - D u0| <= rtol |f| is returned after 0 iterations, a nearby one (the last
+    step of an optimisation loop, a cascade output) saves the iterations that its residual is already below |f|;
+    zeros give the bits of ``u0=None``, which is today's call sequence.
+
+    Differentiable in f and theta when grad mode is on and one of them requires grad (once differentiable): the
+    backward is one more solve with the same theta, face_mean, rtol, maxit and check_every from a zero start (the
+    operator is symmetric), which raises NotConverged like the forward, and, if theta needs a gradient, one
+    srpde_div_theta_grad.  u0 gets no gradient (the solution does not depend on it); iters and resid are not
+    differentiable.  Without a tensor that requires grad, or under no_grad, exactly the calls above."""
     mean = check_face_mean(face_mean)
     f, theta, B, n = _div_fields(f, theta, device)
+    if u0 is not None:
+        u0 = _dev_f64(u0, device).detach()
+        if u0.dim() == 2:
+            u0 = u0.unsqueeze(0)
+        if u0.shape != f.shape:
+            u0 = u0.expand_as(f)
+        u0 = u0.contiguous()
     if maxit is None:
         maxit = 20 * n * n
     maxit, check_every = int(maxit), int(check_every)
     if maxit < 0 or check_every < 0:
         raise ValueError("solve_div: maxit and check_every must be >= 0")
+    if _wants_grad(f, theta):
+        out = _SolveDiv.apply(f, theta, u0, mean, float(rtol), maxit, check_every, bool(check))
+    else:
+        out = _solve_div(f, theta, u0, mean, float(rtol), maxit, check_every, bool(check))
+    return out if return_info else out[0]
+
+
+def _solve_div(f, theta, u0, mean: int, rtol: float, maxit: int, check_every: int, check: bool):
+    """The srpde_div_cg_* call sequence on prepared fields -> (u, iters, resid)."""
+    B, n = f.shape[0], f.shape[-1]
     u = torch.empty_like(f)
     iters = torch.empty(B, dtype=torch.int32, device=f.device)
     resid = torch.empty(B, dtype=torch.float64, device=f.device)
     if B == 0:
-        return (u, iters, resid) if return_info else u
+        return u, iters, resid
     capturing = torch.cuda.is_current_stream_capturing()
     if check_every and capturing:
         raise RuntimeError("solve_div: reading the done flags synchronises the host; capture with check_every=0")
@@ -219,25 +334,31 @@ def solve_div(f, theta, face_mean: str = "harmonic", rtol: float = DEFAULT_RTOL,
     ws_bytes = int(query("srpde_div_cg_workspace_size", B, n))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=f.device)
     sp = stream_ptr(f.device)
-    call("srpde_div_cg_init", f.data_ptr(), B, n, plan.data_ptr(), plan.numel(), ws.data_ptr(), ws_bytes, sp)
+    if u0 is None:
+        call("srpde_div_cg_init", f.data_ptr(), B, n, plan.data_ptr(), plan.numel(), ws.data_ptr(), ws_bytes, sp)
+    else:
+        call("srpde_div_cg_init_from", f.data_ptr(), u0.data_ptr(), theta.data_ptr(), B, n, mean, rtol,
+             plan.data_ptr(), plan.numel(), ws.data_ptr(), ws_bytes, sp)
     done_at = int(query("srpde_div_cg_done_offset", B, n))
     done = ws[done_at:done_at + 4 * B].view(torch.int32)
     k = 0
+    if u0 is not None and check_every and bool(done.all()):   # a u0 that already satisfies rtol: no chunk at all
+        k = maxit
     while k < maxit:
         count = min(check_every, maxit - k) if check_every else maxit
-        call("srpde_div_cg_iterate", theta.data_ptr(), B, n, mean, float(rtol), k + 1, count, plan.data_ptr(),
+        call("srpde_div_cg_iterate", theta.data_ptr(), B, n, mean, rtol, k + 1, count, plan.data_ptr(),
              plan.numel(), ws.data_ptr(), ws_bytes, sp)
         k += count
         if check_every and k < maxit and bool(done.all()):
             break
     call("srpde_div_cg_finish", u.data_ptr(), iters.data_ptr(), resid.data_ptr(), B, n, ws.data_ptr(), ws_bytes, sp)
     if check and not capturing:
-        bad = resid > float(rtol)
+        bad = resid > rtol
         nbad = int(bad.sum())
         if nbad:
             raise NotConverged(f"solve_div: {nbad} of {B} problems (n={n}) above rtol={rtol:g} after {maxit} "
                                f"iterations; worst residual {float(resid.max()):.3e}")
-    return (u, iters, resid) if return_info else u
+    return u, iters, resid
 
 
 def residual_metrics(u, f, theta, interior_only: bool = False, inv_h2: float = None, device="cuda",
@@ -248,7 +369,8 @@ def residual_metrics(u, f, theta, interior_only: bool = False, inv_h2: float = N
     solve_batched / solve_multi_resolution solve; ``interior_only`` leaves the boundary nodes out (a crop of a
     larger solve, whose ring is not zero).  Stream-ordered, no host sync (srpde_pde_residual_metrics).
     ``form="divergence"``: (RMS, max abs) of div(theta grad u) - f with ``face_mean`` instead, through apply_div, in
-    fp64 whatever u's precision."""
+    fp64 whatever u's precision -- and, through apply_div, differentiable in u, f and theta when one of them requires
+    grad (the pointwise metric is not)."""
     if check_form(form) == "divergence":
         f, theta, E, n = _div_fields(f, theta, device)
         u = _dev_f64(u, device).reshape(f.shape)
@@ -302,11 +424,12 @@ def relax(u, f, theta, sweeps: int, omega: float = 0.8, interior_only: bool = Fa
 
 def solve_batched(f, theta, rtol: float = DEFAULT_RTOL, maxit: int = None, device="cuda",
                   return_iters: bool = False, check: bool = True, _start_aborted: bool = False,
-                  method: str = "cg", form: str = "pointwise", face_mean: str = "harmonic"):
+                  method: str = "cg", form: str = "pointwise", face_mean: str = "harmonic", u0=None):
     """u[B, n, n] (float64, on device) with theta*Lap(u) = f per problem.
 
     ``form="divergence"`` solves div(theta grad u) = f instead (solve_div, which has one solver: ``method`` and
-    ``_start_aborted`` are refused; ``return_iters`` gives its iteration counts).
+    ``_start_aborted`` are refused; ``return_iters`` gives its iteration counts; ``u0`` is its initial guess, which
+    the pointwise form and ``method="dst"`` refuse).
 
     ``method="dst"`` solves directly (solve_direct): there is nothing to iterate, so ``return_iters`` gives
     zeros and non-default ``rtol`` / ``maxit`` / ``check`` / ``_start_aborted`` are refused.
@@ -320,8 +443,10 @@ def solve_batched(f, theta, rtol: float = DEFAULT_RTOL, maxit: int = None, devic
         if method != "cg" or _start_aborted:
             raise ValueError('form="divergence" has one solver (solve_div): method and _start_aborted do not apply')
         u, iters, _ = solve_div(f, theta, face_mean=face_mean, rtol=rtol, maxit=maxit, check=check, return_info=True,
-                                device=device)
+                                device=device, u0=u0)
         return (u, iters) if return_iters else u
+    if u0 is not None:
+        raise ValueError('u0 belongs to form="divergence" (solve_div): the pointwise solvers start from zero')
     if check_solver(method) == "dst":
         if rtol != DEFAULT_RTOL or maxit is not None or check is not True or _start_aborted:
             raise ValueError('method="dst" is a direct solve: rtol, maxit, check and _start_aborted do not apply')

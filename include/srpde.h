@@ -74,8 +74,11 @@ typedef struct ihipStream_t* hipStream_t;
  *  19  the divergence-form operator in the smoother and the physics loss: srpde_div_relax_workspace_size,
  *      srpde_div_relax, srpde_physics_loss_div_workspace_size, srpde_physics_loss_div_fwd
  *  20  the adjoint of the divergence-form operator and a warm-started CG: srpde_div_theta_grad,
- *      srpde_div_cg_init_from */
-#define SRPDE_ABI_VERSION 20
+ *      srpde_div_cg_init_from
+ *  21  the shifted operator D_theta - sigma I and implicit time steps: srpde_div_apply_shift,
+ *      srpde_poisson_dst_shift_batched, srpde_div_cg_init_shift, srpde_div_cg_init_from_shift,
+ *      srpde_div_cg_iterate_shift, srpde_div_step_rhs */
+#define SRPDE_ABI_VERSION 21
 
 /* Kernel-family bits (per call; bit 0 of the same argument is the accumulate flag): the forward / dgrad
  * families compute the same outputs, statistics and stored splits bit for bit, so these only route a call to
@@ -792,6 +795,59 @@ int srpde_div_cg_init_from(const double* f, const double* u0, const double* thet
  * not alias an input; inv_h2 > 0 and scale finite. */
 int srpde_div_theta_grad(const double* u, const double* lam, const double* theta, double* g_out, int B, int n,
                          int face_mean, double inv_h2, double scale, hipStream_t stream);
+
+/* ---- The shifted operator A = D_theta - sigma I, sigma >= 0 and finite (ABI 21): the operator of an implicit time
+ *      step of u_t = div(theta grad u) - f (sigma = 1 / dt) and of the screened problem (D_theta - sigma) u = f.  A is
+ *      as symmetric and negative definite as D_theta.  With M = L - sigma_p I, which the sine transform diagonalises
+ *      as it does L, and sigma_p = sigma / theta_g for any theta_g in [theta_min, theta_max],
+ *          min(theta_min, theta_g) (-M) <= -A <= max(theta_max, theta_g) (-M)
+ *      (from theta_min (-L) <= -D_theta <= theta_max (-L)), so cond(M^-1 A) <= theta_max / theta_min for every n and
+ *      every sigma: the CG above, with M as its preconditioner, needs no more iterations than the unshifted solve.
+ *      Every entry here with sigma = 0 (and sigma_p = 0) launches the kernels of its unshifted namesake. ---- */
+/* y = D_theta u - sigma * u: the y of srpde_div_apply (the face sum, * inv_h2), then the one product sigma * u, then
+ * the one subtraction, each rounded once (no contraction).  Arguments as srpde_div_apply.  One launch, the same
+ * kernel: the shift is applied where y is stored. */
+int srpde_div_apply_shift(const double* u, const double* theta, double* y, int B, int n, int face_mean, double inv_h2,
+                          double sigma, hipStream_t stream);
+/* u = solution of (L - sigma_p I) u = f for B problems, L the 5-point Laplacian of srpde_poisson_dst_batched (no
+ * theta): f, u [B][n][n] fp64, n >= 2, sigma_p >= 0 and finite; plan and workspace as srpde_poisson_dst_batched (the
+ * plan format is the same).  The eigenvalue scaling h^2 / (lam_i + lam_j) becomes
+ *     1 / ((lam_i + lam_j) * inv_h2 - sigma_p),   inv_h2 = (n - 1)^2
+ * each operation rounded once in this order (no contraction): the sum of the two eigenvalues, the product with inv_h2,
+ * the subtraction, the reciprocal; the transformed field is then multiplied by it -- in the LDS kernel after its
+ * second product, above srpde_poisson_dst_lds_max_n() at the second launch's store.  sigma_p = 0 runs the unshifted
+ * kernels: the bits of srpde_poisson_dst_batched with theta = 1. */
+int srpde_poisson_dst_shift_batched(const double* f, double* u, int B, int n, double sigma_p, const void* plan,
+                                    size_t plan_bytes, void* ws, size_t ws_bytes, hipStream_t stream);
+/* (D_theta - sigma I) u = f by the CG of srpde_div_cg_*, preconditioned with the sine-transform solve of
+ * L - sigma_p I, on the same workspace (srpde_div_cg_workspace_size, srpde_div_cg_done_offset) and finished by
+ * srpde_div_cg_finish.  init_shift: x = 0, r = f, z = M^-1 r (r does not depend on sigma).  init_from_shift: x = u0,
+ * r = f - (D_theta u0 - sigma * u0) in one fused pass -- the operator in the rounding order of srpde_div_apply_shift
+ * with inv_h2 = (n - 1)^2, then one subtraction -- otherwise as srpde_div_cg_init_from (u0 = 0 gives the zero start's
+ * bits, a u0 within rtol gives iters = 0).  iterate_shift: q = D_theta p - sigma * p in step (a), z = M^-1 r with
+ * sigma_p in step (c); the same sigma, sigma_p, theta, face_mean and rtol in every call of one solve.  The freeze rule,
+ * the per-problem fixed-order sums, batch independence and the absence of atomics, barriers and host reads are those
+ * of srpde_div_cg_iterate: the update, r.z and finish kernels are the same code. */
+int srpde_div_cg_init_shift(const double* f, int B, int n, double sigma_p, const void* plan, size_t plan_bytes,
+                            void* ws, size_t ws_bytes, hipStream_t stream);
+int srpde_div_cg_init_from_shift(const double* f, const double* u0, const double* theta, int B, int n, int face_mean,
+                                 double sigma, double sigma_p, double rtol, const void* plan, size_t plan_bytes,
+                                 void* ws, size_t ws_bytes, hipStream_t stream);
+int srpde_div_cg_iterate_shift(const double* theta, int B, int n, int face_mean, double sigma, double sigma_p,
+                               double rtol, int k_begin, int k_count, const void* plan, size_t plan_bytes, void* ws,
+                               size_t ws_bytes, hipStream_t stream);
+/* The right-hand side of one implicit time step of u_t = D_theta u - f with a forcing constant over the step, for the
+ * solve (D_theta - sigma I) u+ = rhs:
+ *     cn 0, backward Euler,  (u+ - u) / dt = D_theta u+ - f,                  sigma = 1 / dt:
+ *         rhs = f - sigma * u
+ *     cn 1, Crank-Nicolson,  (u+ - u) / dt = (D_theta u+ + D_theta u) / 2 - f, sigma = 2 / dt (the equation times 2):
+ *         rhs = (2 f - sigma * u) - D_theta u
+ * 2 f is exact; D_theta u is srpde_div_apply's y with inv_h2 = (n - 1)^2; the product sigma * u and the subtractions
+ * are rounded once each, in the order written (no contraction).  f == NULL is f = 0 (the same operations on 0.0).
+ * u, theta, rhs (and f) [B][n][n] fp64, 8-byte aligned; rhs must not alias u, f or theta; sigma >= 0 and finite.  One
+ * launch on srpde_div_apply's tiles; backward Euler reads no neighbour. */
+int srpde_div_step_rhs(const double* u, const double* f, const double* theta, double* rhs, int B, int n, int face_mean,
+                       double sigma, int cn, hipStream_t stream);
 
 /* ---- Row-sharded CG for ONE n x n problem over `world` ranks (the 640^2 ground
  *      truth of solve_multi_resolution, src/resolution_comparison.py:62-73).  Rank `rank` owns the

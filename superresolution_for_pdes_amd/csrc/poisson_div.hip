@@ -40,6 +40,15 @@
 // then div_rz_from_kernel, the k = 0 pass that keeps |f| apart from |r0| and decides done at the real rtol.  The
 // iterations above run unchanged on that state; the zero-start kernels are not touched.
 //
+// Shift (srpde_div_apply_shift, srpde_div_cg_*_shift, srpde_div_step_rhs).  A = D_theta - sigma I, sigma >= 0, is the
+// operator of an implicit time step of u_t = D_theta u - f (sigma = 1 / dt) and of the screened problem.  It is as
+// symmetric and negative definite as D_theta, and with M = L - sigma_p I, sigma_p = sigma / theta_g for any theta_g in
+// [theta_min, theta_max], min(theta_min, theta_g) (-M) <= -A <= max(theta_max, theta_g) (-M): cond(M^-1 A) <=
+// theta_max / theta_min for every n and every sigma.  The shift is a template argument of div_apply_kernel and
+// div_init_from_kernel, y = D u - sigma * u as one product and one subtraction after the face sum's * inv_h2, and an
+// argument of the sine-transform solve (poisson_dst.h); everything else of the iteration -- update, r.z, the freeze
+// rule, the fixed-order sums, finish -- is the code above, untouched.  sigma = 0 launches the unshifted kernels.
+//
 // Adjoint (srpde_div_theta_grad).  D_theta is symmetric, so the adjoint of the solve is the same solve, and the
 // gradient in theta of <lam, D_theta u> is the local pair gradient G(u, lam; theta) of div_theta_grad_kernel.
 #include <cmath>
@@ -114,11 +123,12 @@ DivCG carve(void* ws, int B, int n) {
 __device__ __forceinline__ int block_id() { return (int)(blockIdx.y * gridDim.x + blockIdx.x); }
 
 // y = D_theta u for one tile.  PCG: u = p = z + beta p_old is formed here (header, launch (a)).
-template <bool PCG, bool HARM>
+// SHIFT: y = D_theta u - sigma * u (the product, then the subtraction, after the face sum's * inv_h2).
+template <bool PCG, bool HARM, bool SHIFT>
 __global__ __launch_bounds__(kDivThreads) void div_apply_kernel(const double* __restrict__ u,
                                                                 const double* __restrict__ theta,
-                                                                double* __restrict__ y, DivCG g, double inv_h2, int n,
-                                                                int k) {
+                                                                double* __restrict__ y, DivCG g, double inv_h2,
+                                                                double sigma, int n, int k) {
   __shared__ double us[kDivLY * kDivLX];
   __shared__ double ts[kDivLY * kDivLX];
   __shared__ double red[4];
@@ -163,7 +173,8 @@ __global__ __launch_bounds__(kDivThreads) void div_apply_kernel(const double* __
       if (gy < n) {
         const int c = ly * kDivLX + lx;
         const double uc = us[c];
-        const double yv = face_sum<HARM>(us + c, ts + c, kDivLX, gx > 0, gx + 1 < n, gy > 0, gy + 1 < n) * inv_h2;
+        double yv = face_sum<HARM>(us + c, ts + c, kDivLX, gx > 0, gx + 1 < n, gy > 0, gy + 1 < n) * inv_h2;
+        if (SHIFT) yv = yv - sigma * uc;
         const long long at = base + (long long)gy * n + gx;
         y[at] = yv;
         if (PCG) {
@@ -270,11 +281,12 @@ __global__ __launch_bounds__(kDivThreads) void div_init_kernel(const double* __r
 // warm-started init: x = u0, r = f - D_theta u0 (D_theta u0 as div_apply_kernel forms it, then one subtraction) from
 // the halo tiles of u0 and theta; the block's partials of f.f (into the p.q partials, free until iteration 1) and of
 // r.r.  The walk and the sums are div_init_kernel's, so for u0 = 0 (D 0 = +0, f - 0 = f) both partials are its bits.
-template <bool HARM>
+// SHIFT: r = f - (D_theta u0 - sigma * u0), the operator as div_apply_kernel<.., SHIFT> forms it (+0 for u0 = 0 too).
+template <bool HARM, bool SHIFT>
 __global__ __launch_bounds__(kDivThreads) void div_init_from_kernel(const double* __restrict__ f,
                                                                     const double* __restrict__ u0,
                                                                     const double* __restrict__ theta, DivCG g,
-                                                                    double inv_h2) {
+                                                                    double inv_h2, double sigma) {
   __shared__ double us[kDivLY * kDivLX];
   __shared__ double ts[kDivLY * kDivLX];
   __shared__ double red[4];
@@ -304,7 +316,8 @@ __global__ __launch_bounds__(kDivThreads) void div_init_from_kernel(const double
       const int ly = ly0 + r, gy = y0 + ly - 1;
       if (gy < n) {
         const int c = ly * kDivLX + lx;
-        const double du = face_sum<HARM>(us + c, ts + c, kDivLX, gx > 0, gx + 1 < n, gy > 0, gy + 1 < n) * inv_h2;
+        double du = face_sum<HARM>(us + c, ts + c, kDivLX, gx > 0, gx + 1 < n, gy > 0, gy + 1 < n) * inv_h2;
+        if (SHIFT) du = du - sigma * us[c];
         const long long at = base + (long long)gy * n + gx;
         const double fv = f[at];
         const double rv = fv - du;
@@ -361,6 +374,58 @@ __global__ __launch_bounds__(kDivThreads) void div_rz_from_kernel(DivCG g, doubl
     g.iters[b] = 0;
     g.resid[b] = nf > 0.0 ? nr / nf : 0.0;
     g.done[b] = (ff == 0.0 || nr <= rtol * nf) ? 1 : 0;
+  }
+}
+
+// The right-hand side of one implicit time step of u_t = D_theta u - f, for the solve (D_theta - sigma I) u+ = rhs:
+//   CN false (backward Euler, sigma = 1 / dt):  rhs = f - sigma * u
+//   CN true  (Crank-Nicolson, sigma = 2 / dt):  rhs = (2 f - sigma * u) - D_theta u
+// 2 f is exact, D_theta u is div_apply_kernel's (face sum * inv_h2), every other operation is rounded once in the
+// order written; f == nullptr is f = 0.  Backward Euler reads no neighbour and stages nothing in LDS.
+template <bool CN, bool HARM>
+__global__ __launch_bounds__(kDivThreads) void div_step_rhs_kernel(const double* __restrict__ u,
+                                                                   const double* __restrict__ f,
+                                                                   const double* __restrict__ theta,
+                                                                   double* __restrict__ rhs, double inv_h2,
+                                                                   double sigma, int n) {
+  __shared__ double us[CN ? kDivLY * kDivLX : 1];
+  __shared__ double ts[CN ? kDivLY * kDivLX : 1];
+  const int tid = threadIdx.x, b = blockIdx.z;
+  const long long base = (long long)b * n * n;
+  const int x0 = (int)blockIdx.x * kDivTX, y0 = (int)blockIdx.y * kDivTY;
+  if (CN) {
+    for (int i = tid; i < kDivLY * kDivLX; i += kDivThreads) {
+      const int ly = i / kDivLX, lx = i - ly * kDivLX;
+      const int gy = y0 - 1 + ly, gx = x0 - 1 + lx;
+      double uv = 0.0, tv = 1.0;
+      if (gy >= 0 && gy < n && gx >= 0 && gx < n) {
+        const long long at = base + (long long)gy * n + gx;
+        uv = u[at];
+        tv = theta[at];
+      }
+      us[i] = uv;
+      ts[i] = tv;
+    }
+    __syncthreads();
+  }
+
+  const int lx = (tid & 63) + 1, gx = x0 + (tid & 63);
+  const int ly0 = (tid >> 6) * kDivR + 1;
+  if (gx >= n) return;
+#pragma unroll
+  for (int r = 0; r < kDivR; ++r) {
+    const int ly = ly0 + r, gy = y0 + ly - 1;
+    if (gy < n) {
+      const long long at = base + (long long)gy * n + gx;
+      const double fv = f ? f[at] : 0.0;
+      if (CN) {
+        const int c = ly * kDivLX + lx;
+        const double du = face_sum<HARM>(us + c, ts + c, kDivLX, gx > 0, gx + 1 < n, gy > 0, gy + 1 < n) * inv_h2;
+        rhs[at] = (2.0 * fv - sigma * us[c]) - du;
+      } else {
+        rhs[at] = fv - sigma * u[at];
+      }
+    }
   }
 }
 
@@ -466,41 +531,134 @@ size_t srpde_div_cg_done_offset(int B, int n) {
   return (size_t)(reinterpret_cast<char*>(carve(nullptr, B, n).done) - static_cast<char*>(nullptr));
 }
 
-int srpde_div_apply(const double* u, const double* theta, double* y, int B, int n, int face_mean, double inv_h2,
-                    hipStream_t stream) {
-  const char* name = "srpde_div_apply";
-  SRPDE_CHECK_ARG(u && theta && y, "srpde_div_apply: null pointer");
+// sigma >= 0 and finite; the message names the entry
+static int div_check_sigma(const char* name, const char* what, double sigma) {
+  if (!(sigma >= 0.0) || !std::isfinite(sigma)) SRPDE_FAIL(kErrArg, "%s: %s=%g must be >= 0 and finite", name, what, sigma);
+  return 0;
+}
+
+// srpde_div_apply and srpde_div_apply_shift: sigma = 0 is the unshifted kernel
+static int div_apply_launch(const char* name, const double* u, const double* theta, double* y, int B, int n,
+                            int face_mean, double inv_h2, double sigma, hipStream_t stream) {
+  SRPDE_CHECK_ARG(u && theta && y, "%s: null pointer", name);
   if (int rc = div_check(name, B, n, face_mean)) return rc;
   if (!(inv_h2 > 0.0) || !std::isfinite(inv_h2))
-    SRPDE_FAIL(kErrArg, "srpde_div_apply: inv_h2=%g must be positive and finite", inv_h2);
+    SRPDE_FAIL(kErrArg, "%s: inv_h2=%g must be positive and finite", name, inv_h2);
+  if (int rc = div_check_sigma(name, "sigma", sigma)) return rc;
   if ((reinterpret_cast<uintptr_t>(u) | reinterpret_cast<uintptr_t>(theta) | reinterpret_cast<uintptr_t>(y)) & 7u)
-    SRPDE_FAIL(kErrAlign, "srpde_div_apply: a pointer is not 8-byte aligned");
-  if (y == u || y == theta) SRPDE_FAIL(kErrArg, "srpde_div_apply: y aliases an input (a node reads its neighbours)");
+    SRPDE_FAIL(kErrAlign, "%s: a pointer is not 8-byte aligned", name);
+  if (y == u || y == theta) SRPDE_FAIL(kErrArg, "%s: y aliases an input (a node reads its neighbours)", name);
   DivCG none = {};
-  if (face_mean)
-    hipLaunchKernelGGL((div_apply_kernel<false, true>), div_grid(B, n), dim3(kDivThreads), 0, stream, u, theta, y, none,
-                       inv_h2, n, 0);
+  const dim3 grid = div_grid(B, n), block(kDivThreads);
+  if (sigma != 0.0) {
+    if (face_mean)
+      hipLaunchKernelGGL((div_apply_kernel<false, true, true>), grid, block, 0, stream, u, theta, y, none, inv_h2,
+                         sigma, n, 0);
+    else
+      hipLaunchKernelGGL((div_apply_kernel<false, false, true>), grid, block, 0, stream, u, theta, y, none, inv_h2,
+                         sigma, n, 0);
+  } else if (face_mean) {
+    hipLaunchKernelGGL((div_apply_kernel<false, true, false>), grid, block, 0, stream, u, theta, y, none, inv_h2, 0.0,
+                       n, 0);
+  } else {
+    hipLaunchKernelGGL((div_apply_kernel<false, false, false>), grid, block, 0, stream, u, theta, y, none, inv_h2, 0.0,
+                       n, 0);
+  }
+  SRPDE_LAUNCH_CHECK(name);
+  return 0;
+}
+
+int srpde_div_apply(const double* u, const double* theta, double* y, int B, int n, int face_mean, double inv_h2,
+                    hipStream_t stream) {
+  return div_apply_launch("srpde_div_apply", u, theta, y, B, n, face_mean, inv_h2, 0.0, stream);
+}
+
+int srpde_div_apply_shift(const double* u, const double* theta, double* y, int B, int n, int face_mean, double inv_h2,
+                          double sigma, hipStream_t stream) {
+  return div_apply_launch("srpde_div_apply_shift", u, theta, y, B, n, face_mean, inv_h2, sigma, stream);
+}
+
+int srpde_div_step_rhs(const double* u, const double* f, const double* theta, double* rhs, int B, int n, int face_mean,
+                       double sigma, int cn, hipStream_t stream) {
+  const char* name = "srpde_div_step_rhs";
+  SRPDE_CHECK_ARG(u && theta && rhs, "srpde_div_step_rhs: null pointer");
+  if (int rc = div_check(name, B, n, face_mean)) return rc;
+  if (cn != 0 && cn != 1) SRPDE_FAIL(kErrArg, "srpde_div_step_rhs: cn=%d (0 backward Euler, 1 Crank-Nicolson)", cn);
+  if (int rc = div_check_sigma(name, "sigma", sigma)) return rc;
+  if ((reinterpret_cast<uintptr_t>(u) | reinterpret_cast<uintptr_t>(f) | reinterpret_cast<uintptr_t>(theta) |
+       reinterpret_cast<uintptr_t>(rhs)) & 7u)
+    SRPDE_FAIL(kErrAlign, "srpde_div_step_rhs: a pointer is not 8-byte aligned");
+  if (rhs == u || rhs == theta || rhs == f)
+    SRPDE_FAIL(kErrArg, "srpde_div_step_rhs: rhs aliases an input (a node reads its neighbours)");
+  const double inv_h2 = (double)(n - 1) * (double)(n - 1);
+  const dim3 grid = div_grid(B, n), block(kDivThreads);
+  if (!cn)
+    hipLaunchKernelGGL((div_step_rhs_kernel<false, false>), grid, block, 0, stream, u, f, theta, rhs, inv_h2, sigma, n);
+  else if (face_mean)
+    hipLaunchKernelGGL((div_step_rhs_kernel<true, true>), grid, block, 0, stream, u, f, theta, rhs, inv_h2, sigma, n);
   else
-    hipLaunchKernelGGL((div_apply_kernel<false, false>), div_grid(B, n), dim3(kDivThreads), 0, stream, u, theta, y,
-                       none, inv_h2, n, 0);
+    hipLaunchKernelGGL((div_step_rhs_kernel<true, false>), grid, block, 0, stream, u, f, theta, rhs, inv_h2, sigma, n);
+  SRPDE_LAUNCH_CHECK(name);
+  return 0;
+}
+
+// srpde_div_cg_init and srpde_div_cg_init_shift (the zero start has r = f whatever sigma is: only M changes)
+static int div_cg_init(const char* name, const double* f, int B, int n, double sigma_p, const void* plan,
+                       size_t plan_bytes, void* ws, size_t ws_bytes, hipStream_t stream) {
+  SRPDE_CHECK_ARG(f, "%s: null pointer", name);
+  if (int rc = div_check(name, B, n, 0)) return rc;
+  if (int rc = div_check_sigma(name, "sigma_p", sigma_p)) return rc;
+  if (reinterpret_cast<uintptr_t>(f) & 7u) SRPDE_FAIL(kErrAlign, "%s: f not 8-byte aligned", name);
+  if (int rc = div_check_plan(name, n, plan, plan_bytes)) return rc;
+  if (int rc = div_check_ws(name, B, n, ws, ws_bytes)) return rc;
+  DivCG g = carve(ws, B, n);
+  hipLaunchKernelGGL(div_init_kernel, div_grid(B, n), dim3(kDivThreads), 0, stream, f, g);
+  SRPDE_LAUNCH_CHECK(name);
+  if (int rc = dst_solve_launch(name, g.r, nullptr, g.z, B, n, plan, g.dst_ws, stream, sigma_p)) return rc;
+  // rtol 0: only |f| = 0 is done before the first iteration
+  hipLaunchKernelGGL(div_rz_kernel, div_grid(B, n), dim3(kDivThreads), 0, stream, g, 0, 0.0);
   SRPDE_LAUNCH_CHECK(name);
   return 0;
 }
 
 int srpde_div_cg_init(const double* f, int B, int n, const void* plan, size_t plan_bytes, void* ws, size_t ws_bytes,
                       hipStream_t stream) {
-  const char* name = "srpde_div_cg_init";
-  SRPDE_CHECK_ARG(f, "srpde_div_cg_init: null pointer");
-  if (int rc = div_check(name, B, n, 0)) return rc;
-  if (reinterpret_cast<uintptr_t>(f) & 7u) SRPDE_FAIL(kErrAlign, "srpde_div_cg_init: f not 8-byte aligned");
+  return div_cg_init("srpde_div_cg_init", f, B, n, 0.0, plan, plan_bytes, ws, ws_bytes, stream);
+}
+
+int srpde_div_cg_init_shift(const double* f, int B, int n, double sigma_p, const void* plan, size_t plan_bytes,
+                            void* ws, size_t ws_bytes, hipStream_t stream) {
+  return div_cg_init("srpde_div_cg_init_shift", f, B, n, sigma_p, plan, plan_bytes, ws, ws_bytes, stream);
+}
+
+static int div_cg_init_from(const char* name, const double* f, const double* u0, const double* theta, int B, int n,
+                            int face_mean, double sigma, double sigma_p, double rtol, const void* plan,
+                            size_t plan_bytes, void* ws, size_t ws_bytes, hipStream_t stream) {
+  SRPDE_CHECK_ARG(f && u0 && theta, "%s: null pointer", name);
+  if (int rc = div_check(name, B, n, face_mean)) return rc;
+  if (int rc = div_check_sigma(name, "sigma", sigma)) return rc;
+  if (int rc = div_check_sigma(name, "sigma_p", sigma_p)) return rc;
+  if ((reinterpret_cast<uintptr_t>(f) | reinterpret_cast<uintptr_t>(u0) | reinterpret_cast<uintptr_t>(theta)) & 7u)
+    SRPDE_FAIL(kErrAlign, "%s: a pointer is not 8-byte aligned", name);
+  if (!(rtol >= 0.0)) SRPDE_FAIL(kErrArg, "%s: rtol=%g must be >= 0", name, rtol);
   if (int rc = div_check_plan(name, n, plan, plan_bytes)) return rc;
   if (int rc = div_check_ws(name, B, n, ws, ws_bytes)) return rc;
   DivCG g = carve(ws, B, n);
-  hipLaunchKernelGGL(div_init_kernel, div_grid(B, n), dim3(kDivThreads), 0, stream, f, g);
+  const double inv_h2 = (double)(n - 1) * (double)(n - 1);
+  const dim3 grid = div_grid(B, n), block(kDivThreads);
+  if (sigma != 0.0) {
+    if (face_mean)
+      hipLaunchKernelGGL((div_init_from_kernel<true, true>), grid, block, 0, stream, f, u0, theta, g, inv_h2, sigma);
+    else
+      hipLaunchKernelGGL((div_init_from_kernel<false, true>), grid, block, 0, stream, f, u0, theta, g, inv_h2, sigma);
+  } else if (face_mean) {
+    hipLaunchKernelGGL((div_init_from_kernel<true, false>), grid, block, 0, stream, f, u0, theta, g, inv_h2, 0.0);
+  } else {
+    hipLaunchKernelGGL((div_init_from_kernel<false, false>), grid, block, 0, stream, f, u0, theta, g, inv_h2, 0.0);
+  }
   SRPDE_LAUNCH_CHECK(name);
-  if (int rc = dst_solve_launch(name, g.r, nullptr, g.z, B, n, plan, g.dst_ws, stream)) return rc;
-  // rtol 0: only |f| = 0 is done before the first iteration
-  hipLaunchKernelGGL(div_rz_kernel, div_grid(B, n), dim3(kDivThreads), 0, stream, g, 0, 0.0);
+  if (int rc = dst_solve_launch(name, g.r, nullptr, g.z, B, n, plan, g.dst_ws, stream, sigma_p)) return rc;
+  hipLaunchKernelGGL(div_rz_from_kernel, grid, block, 0, stream, g, rtol);
   SRPDE_LAUNCH_CHECK(name);
   return 0;
 }
@@ -508,26 +666,15 @@ int srpde_div_cg_init(const double* f, int B, int n, const void* plan, size_t pl
 int srpde_div_cg_init_from(const double* f, const double* u0, const double* theta, int B, int n, int face_mean,
                            double rtol, const void* plan, size_t plan_bytes, void* ws, size_t ws_bytes,
                            hipStream_t stream) {
-  const char* name = "srpde_div_cg_init_from";
-  SRPDE_CHECK_ARG(f && u0 && theta, "srpde_div_cg_init_from: null pointer");
-  if (int rc = div_check(name, B, n, face_mean)) return rc;
-  if ((reinterpret_cast<uintptr_t>(f) | reinterpret_cast<uintptr_t>(u0) | reinterpret_cast<uintptr_t>(theta)) & 7u)
-    SRPDE_FAIL(kErrAlign, "srpde_div_cg_init_from: a pointer is not 8-byte aligned");
-  if (!(rtol >= 0.0)) SRPDE_FAIL(kErrArg, "srpde_div_cg_init_from: rtol=%g must be >= 0", rtol);
-  if (int rc = div_check_plan(name, n, plan, plan_bytes)) return rc;
-  if (int rc = div_check_ws(name, B, n, ws, ws_bytes)) return rc;
-  DivCG g = carve(ws, B, n);
-  const double inv_h2 = (double)(n - 1) * (double)(n - 1);
-  const dim3 grid = div_grid(B, n), block(kDivThreads);
-  if (face_mean)
-    hipLaunchKernelGGL(div_init_from_kernel<true>, grid, block, 0, stream, f, u0, theta, g, inv_h2);
-  else
-    hipLaunchKernelGGL(div_init_from_kernel<false>, grid, block, 0, stream, f, u0, theta, g, inv_h2);
-  SRPDE_LAUNCH_CHECK(name);
-  if (int rc = dst_solve_launch(name, g.r, nullptr, g.z, B, n, plan, g.dst_ws, stream)) return rc;
-  hipLaunchKernelGGL(div_rz_from_kernel, grid, block, 0, stream, g, rtol);
-  SRPDE_LAUNCH_CHECK(name);
-  return 0;
+  return div_cg_init_from("srpde_div_cg_init_from", f, u0, theta, B, n, face_mean, 0.0, 0.0, rtol, plan, plan_bytes,
+                          ws, ws_bytes, stream);
+}
+
+int srpde_div_cg_init_from_shift(const double* f, const double* u0, const double* theta, int B, int n, int face_mean,
+                                 double sigma, double sigma_p, double rtol, const void* plan, size_t plan_bytes,
+                                 void* ws, size_t ws_bytes, hipStream_t stream) {
+  return div_cg_init_from("srpde_div_cg_init_from_shift", f, u0, theta, B, n, face_mean, sigma, sigma_p, rtol, plan,
+                          plan_bytes, ws, ws_bytes, stream);
 }
 
 int srpde_div_theta_grad(const double* u, const double* lam, const double* theta, double* g_out, int B, int n,
@@ -553,32 +700,61 @@ int srpde_div_theta_grad(const double* u, const double* lam, const double* theta
   return 0;
 }
 
-int srpde_div_cg_iterate(const double* theta, int B, int n, int face_mean, double rtol, int k_begin, int k_count,
-                         const void* plan, size_t plan_bytes, void* ws, size_t ws_bytes, hipStream_t stream) {
-  const char* name = "srpde_div_cg_iterate";
-  SRPDE_CHECK_ARG(theta, "srpde_div_cg_iterate: null pointer");
+static int div_cg_iterate(const char* name, const double* theta, int B, int n, int face_mean, double sigma,
+                          double sigma_p, double rtol, int k_begin, int k_count, const void* plan, size_t plan_bytes,
+                          void* ws, size_t ws_bytes, hipStream_t stream) {
+  SRPDE_CHECK_ARG(theta, "%s: null pointer", name);
   if (int rc = div_check(name, B, n, face_mean)) return rc;
-  if (reinterpret_cast<uintptr_t>(theta) & 7u) SRPDE_FAIL(kErrAlign, "srpde_div_cg_iterate: theta not 8-byte aligned");
-  if (!(rtol >= 0.0)) SRPDE_FAIL(kErrArg, "srpde_div_cg_iterate: rtol=%g must be >= 0", rtol);
+  if (int rc = div_check_sigma(name, "sigma", sigma)) return rc;
+  if (int rc = div_check_sigma(name, "sigma_p", sigma_p)) return rc;
+  if (reinterpret_cast<uintptr_t>(theta) & 7u) SRPDE_FAIL(kErrAlign, "%s: theta not 8-byte aligned", name);
+  if (!(rtol >= 0.0)) SRPDE_FAIL(kErrArg, "%s: rtol=%g must be >= 0", name, rtol);
   if (k_begin < 1 || k_count < 0 || k_count > INT32_MAX - k_begin)
-    SRPDE_FAIL(kErrArg, "srpde_div_cg_iterate: k_begin=%d k_count=%d (iterations count from 1)", k_begin, k_count);
+    SRPDE_FAIL(kErrArg, "%s: k_begin=%d k_count=%d (iterations count from 1)", name, k_begin, k_count);
   if (int rc = div_check_plan(name, n, plan, plan_bytes)) return rc;
   if (int rc = div_check_ws(name, B, n, ws, ws_bytes)) return rc;
   DivCG g = carve(ws, B, n);
   const double inv_h2 = (double)(n - 1) * (double)(n - 1);
   const dim3 grid = div_grid(B, n), block(kDivThreads);
+  const int variant = (sigma != 0.0 ? 2 : 0) + (face_mean ? 1 : 0);
   for (int k = k_begin; k < k_begin + k_count; ++k) {
-    if (face_mean)
-      hipLaunchKernelGGL((div_apply_kernel<true, true>), grid, block, 0, stream, g.z, theta, g.q, g, inv_h2, n, k);
-    else
-      hipLaunchKernelGGL((div_apply_kernel<true, false>), grid, block, 0, stream, g.z, theta, g.q, g, inv_h2, n, k);
+    switch (variant) {
+      case 0:
+        hipLaunchKernelGGL((div_apply_kernel<true, false, false>), grid, block, 0, stream, g.z, theta, g.q, g, inv_h2,
+                           0.0, n, k);
+        break;
+      case 1:
+        hipLaunchKernelGGL((div_apply_kernel<true, true, false>), grid, block, 0, stream, g.z, theta, g.q, g, inv_h2,
+                           0.0, n, k);
+        break;
+      case 2:
+        hipLaunchKernelGGL((div_apply_kernel<true, false, true>), grid, block, 0, stream, g.z, theta, g.q, g, inv_h2,
+                           sigma, n, k);
+        break;
+      default:
+        hipLaunchKernelGGL((div_apply_kernel<true, true, true>), grid, block, 0, stream, g.z, theta, g.q, g, inv_h2,
+                           sigma, n, k);
+    }
     hipLaunchKernelGGL(div_update_kernel, grid, block, 0, stream, g, k);
     SRPDE_LAUNCH_CHECK(name);
-    if (int rc = dst_solve_launch(name, g.r, nullptr, g.z, B, n, plan, g.dst_ws, stream)) return rc;
+    if (int rc = dst_solve_launch(name, g.r, nullptr, g.z, B, n, plan, g.dst_ws, stream, sigma_p)) return rc;
     hipLaunchKernelGGL(div_rz_kernel, grid, block, 0, stream, g, k, rtol);
     SRPDE_LAUNCH_CHECK(name);
   }
   return 0;
+}
+
+int srpde_div_cg_iterate(const double* theta, int B, int n, int face_mean, double rtol, int k_begin, int k_count,
+                         const void* plan, size_t plan_bytes, void* ws, size_t ws_bytes, hipStream_t stream) {
+  return div_cg_iterate("srpde_div_cg_iterate", theta, B, n, face_mean, 0.0, 0.0, rtol, k_begin, k_count, plan,
+                        plan_bytes, ws, ws_bytes, stream);
+}
+
+int srpde_div_cg_iterate_shift(const double* theta, int B, int n, int face_mean, double sigma, double sigma_p,
+                               double rtol, int k_begin, int k_count, const void* plan, size_t plan_bytes, void* ws,
+                               size_t ws_bytes, hipStream_t stream) {
+  return div_cg_iterate("srpde_div_cg_iterate_shift", theta, B, n, face_mean, sigma, sigma_p, rtol, k_begin, k_count,
+                        plan, plan_bytes, ws, ws_bytes, stream);
 }
 
 int srpde_div_cg_finish(double* u, int* iters, double* resid, int B, int n, void* ws, size_t ws_bytes,

@@ -24,8 +24,15 @@
 // Both use v_mfma_f64_16x16x4_f64.  Lane l gives A[row l & 15][k = l >> 4] and B[k = l >> 4][col l & 15] and
 // holds C[row (l >> 4) + 4 r][col l & 15] in register r = 0..3 (not the f32 16x16 map).
 //
+// Shifted solve (srpde_poisson_dst_shift_batched, the preconditioner of the shifted CG of poisson_div.hip): S
+// diagonalises L - sigma I as well, with eigenvalues (lam_i + lam_j) / h^2 - sigma, so the same products solve
+// (L - sigma I) u = f once the scaling h^2 / (lam_i + lam_j) becomes dst_shift_scale's 1 / ((lam_i + lam_j) inv_h2 -
+// sigma).  It is a template argument of the two kernels that scale; sigma = 0 launches the unshifted instantiations.
+//
 // The k order of every sum is ascending and fixed by n alone, there are no atomics, and a problem's blocks
 // never see another problem: results are bit-reproducible and independent of B.
+#include <cmath>
+
 #include "common.h"
 #include "field_reduce.h"
 #include "poisson_dst.h"
@@ -58,6 +65,15 @@ __global__ __launch_bounds__(256) void dst_plan_kernel(int n, double* __restrict
   }
 }
 
+// The shifted eigenvalue scaling, every operation rounded once in this order (no contraction): the sum lam_i + lam_j,
+// times inv_h2 = (n - 1)^2, minus sigma, then the reciprocal.  sigma >= 0 and the sum is negative: never 0.
+__device__ __forceinline__ double dst_shift_scale(double li, double lj, double inv_h2, double sigma) {
+#pragma clang fp contract(off)
+  const double s = li + lj;
+  const double d = s * inv_h2;
+  return 1.0 / (d - sigma);
+}
+
 // ---- general path ------------------------------------------------------------------------------------------
 constexpr int kGT = 64;            // block tile (rows and columns); four waves, 32 x 32 each
 constexpr int kGK = 16;            // k per LDS stage
@@ -66,13 +82,15 @@ constexpr int kGLdB = kGT + 16;    // Bs[k][c]: the two k rows of a half wave la
 
 // C[b] = A[b] B[b], all [n][n] row-major, batch strides sA / sB / sC in elements (0: shared by every problem).
 // DIV: A's elements are divided by th's (same indexing as A) as they are loaded.
-// SCALE: C[i][j] is multiplied by h2 / (lam[i] + lam[j]) as it is stored.
-template <bool DIV, bool SCALE>
+// SCALE 1: C[i][j] is multiplied by h2 / (lam[i] + lam[j]) as it is stored; SCALE 2: by dst_shift_scale(lam[i],
+// lam[j], inv_h2, sigma) instead.
+template <bool DIV, int SCALE>
 __global__ __launch_bounds__(256) void dst_gemm_kernel(const double* __restrict__ A, long long sA,
                                                        const double* __restrict__ Bm, long long sB,
                                                        double* __restrict__ C, long long sC,
                                                        const double* __restrict__ th, const double* __restrict__ lam,
-                                                       double h2, int n, int nbatch) {
+                                                       double h2, double inv_h2, double sigma, int n,
+                                                       int nbatch) {
   __shared__ double As[kGT * kGLdA];
   __shared__ double Bs[kGK * kGLdB];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -141,7 +159,8 @@ __global__ __launch_bounds__(256) void dst_gemm_kernel(const double* __restrict_
           const int row = m0 + wr + 16 * i + l4 + 4 * r;
           if (row < n && col < n) {
             double v = acc[i][j][r];
-            if (SCALE) v = v * (h2 / (lam[row] + lam[col]));
+            if (SCALE == 1) v = v * (h2 / (lam[row] + lam[col]));
+            if (SCALE == 2) v = v * dst_shift_scale(lam[row], lam[col], inv_h2, sigma);
             Cb[(long long)row * n + col] = v;
           }
         }
@@ -157,6 +176,7 @@ __global__ __launch_bounds__(256) void dst_gemm_kernel(const double* __restrict_
 // symmetry, S[m][k] = S[k][m], so S is always read along its rows); the last one goes to global memory.
 // SOLVE: h^2 / (lam_i + lam_j) after the second product, four products; else two (y = S x S).
 // DIV: x / theta at the load (without it SOLVE is the plain L u = x, the preconditioner of poisson_div.hip).
+// SHIFT (with SOLVE): dst_shift_scale after the second product instead, (L - sigma I) u = x.
 constexpr int kFusedGroupTiles = 3;
 
 static int dst_fused_np(int n) { return (n + 15) & ~15; }
@@ -169,10 +189,11 @@ static size_t dst_fused_lds(int n) {
   return (size_t)2 * np * (np + 2) * sizeof(double);
 }
 
-template <bool SOLVE, bool DIV>
+template <bool SOLVE, bool DIV, bool SHIFT>
 __global__ __launch_bounds__(768) void dst_fused_kernel(const double* __restrict__ x, const double* __restrict__ th,
                                                         double* __restrict__ y, const double* __restrict__ S,
-                                                        const double* __restrict__ lam, double h2, int n) {
+                                                        const double* __restrict__ lam, double h2, double inv_h2,
+                                                        double sigma, int n) {
   extern __shared__ double dst_lds[];
   const int np = (n + 15) & ~15, ld = np + 2;
   double* Sl = dst_lds;
@@ -231,7 +252,8 @@ __global__ __launch_bounds__(768) void dst_fused_kernel(const double* __restrict
           const int row = row0 + l4 + 4 * r;
           const bool in = row < n && col < n;
           double v = acc[j][r];
-          if (SOLVE && p == 1) v = in ? v * (h2 / (lam[row] + lam[col])) : 0.0;
+          if (SOLVE && !SHIFT && p == 1) v = in ? v * (h2 / (lam[row] + lam[col])) : 0.0;
+          if (SOLVE && SHIFT && p == 1) v = in ? v * dst_shift_scale(lam[row], lam[col], inv_h2, sigma) : 0.0;
           if (last) {
             if (in) yb[row * n + col] = v;
           } else {
@@ -243,46 +265,60 @@ __global__ __launch_bounds__(768) void dst_fused_kernel(const double* __restrict
   }
 }
 
-static int gemm_launch(bool div, bool scale, const double* A, long long sA, const double* Bm, long long sB, double* C,
-                       long long sC, const double* th, const double* lam, double h2, int n, int B,
-                       hipStream_t stream) {
+// scale: 0 none, 1 h2 / (lam + lam), 2 dst_shift_scale with inv_h2 and sigma
+static int gemm_launch(bool div, int scale, const double* A, long long sA, const double* Bm, long long sB, double* C,
+                       long long sC, const double* th, const double* lam, double h2, int n, int B, hipStream_t stream,
+                       double inv_h2 = 0.0, double sigma = 0.0) {
   const int t = ceil_div(n, kGT);
   const dim3 grid(t, t, std::min(B, 65535)), block(256);
   if (div)
-    hipLaunchKernelGGL((dst_gemm_kernel<true, false>), grid, block, 0, stream, A, sA, Bm, sB, C, sC, th, lam, h2, n, B);
-  else if (scale)
-    hipLaunchKernelGGL((dst_gemm_kernel<false, true>), grid, block, 0, stream, A, sA, Bm, sB, C, sC, th, lam, h2, n, B);
+    hipLaunchKernelGGL((dst_gemm_kernel<true, 0>), grid, block, 0, stream, A, sA, Bm, sB, C, sC, th, lam, h2, inv_h2,
+                       sigma, n, B);
+  else if (scale == 1)
+    hipLaunchKernelGGL((dst_gemm_kernel<false, 1>), grid, block, 0, stream, A, sA, Bm, sB, C, sC, th, lam, h2, inv_h2,
+                       sigma, n, B);
+  else if (scale == 2)
+    hipLaunchKernelGGL((dst_gemm_kernel<false, 2>), grid, block, 0, stream, A, sA, Bm, sB, C, sC, th, lam, h2, inv_h2,
+                       sigma, n, B);
   else
-    hipLaunchKernelGGL((dst_gemm_kernel<false, false>), grid, block, 0, stream, A, sA, Bm, sB, C, sC, th, lam, h2, n, B);
+    hipLaunchKernelGGL((dst_gemm_kernel<false, 0>), grid, block, 0, stream, A, sA, Bm, sB, C, sC, th, lam, h2, inv_h2,
+                       sigma, n, B);
   return 0;
 }
 
-// u = L^-1 (f / theta) for B problems, theta == nullptr: no division (u = L^-1 f).  Arguments already checked.
+// u = L^-1 (f / theta) for B problems, theta == nullptr: no division (u = L^-1 f).  sigma > 0 (theta == nullptr
+// only): u = (L - sigma I)^-1 f; sigma = 0 is the unshifted code, kernel for kernel.  Arguments already checked.
 int dst_solve_launch(const char* name, const double* f, const double* theta, double* u, int B, int n, const void* plan,
-                     void* ws, hipStream_t stream) {
+                     void* ws, hipStream_t stream, double sigma) {
   const double* S = static_cast<const double*>(plan);
   const double* lam = S + (size_t)n * n;
   const double h = 1.0 / (double)(n - 1), h2 = h * h;
+  const double inv_h2 = (double)(n - 1) * (double)(n - 1);
+  const bool shift = sigma != 0.0;
   if (n <= kDstLdsMaxN) {
     const dim3 grid(B), block(64 * dst_fused_waves(n));
-    if (theta)
-      hipLaunchKernelGGL((dst_fused_kernel<true, true>), grid, block, dst_fused_lds(n), stream, f, theta, u, S, lam, h2,
-                         n);
+    if (shift)
+      hipLaunchKernelGGL((dst_fused_kernel<true, false, true>), grid, block, dst_fused_lds(n), stream, f, theta, u, S,
+                         lam, h2, inv_h2, sigma, n);
+    else if (theta)
+      hipLaunchKernelGGL((dst_fused_kernel<true, true, false>), grid, block, dst_fused_lds(n), stream, f, theta, u, S,
+                         lam, h2, 0.0, 0.0, n);
     else
-      hipLaunchKernelGGL((dst_fused_kernel<true, false>), grid, block, dst_fused_lds(n), stream, f, theta, u, S, lam,
-                         h2, n);
+      hipLaunchKernelGGL((dst_fused_kernel<true, false, false>), grid, block, dst_fused_lds(n), stream, f, theta, u, S,
+                         lam, h2, 0.0, 0.0, n);
     SRPDE_LAUNCH_CHECK(name);
     return 0;
   }
   const long long nn = (long long)n * n;
   double* w = static_cast<double*>(ws);
-  gemm_launch(theta != nullptr, false, f, nn, S, 0, w, nn, theta, lam, h2, n, B, stream);   // w = (f / theta) S
+  gemm_launch(theta != nullptr, 0, f, nn, S, 0, w, nn, theta, lam, h2, n, B, stream);   // w = (f / theta) S
   SRPDE_LAUNCH_CHECK(name);
-  gemm_launch(false, true, S, 0, w, nn, u, nn, nullptr, lam, h2, n, B, stream);   // u = (S w) o h^2 / (lam + lam)
+  // u = (S w) o h^2 / (lam + lam), or o dst_shift_scale
+  gemm_launch(false, shift ? 2 : 1, S, 0, w, nn, u, nn, nullptr, lam, h2, n, B, stream, inv_h2, sigma);
   SRPDE_LAUNCH_CHECK(name);
-  gemm_launch(false, false, u, nn, S, 0, w, nn, nullptr, lam, h2, n, B, stream);  // w = u S
+  gemm_launch(false, 0, u, nn, S, 0, w, nn, nullptr, lam, h2, n, B, stream);  // w = u S
   SRPDE_LAUNCH_CHECK(name);
-  gemm_launch(false, false, S, 0, w, nn, u, nn, nullptr, lam, h2, n, B, stream);  // u = S w
+  gemm_launch(false, 0, S, 0, w, nn, u, nn, nullptr, lam, h2, n, B, stream);  // u = S w
   SRPDE_LAUNCH_CHECK(name);
   return 0;
 }
@@ -345,6 +381,18 @@ int srpde_poisson_dst_batched(const double* f, const double* theta, double* u, i
   return dst_solve_launch(name, f, theta, u, B, n, plan, ws, stream);
 }
 
+int srpde_poisson_dst_shift_batched(const double* f, double* u, int B, int n, double sigma_p, const void* plan,
+                                    size_t plan_bytes, void* ws, size_t ws_bytes, hipStream_t stream) {
+  const char* name = "srpde_poisson_dst_shift_batched";
+  SRPDE_CHECK_ARG(f && u && plan, "srpde_poisson_dst_shift_batched: null pointer");
+  if (!(sigma_p >= 0.0) || !std::isfinite(sigma_p))
+    SRPDE_FAIL(kErrArg, "srpde_poisson_dst_shift_batched: sigma_p=%g must be >= 0 and finite", sigma_p);
+  if ((reinterpret_cast<uintptr_t>(f) | reinterpret_cast<uintptr_t>(u)) & 7u)
+    SRPDE_FAIL(kErrAlign, "srpde_poisson_dst_shift_batched: a pointer is not 8-byte aligned");
+  if (int rc = dst_check(name, B, n, 2, plan, plan_bytes, ws, ws_bytes)) return rc;
+  return dst_solve_launch(name, f, nullptr, u, B, n, plan, ws, stream, sigma_p);
+}
+
 int srpde_poisson_dst_apply(const double* x, double* y, int B, int n, const void* plan, size_t plan_bytes, void* ws,
                             size_t ws_bytes, hipStream_t stream) {
   const char* name = "srpde_poisson_dst_apply";
@@ -353,16 +401,16 @@ int srpde_poisson_dst_apply(const double* x, double* y, int B, int n, const void
   const double* S = static_cast<const double*>(plan);
   const double* lam = S + (size_t)n * n;
   if (n <= kDstLdsMaxN) {
-    hipLaunchKernelGGL((dst_fused_kernel<false, false>), dim3(B), dim3(64 * dst_fused_waves(n)), dst_fused_lds(n), stream, x,
-                       nullptr, y, S, lam, 0.0, n);
+    hipLaunchKernelGGL((dst_fused_kernel<false, false, false>), dim3(B), dim3(64 * dst_fused_waves(n)),
+                       dst_fused_lds(n), stream, x, nullptr, y, S, lam, 0.0, 0.0, 0.0, n);
     SRPDE_LAUNCH_CHECK(name);
     return 0;
   }
   const long long nn = (long long)n * n;
   double* w = static_cast<double*>(ws);
-  gemm_launch(false, false, x, nn, S, 0, w, nn, nullptr, lam, 0.0, n, B, stream);   // w = x S
+  gemm_launch(false, 0, x, nn, S, 0, w, nn, nullptr, lam, 0.0, n, B, stream);   // w = x S
   SRPDE_LAUNCH_CHECK(name);
-  gemm_launch(false, false, S, 0, w, nn, y, nn, nullptr, lam, 0.0, n, B, stream);   // y = S w
+  gemm_launch(false, 0, S, 0, w, nn, y, nn, nullptr, lam, 0.0, n, B, stream);   // y = S w
   SRPDE_LAUNCH_CHECK(name);
   return 0;
 }

@@ -71,12 +71,7 @@ def default_pcg_iters(theta_range, tol: float = 1e-12, margin: int = 4) -> int:
     lo, hi = (float(v) for v in theta_range)
     if not 0.0 < lo <= hi:
         raise ValueError(f"theta_range {theta_range}: 0 < lo <= hi")
-    s = (hi / lo) ** 0.5
-    rho = (s - 1.0) / (s + 1.0)
-    k = 0
-    while 2.0 * rho ** k > tol:
-        k += 1
-    return k + margin
+    return P.pcg_iterations(lo, hi, tol) + margin     # the bound itself: also diffuse's, for any time step
 
 
 def slot_kinds(n: int, sub_fraction: float) -> list:

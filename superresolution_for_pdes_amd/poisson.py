@@ -23,7 +23,9 @@ by CG preconditioned with the sine-transform solve of L, whose iteration count i
 does not grow with n.  Opt-in as well: every default stays pointwise.  ``apply_div`` and ``solve_div`` are
 differentiable in their fields and in theta (the operator is symmetric, so the solve's adjoint is the same solve;
 ``div_theta_grad`` is the one local pass the theta gradient needs), and ``solve_div(..., u0=)`` starts the iteration
-from a guess.
+from a guess.  ``shift=`` on both makes the operator div(theta grad u) - sigma u, preconditioned with the
+sine-transform solve of L - sigma_p I at the same condition bound, and ``diffuse`` steps u_t = div(theta grad u) - f
+implicitly with it (backward Euler or Crank-Nicolson), each solve warm-started from the previous state.
 """
 from __future__ import annotations
 
@@ -180,12 +182,53 @@ def _wants_grad(*tensors) -> bool:
     return torch.is_grad_enabled() and any(t.requires_grad for t in tensors)
 
 
-def _apply_div(u, theta, mean: int, inv_h2: float):
-    """srpde_div_apply on prepared fields (_div_fields)."""
+def check_shift(shift, what: str = "shift") -> float:
+    """A shift sigma of D_theta - sigma I (or of the preconditioner L - sigma_p I): finite and >= 0."""
+    shift = float(shift)
+    if not (shift >= 0.0 and np.isfinite(shift)):
+        raise ValueError(f"{what} must be finite and >= 0, got {shift}")
+    return shift
+
+
+def pcg_iterations(theta_lo: float, theta_hi: float, tol: float = 1e-12) -> int:
+    """The smallest k with 2 ((sqrt(c) - 1) / (sqrt(c) + 1))^k <= tol for c = theta_hi / theta_lo: CG's bound at the
+    condition number that theta_max / theta_min bounds for the sine-preconditioned operator -- D_theta, and
+    D_theta - sigma I with the preconditioner L - (sigma / theta_g) I for any sigma >= 0.  A fixed
+    iteration count for ``solve_div(check_every=0)`` and ``diffuse(pcg_iters=)``; add a margin of a few."""
+    lo, hi = float(theta_lo), float(theta_hi)
+    if not 0.0 < lo <= hi:
+        raise ValueError(f"theta range ({theta_lo}, {theta_hi}): 0 < lo <= hi")
+    s = (hi / lo) ** 0.5
+    rho = (s - 1.0) / (s + 1.0)
+    k = 0
+    while 2.0 * rho ** k > tol:
+        k += 1
+    return k
+
+
+def precond_shift_for(theta, shift: float) -> float:
+    """sigma_p = shift / theta_g with theta_g = sqrt(theta_min theta_max) over the whole batch: the default shift of
+    the preconditioner L - sigma_p I.  ONE HOST READ of two device scalars, so not under stream capture."""
+    if shift == 0.0:
+        return 0.0
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("precond_shift=None reads theta's range back (a host sync): give precond_shift under "
+                           "stream capture")
+    lo, hi = torch.stack(torch.aminmax(theta.detach())).tolist()       # the one read
+    if not 0.0 < lo <= hi:
+        raise ValueError(f"theta must be positive (range {lo:g} .. {hi:g})")
+    return shift / float(np.sqrt(lo * hi))
+
+
+def _apply_div(u, theta, mean: int, inv_h2: float, shift: float = 0.0):
+    """srpde_div_apply (shift 0: today's call) or srpde_div_apply_shift on prepared fields (_div_fields)."""
     y = torch.empty_like(u)
-    if u.shape[0]:
+    if u.shape[0] and shift == 0.0:
         call("srpde_div_apply", u.data_ptr(), theta.data_ptr(), y.data_ptr(), u.shape[0], u.shape[-1], mean,
              inv_h2, stream_ptr(u.device))
+    elif u.shape[0]:
+        call("srpde_div_apply_shift", u.data_ptr(), theta.data_ptr(), y.data_ptr(), u.shape[0], u.shape[-1], mean,
+             inv_h2, shift, stream_ptr(u.device))
     return y
 
 
@@ -215,35 +258,37 @@ def div_theta_grad(u, lam, theta, face_mean: str = "harmonic", inv_h2: float = N
 
 
 class _ApplyDiv(torch.autograd.Function):
-    """y = D_theta u.  D_theta is symmetric: grad_u = D_theta grad_y; grad_theta = -G(u, grad_y; theta)."""
+    """y = D_theta u - shift u.  The operator is symmetric: grad_u = (D_theta - shift) grad_y; the shift does not
+    depend on theta, so grad_theta = -G(u, grad_y; theta) as without it."""
 
     @staticmethod
-    def forward(ctx, u, theta, mean, inv_h2):
+    def forward(ctx, u, theta, mean, inv_h2, shift=0.0):
         u, theta = u.detach().contiguous(), theta.detach().contiguous()
         ctx.save_for_backward(u, theta)
-        ctx.mean, ctx.inv_h2 = mean, inv_h2
-        return _apply_div(u, theta, mean, inv_h2)
+        ctx.mean, ctx.inv_h2, ctx.shift = mean, inv_h2, shift
+        return _apply_div(u, theta, mean, inv_h2, shift)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gy):
         u, theta = ctx.saved_tensors
         gy = gy.contiguous()
-        gu = _apply_div(gy, theta, ctx.mean, ctx.inv_h2) if ctx.needs_input_grad[0] else None
+        gu = _apply_div(gy, theta, ctx.mean, ctx.inv_h2, ctx.shift) if ctx.needs_input_grad[0] else None
         gth = _div_theta_grad(u, gy, theta, ctx.mean, ctx.inv_h2, -1.0) if ctx.needs_input_grad[1] else None
-        return gu, gth, None, None
+        return gu, gth, None, None, None
 
 
 class _SolveDiv(torch.autograd.Function):
-    """u = D_theta^-1 f.  The adjoint solve is the same solve: lam = D_theta^-1 grad_u with the forward's face mean,
-    tolerance and limits, from a zero start; grad_f = lam; grad_theta = +G(u, lam; theta).  Nothing depends on u0."""
+    """u = (D_theta - shift)^-1 f.  The adjoint solve is the same solve: lam = (D_theta - shift)^-1 grad_u with the
+    forward's face mean, tolerance, limits, shift and preconditioner shift, from a zero start; grad_f = lam;
+    grad_theta = +G(u, lam; theta), the shift not depending on theta.  Nothing depends on u0."""
 
     @staticmethod
-    def forward(ctx, f, theta, u0, mean, rtol, maxit, check_every, check):
+    def forward(ctx, f, theta, u0, mean, rtol, maxit, check_every, check, shift=0.0, pshift=0.0):
         f, theta = f.detach().contiguous(), theta.detach().contiguous()
-        u, iters, resid = _solve_div(f, theta, u0, mean, rtol, maxit, check_every, check)
+        u, iters, resid = _solve_div(f, theta, u0, mean, rtol, maxit, check_every, check, shift, pshift)
         ctx.save_for_backward(u, theta)
-        ctx.args = (mean, rtol, maxit, check_every, check)
+        ctx.args = (mean, rtol, maxit, check_every, check, shift, pshift)
         ctx.mark_non_differentiable(iters, resid)
         return u, iters, resid
 
@@ -256,27 +301,33 @@ class _SolveDiv(torch.autograd.Function):
         gth = None
         if ctx.needs_input_grad[1]:
             gth = _div_theta_grad(u, lam, theta, mean, float((u.shape[-1] - 1) ** 2), 1.0)
-        return (lam if ctx.needs_input_grad[0] else None), gth, None, None, None, None, None, None
+        return (lam if ctx.needs_input_grad[0] else None), gth, None, None, None, None, None, None, None, None
 
 
-def apply_div(u, theta, face_mean: str = "harmonic", inv_h2: float = None, device="cuda"):
+def apply_div(u, theta, face_mean: str = "harmonic", inv_h2: float = None, device="cuda", shift: float = 0.0):
     """y = div(theta grad u) on the project's grid (zero ghost ring, h = 1 / (n - 1)): a new [B, n, n] fp64 device
     tensor.  The face coefficient between nodes a and b is 0.5 (ta + tb) (``"arithmetic"``) or 2 ta tb / (ta + tb)
     (``"harmonic"``), theta_a towards the ghost ring; ``inv_h2`` defaults to (n - 1)^2.  One launch, stream-ordered,
     no host sync (srpde_div_apply; include/srpde.h states the rounding order).
 
     Differentiable in u and theta when grad mode is on and one of them requires grad (one more srpde_div_apply for
-    u, one srpde_div_theta_grad for theta; once differentiable); otherwise exactly the call above."""
+    u, one srpde_div_theta_grad for theta; once differentiable); otherwise exactly the call above.
+
+    ``shift`` (sigma >= 0, finite): y = div(theta grad u) - sigma u, the operator of an implicit time step, in the
+    same launch (srpde_div_apply_shift: the product sigma * u, then one subtraction).  The gradient in u carries the
+    shift, the one in theta does not change, the shift itself gets none.  0.0 (default) is exactly today's call."""
     mean = check_face_mean(face_mean)
+    shift = check_shift(shift)
     u, theta, B, n = _div_fields(u, theta, device)
     inv_h2 = float((n - 1) ** 2 if inv_h2 is None else inv_h2)
     if _wants_grad(u, theta):
-        return _ApplyDiv.apply(u, theta, mean, inv_h2)
-    return _apply_div(u, theta, mean, inv_h2)
+        return _ApplyDiv.apply(u, theta, mean, inv_h2, shift)
+    return _apply_div(u, theta, mean, inv_h2, shift)
 
 
 def solve_div(f, theta, face_mean: str = "harmonic", rtol: float = DEFAULT_RTOL, maxit: int = None,
-              check_every: int = 8, check: bool = True, return_info: bool = False, device="cuda", u0=None):
+              check_every: int = 8, check: bool = True, return_info: bool = False, device="cuda", u0=None,
+              shift: float = 0.0, precond_shift: float = None):
     """u[B, n, n] (float64, on device) with div(theta grad u) = f per problem, by CG preconditioned with the
     sine-transform solve of the constant-coefficient operator (srpde_div_cg_*).  Convergence, |r| <= rtol |f|, is
     decided per problem on the device, and a converged problem is frozen, so a problem's u / iters / resid are the
@@ -297,8 +348,24 @@ def solve_div(f, theta, face_mean: str = "harmonic", rtol: float = DEFAULT_RTOL,
     backward is one more solve with the same theta, face_mean, rtol, maxit and check_every from a zero start (the
     operator is symmetric), which raises NotConverged like the forward, and, if theta needs a gradient, one
     srpde_div_theta_grad.  u0 gets no gradient (the solution does not depend on it); iters and resid are not
-    differentiable.  Without a tensor that requires grad, or under no_grad, exactly the calls above."""
+    differentiable.  Without a tensor that requires grad, or under no_grad, exactly the calls above.
+
+    ``shift`` (sigma >= 0, finite): solves div(theta grad u) - sigma u = f, one implicit time step or the screened
+    problem (srpde_div_cg_*_shift), preconditioned with the sine-transform solve of L - sigma_p I.  ``precond_shift``
+    is sigma_p; None takes sigma / sqrt(theta_min theta_max) over the batch, which is one host read of theta's range:
+    in fixed-iteration mode (``check_every=0``) and under stream capture it must be given.  Any sigma_p = sigma /
+    theta_g with theta_g in theta's range keeps cond <= theta_max / theta_min, so the iteration count is at most the
+    unshifted one's bound (``pcg_iterations``) for every sigma.  The adjoint solve uses the same two shifts; the shift
+    gets no gradient.  ``shift=0.0`` (default; ``precond_shift`` must then be None or 0) makes exactly today's calls."""
     mean = check_face_mean(face_mean)
+    shift = check_shift(shift)
+    if precond_shift is not None:
+        precond_shift = check_shift(precond_shift, "precond_shift")
+        if shift == 0.0 and precond_shift != 0.0:
+            raise ValueError("solve_div: precond_shift belongs to a shifted solve (shift > 0)")
+    elif shift != 0.0 and (int(check_every) == 0 or torch.cuda.is_current_stream_capturing()):
+        raise ValueError("solve_div: precond_shift=None reads theta's range back (a host sync): give precond_shift "
+                         "in fixed-iteration mode (check_every=0) and under stream capture")
     f, theta, B, n = _div_fields(f, theta, device)
     if u0 is not None:
         u0 = _dev_f64(u0, device).detach()
@@ -312,19 +379,28 @@ def solve_div(f, theta, face_mean: str = "harmonic", rtol: float = DEFAULT_RTOL,
     maxit, check_every = int(maxit), int(check_every)
     if maxit < 0 or check_every < 0:
         raise ValueError("solve_div: maxit and check_every must be >= 0")
-    if _wants_grad(f, theta):
-        out = _SolveDiv.apply(f, theta, u0, mean, float(rtol), maxit, check_every, bool(check))
+    if shift == 0.0:
+        pshift = 0.0
     else:
-        out = _solve_div(f, theta, u0, mean, float(rtol), maxit, check_every, bool(check))
+        pshift = precond_shift_for(theta, shift) if precond_shift is None else precond_shift
+    if _wants_grad(f, theta):
+        out = _SolveDiv.apply(f, theta, u0, mean, float(rtol), maxit, check_every, bool(check), shift, pshift)
+    else:
+        out = _solve_div(f, theta, u0, mean, float(rtol), maxit, check_every, bool(check), shift, pshift)
     return out if return_info else out[0]
 
 
-def _solve_div(f, theta, u0, mean: int, rtol: float, maxit: int, check_every: int, check: bool):
-    """The srpde_div_cg_* call sequence on prepared fields -> (u, iters, resid)."""
+def _solve_div(f, theta, u0, mean: int, rtol: float, maxit: int, check_every: int, check: bool, shift: float = 0.0,
+               pshift: float = 0.0, ws=None, out=None):
+    """The srpde_div_cg_* call sequence on prepared fields -> (u, iters, resid); shift 0 is the unshifted entries'
+    sequence, call for call.  ``ws`` / ``out`` = (u, iters, resid): the caller's buffers (diffuse reuses them)."""
     B, n = f.shape[0], f.shape[-1]
-    u = torch.empty_like(f)
-    iters = torch.empty(B, dtype=torch.int32, device=f.device)
-    resid = torch.empty(B, dtype=torch.float64, device=f.device)
+    if out is None:
+        u = torch.empty_like(f)
+        iters = torch.empty(B, dtype=torch.int32, device=f.device)
+        resid = torch.empty(B, dtype=torch.float64, device=f.device)
+    else:
+        u, iters, resid = out
     if B == 0:
         return u, iters, resid
     capturing = torch.cuda.is_current_stream_capturing()
@@ -332,9 +408,17 @@ def _solve_div(f, theta, u0, mean: int, rtol: float, maxit: int, check_every: in
         raise RuntimeError("solve_div: reading the done flags synchronises the host; capture with check_every=0")
     plan = dst_plan(n, f.device)
     ws_bytes = int(query("srpde_div_cg_workspace_size", B, n))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=f.device)
+    if ws is None:
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=f.device)
     sp = stream_ptr(f.device)
-    if u0 is None:
+    if shift != 0.0:
+        if u0 is None:
+            call("srpde_div_cg_init_shift", f.data_ptr(), B, n, pshift, plan.data_ptr(), plan.numel(), ws.data_ptr(),
+                 ws_bytes, sp)
+        else:
+            call("srpde_div_cg_init_from_shift", f.data_ptr(), u0.data_ptr(), theta.data_ptr(), B, n, mean, shift,
+                 pshift, rtol, plan.data_ptr(), plan.numel(), ws.data_ptr(), ws_bytes, sp)
+    elif u0 is None:
         call("srpde_div_cg_init", f.data_ptr(), B, n, plan.data_ptr(), plan.numel(), ws.data_ptr(), ws_bytes, sp)
     else:
         call("srpde_div_cg_init_from", f.data_ptr(), u0.data_ptr(), theta.data_ptr(), B, n, mean, rtol,
@@ -346,8 +430,12 @@ def _solve_div(f, theta, u0, mean: int, rtol: float, maxit: int, check_every: in
         k = maxit
     while k < maxit:
         count = min(check_every, maxit - k) if check_every else maxit
-        call("srpde_div_cg_iterate", theta.data_ptr(), B, n, mean, rtol, k + 1, count, plan.data_ptr(),
-             plan.numel(), ws.data_ptr(), ws_bytes, sp)
+        if shift != 0.0:
+            call("srpde_div_cg_iterate_shift", theta.data_ptr(), B, n, mean, shift, pshift, rtol, k + 1, count,
+                 plan.data_ptr(), plan.numel(), ws.data_ptr(), ws_bytes, sp)
+        else:
+            call("srpde_div_cg_iterate", theta.data_ptr(), B, n, mean, rtol, k + 1, count, plan.data_ptr(),
+                 plan.numel(), ws.data_ptr(), ws_bytes, sp)
         k += count
         if check_every and k < maxit and bool(done.all()):
             break
@@ -359,6 +447,106 @@ def _solve_div(f, theta, u0, mean: int, rtol: float, maxit: int, check_every: in
             raise NotConverged(f"solve_div: {nbad} of {B} problems (n={n}) above rtol={rtol:g} after {maxit} "
                                f"iterations; worst residual {float(resid.max()):.3e}")
     return u, iters, resid
+
+
+SCHEMES = ("be", "cn")
+
+
+def diffuse(u0, theta, f=None, dt: float = None, steps: int = 1, scheme: str = "be", face_mean: str = "harmonic",
+            rtol: float = DEFAULT_RTOL, maxit: int = None, pcg_iters: int = None, precond_shift: float = None,
+            save_every: int = None, check: bool = False, check_every: int = 8, device="cuda"):
+    """``steps`` implicit time steps of u_t = div(theta grad u) - f from u0, the forcing constant in time (None: 0),
+    on the project's grid (zero ghost ring).  Each step solves (D_theta - sigma I) u+ = rhs by the shifted
+    sine-preconditioned CG, warm-started from the current state:
+        ``scheme="be"``  backward Euler,  sigma = 1 / dt,  rhs = f - sigma u              (first order, L-stable)
+        ``scheme="cn"``  Crank-Nicolson,  sigma = 2 / dt,  rhs = 2 f - sigma u - D_theta u (second order)
+    u0, f [n, n] or [B, n, n]; theta is broadcast.  -> the final u [B, n, n] fp64; with ``save_every`` = s also the
+    frames after steps s, 2 s, ... as [T, B, n, n]; with ``check`` also the per-step iteration counts [steps, B]
+    int32 -- in that order, as a tuple when there is more than u.
+
+    One step is srpde_div_step_rhs, srpde_div_cg_init_from_shift with u0 = the current state, srpde_div_cg_iterate_
+    shift, srpde_div_cg_finish; the plan, the workspace and sigma_p are made once, outside the loop.
+    ``pcg_iters`` = k selects fixed mode: exactly k iterations per step (converged problems freeze), no host read
+    anywhere in the loop, so the whole loop is capturable in one graph once ``dst_plan(n)`` exists; it needs a
+    ``precond_shift`` (the default, sigma / sqrt(theta_min theta_max), is a host read).  ``pcg_iterations(theta_lo,
+    theta_hi, tol)`` bounds k for every dt.  Without ``pcg_iters`` a step iterates to ``rtol`` in chunks of
+    ``check_every`` (one small host read each, ``maxit`` at most, default 20 n^2) and raises NotConverged above it.
+
+    Differentiable in theta, u0 and f when grad mode is on and one of them requires grad: the steps are then composed
+    from the autograd ``solve_div(shift=, u0=)`` and ``apply_div`` plus torch arithmetic for rhs (same solves, a few
+    more launches and one adjoint solve per step in the backward; once differentiable).  dt and the shift get no
+    gradient.  Otherwise the direct ABI path above."""
+    if scheme not in SCHEMES:
+        raise ValueError(f"unknown time scheme {scheme!r}: one of {SCHEMES}")
+    mean = check_face_mean(face_mean)
+    if dt is None or not (float(dt) > 0.0 and np.isfinite(float(dt))):
+        raise ValueError(f"diffuse: dt must be positive and finite, got {dt}")
+    steps = int(steps)
+    if steps < 0:
+        raise ValueError("diffuse: steps must be >= 0")
+    if save_every is not None and int(save_every) < 1:
+        raise ValueError("diffuse: save_every must be >= 1")
+    cn = SCHEMES.index(scheme)
+    sigma = check_shift((2.0 if cn else 1.0) / float(dt), "1 / dt")
+    fixed = pcg_iters is not None
+    if fixed and int(pcg_iters) < 1:
+        raise ValueError("diffuse: pcg_iters must be >= 1")
+    if precond_shift is not None:
+        precond_shift = check_shift(precond_shift, "precond_shift")
+    elif fixed or torch.cuda.is_current_stream_capturing():
+        raise ValueError("diffuse: precond_shift=None reads theta's range back (a host sync): give precond_shift "
+                         "in fixed mode (pcg_iters) and under stream capture")
+    u, theta, B, n = _div_fields(u0, theta, device)
+    if f is not None:
+        f = _dev_f64(f, device)
+        if f.dim() == 2:
+            f = f.unsqueeze(0)
+        if f.shape != u.shape:
+            f = f.expand_as(u)
+        f = f.contiguous()
+    pshift = precond_shift_for(theta, sigma) if precond_shift is None else precond_shift
+    if maxit is None:
+        maxit = 20 * n * n
+    it_max, chunk = (int(pcg_iters), 0) if fixed else (int(maxit), int(check_every))
+    if not fixed and chunk < 1:
+        raise ValueError("diffuse: check_every must be >= 1 (pcg_iters selects the mode without host reads)")
+    frames = []
+    counts = torch.zeros(steps, B, dtype=torch.int32, device=u.device)
+
+    if _wants_grad(u, theta, *(() if f is None else (f,))):
+        for s in range(steps):
+            rhs = -sigma * u if f is None else (2.0 * f if cn else f) - sigma * u
+            if cn:
+                rhs = rhs - apply_div(u, theta, face_mean, device=device)
+            u, it, _ = solve_div(rhs, theta, face_mean=face_mean, rtol=rtol, maxit=it_max, check_every=chunk,
+                                 check=not fixed, return_info=True, device=device, u0=u.detach(), shift=sigma,
+                                 precond_shift=pshift)
+            counts[s] = it
+            if save_every and (s + 1) % int(save_every) == 0:
+                frames.append(u)
+    else:
+        u = u.detach().clone()           # the state, advanced in place: u0 is left as it was
+        theta = theta.detach()
+        if B and steps:
+            plan = dst_plan(n, u.device)
+            ws = torch.empty(int(query("srpde_div_cg_workspace_size", B, n)), dtype=torch.uint8, device=u.device)
+            rhs = torch.empty_like(u)
+            resid = torch.empty(B, dtype=torch.float64, device=u.device)
+            fp = 0 if f is None else f.data_ptr()
+        for s in range(steps if B else 0):
+            call("srpde_div_step_rhs", u.data_ptr(), fp, theta.data_ptr(), rhs.data_ptr(), B, n, mean, sigma, cn,
+                 stream_ptr(u.device))
+            # init_from copies the state into the workspace before finish overwrites it with the new one
+            _solve_div(rhs, theta, u, mean, float(rtol), it_max, chunk, not fixed, sigma, pshift, ws=ws,
+                       out=(u, counts[s], resid))
+            if save_every and (s + 1) % int(save_every) == 0:
+                frames.append(u.clone())
+    out = (u,)
+    if save_every:
+        out += (torch.stack(frames) if frames else u.new_empty((0,) + tuple(u.shape)),)
+    if check:
+        out += (counts,)
+    return out if len(out) > 1 else out[0]
 
 
 def residual_metrics(u, f, theta, interior_only: bool = False, inv_h2: float = None, device="cuda",
@@ -424,12 +612,15 @@ def relax(u, f, theta, sweeps: int, omega: float = 0.8, interior_only: bool = Fa
 
 def solve_batched(f, theta, rtol: float = DEFAULT_RTOL, maxit: int = None, device="cuda",
                   return_iters: bool = False, check: bool = True, _start_aborted: bool = False,
-                  method: str = "cg", form: str = "pointwise", face_mean: str = "harmonic", u0=None):
+                  method: str = "cg", form: str = "pointwise", face_mean: str = "harmonic", u0=None,
+                  shift: float = 0.0, precond_shift: float = None):
     """u[B, n, n] (float64, on device) with theta*Lap(u) = f per problem.
 
     ``form="divergence"`` solves div(theta grad u) = f instead (solve_div, which has one solver: ``method`` and
     ``_start_aborted`` are refused; ``return_iters`` gives its iteration counts; ``u0`` is its initial guess, which
-    the pointwise form and ``method="dst"`` refuse).
+    the pointwise form and ``method="dst"`` refuse; ``shift`` / ``precond_shift`` solve div(theta grad u) - shift u
+    = f, as solve_div does -- the pointwise forms refuse them too: theta * L - shift is not diagonalised by the sine
+    transform and their CG kernels have no shift).
 
     ``method="dst"`` solves directly (solve_direct): there is nothing to iterate, so ``return_iters`` gives
     zeros and non-default ``rtol`` / ``maxit`` / ``check`` / ``_start_aborted`` are refused.
@@ -443,8 +634,11 @@ def solve_batched(f, theta, rtol: float = DEFAULT_RTOL, maxit: int = None, devic
         if method != "cg" or _start_aborted:
             raise ValueError('form="divergence" has one solver (solve_div): method and _start_aborted do not apply')
         u, iters, _ = solve_div(f, theta, face_mean=face_mean, rtol=rtol, maxit=maxit, check=check, return_info=True,
-                                device=device, u0=u0)
+                                device=device, u0=u0, shift=shift, precond_shift=precond_shift)
         return (u, iters) if return_iters else u
+    if check_shift(shift) != 0.0 or precond_shift is not None:
+        raise ValueError('shift and precond_shift belong to form="divergence" (solve_div): the pointwise solvers '
+                         "have no shifted operator")
     if u0 is not None:
         raise ValueError('u0 belongs to form="divergence" (solve_div): the pointwise solvers start from zero')
     if check_solver(method) == "dst":

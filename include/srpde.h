@@ -77,8 +77,12 @@ typedef struct ihipStream_t* hipStream_t;
  *      srpde_div_cg_init_from
  *  21  the shifted operator D_theta - sigma I and implicit time steps: srpde_div_apply_shift,
  *      srpde_poisson_dst_shift_batched, srpde_div_cg_init_shift, srpde_div_cg_init_from_shift,
- *      srpde_div_cg_iterate_shift, srpde_div_step_rhs */
-#define SRPDE_ABI_VERSION 21
+ *      srpde_div_cg_iterate_shift, srpde_div_step_rhs
+ *  22  zero-flux (Neumann) sides for the divergence-form operator and its CG: srpde_div_apply_bc,
+ *      srpde_div_step_rhs_bc, srpde_div_theta_grad_bc, srpde_div_cg_workspace_size_bc, srpde_div_cg_init_bc,
+ *      srpde_div_cg_init_from_bc, srpde_div_cg_iterate_bc, srpde_poisson_sep_plan(_size),
+ *      srpde_poisson_sep_workspace_size, srpde_poisson_sep_shift_batched */
+#define SRPDE_ABI_VERSION 22
 
 /* Kernel-family bits (per call; bit 0 of the same argument is the accumulate flag): the forward / dgrad
  * families compute the same outputs, statistics and stored splits bit for bit, so these only route a call to
@@ -848,6 +852,68 @@ int srpde_div_cg_iterate_shift(const double* theta, int B, int n, int face_mean,
  * launch on srpde_div_apply's tiles; backward Euler reads no neighbour. */
 int srpde_div_step_rhs(const double* u, const double* f, const double* theta, double* rhs, int B, int n, int face_mean,
                        double sigma, int cn, hipStream_t stream);
+
+/* ---- Zero-flux (Neumann) sides (ABI 22).  Every entry above wraps the grid in a ghost ring that holds 0: four
+ *      homogeneous Dirichlet sides.  The entries here take a side mask bc, 0 .. 15:
+ *          bit 0  the row 0 side          bit 1  the row n - 1 side
+ *          bit 2  the column 0 side       bit 3  the column n - 1 side
+ *      A clear bit is the zero ghost ring as above; a set bit is a zero-flux side, du/dn = 0: that side's ghost faces
+ *      are missing, i.e. their coefficient is 0 where it was theta_a (the same as a ghost value equal to the edge
+ *      node's).  Every other operation, and its place in the rounding orders stated above, is unchanged: a missing
+ *      face's term is 0 * (0 - u_a) (and 0 * (0 - u_a) * (0 - lam_a) in the pair gradient, d_ab = 0), so bc = 0 gives
+ *      the bits of the unmasked namesake.  h stays 1 / (n - 1), inv_h2 = (n - 1)^2.  The operator stays exactly
+ *      symmetric; it is negative definite unless bc = 15, where the constants are its null space: bc = 15 needs
+ *      sigma > 0 (and sigma_p > 0) in every solve entry and is refused without.  A, and M = L_bc - sigma_p I (theta = 1,
+ *      the same sides), are sums over the same faces with coefficients in [theta_min, theta_max] and 1, so
+ *      cond(M^-1 A) <= theta_max / theta_min for every n, sigma and bc, as above. ---- */
+/* y = D_theta u - sigma * u with the sides bc: srpde_div_apply_shift's arguments, rounding order and launch (sigma = 0:
+ * srpde_div_apply's). */
+int srpde_div_apply_bc(const double* u, const double* theta, double* y, int B, int n, int face_mean, double inv_h2,
+                       double sigma, int bc, hipStream_t stream);
+/* srpde_div_step_rhs with the sides bc in Crank-Nicolson's D_theta u (backward Euler reads no neighbour: its rhs does
+ * not depend on bc). */
+int srpde_div_step_rhs_bc(const double* u, const double* f, const double* theta, double* rhs, int B, int n,
+                          int face_mean, double sigma, int cn, int bc, hipStream_t stream);
+/* srpde_div_theta_grad with the sides bc: d_ab = 0 towards a zero-flux side (1 towards a ghost-ring side). */
+int srpde_div_theta_grad_bc(const double* u, const double* lam, const double* theta, double* g_out, int B, int n,
+                            int face_mean, double inv_h2, double scale, int bc, hipStream_t stream);
+/* The separable solve of the constant-coefficient operator with the sides bc, the preconditioner of the CG below:
+ * L_bc = (T_y (x) I + I (x) T_x) / h^2 with T tridiagonal, 1 off the diagonal, -2 on it and -1 at a zero-flux end (T_y
+ * acts along the rows' index, its ends are bits 0 / 1; T_x along the columns', bits 2 / 3).  T = Q diag(lam) Q^T with,
+ * for nodes j and modes k = 0 .. n - 1, unit columns
+ *     ring - ring   Q[j][k] = sqrt(2 / (n + 1)) sin(pi (j + 1)(k + 1) / (n + 1)),      lam_k = -4 sin^2(pi (k + 1) / (2 (n + 1)))
+ *     ring - flux   Q[j][k] = 2 / sqrt(2 n + 1) sin(pi (j + 1)(2 k + 1) / (2 n + 1)),  lam_k = -4 sin^2(pi (2 k + 1) / (2 (2 n + 1)))
+ *     flux - ring   the same with j -> n - 1 - j
+ *     flux - flux   Q[j][k] = sqrt((k ? 2 : 1) / n) cos(pi (2 j + 1) k / (2 n)),       lam_k = -4 sin^2(pi k / (2 n))
+ * (the trigonometric arguments reduced in integers first), so
+ *     U = Q_y ( (Q_y^T F Q_x) o 1 / ((lam_y,i + lam_x,j) * inv_h2 - sigma_p) ) Q_x^T
+ * the scaling in the rounding order of srpde_poisson_dst_shift_batched.  Four launches of the batched fp64-MFMA tile
+ * product at every n (there is no one-workgroup kernel for mixed sides).
+ * The plan is a caller-owned device buffer of doubles: Q_x, Q_x^T, Q_y, Q_y^T ([n][n] each), lam_y [n], lam_x [n], the
+ * mask as a double, then bc unused doubles -- so that a plan's size, srpde_poisson_sep_plan_size(n, bc) bytes (0 for a
+ * bad n or mask), names both its n and its mask, and every entry refuses a plan made for another of either without
+ * reading it back.  Workspace: srpde_poisson_sep_workspace_size(B, n) bytes, one [B][n][n] field, 16-byte aligned. */
+size_t srpde_poisson_sep_plan_size(int n, int bc);
+int srpde_poisson_sep_plan(int n, int bc, void* plan, size_t plan_bytes, hipStream_t stream);
+size_t srpde_poisson_sep_workspace_size(int B, int n);
+/* u = solution of (L_bc - sigma_p I) u = f for B problems: f, u [B][n][n] fp64, 8-byte aligned, u must not alias f;
+ * n >= 2, sigma_p >= 0 and finite, > 0 for bc = 15.  Stream-ordered, no host sync, no state. */
+int srpde_poisson_sep_shift_batched(const double* f, double* u, int B, int n, int bc, double sigma_p, const void* plan,
+                                    size_t plan_bytes, void* ws, size_t ws_bytes, hipStream_t stream);
+/* (D_theta - sigma I) u = f with the sides bc by the CG of srpde_div_cg_*_shift, preconditioned with the separable
+ * solve above (plan: srpde_poisson_sep_plan for n and the same bc).  Arguments, rounding orders, the freeze rule and
+ * the per-problem fixed-order sums are the shifted entries'; sigma = sigma_p = 0 is the unshifted problem.  The
+ * workspace is srpde_div_cg_workspace_size_bc(B, n) bytes: the layout of srpde_div_cg_workspace_size with the separable
+ * solve's field behind it, so srpde_div_cg_done_offset and srpde_div_cg_finish serve these entries too. */
+size_t srpde_div_cg_workspace_size_bc(int B, int n);
+int srpde_div_cg_init_bc(const double* f, int B, int n, int bc, double sigma_p, const void* plan, size_t plan_bytes,
+                         void* ws, size_t ws_bytes, hipStream_t stream);
+int srpde_div_cg_init_from_bc(const double* f, const double* u0, const double* theta, int B, int n, int face_mean,
+                              int bc, double sigma, double sigma_p, double rtol, const void* plan, size_t plan_bytes,
+                              void* ws, size_t ws_bytes, hipStream_t stream);
+int srpde_div_cg_iterate_bc(const double* theta, int B, int n, int face_mean, int bc, double sigma, double sigma_p,
+                            double rtol, int k_begin, int k_count, const void* plan, size_t plan_bytes, void* ws,
+                            size_t ws_bytes, hipStream_t stream);
 
 /* ---- Row-sharded CG for ONE n x n problem over `world` ranks (the 640^2 ground
  *      truth of solve_multi_resolution, src/resolution_comparison.py:62-73).  Rank `rank` owns the

@@ -49,6 +49,15 @@
 // argument of the sine-transform solve (poisson_dst.h); everything else of the iteration -- update, r.z, the freeze
 // rule, the fixed-order sums, finish -- is the code above, untouched.  sigma = 0 launches the unshifted kernels.
 //
+// Boundary pattern (the *_bc entries).  bc is a 4-bit mask, bit 0 the row 0 side, bit 1 the row n - 1 side, bit 2 the
+// column 0 side, bit 3 the column n - 1 side; a set bit is a zero-flux side: its ghost faces are missing (coefficient
+// 0), a clear bit is the zero ghost ring above.  The operator stays a sum over faces with c in [theta_min, theta_max],
+// and so does M = L_bc - sigma_p I, the constant-coefficient operator with the same sides, which poisson_dst.hip's
+// separable solve inverts exactly: cond(M^-1 A) <= theta_max / theta_min for every n, sigma and pattern.  All four sides
+// zero-flux with sigma = 0 is singular (the constants) and refused.  The kernels are the tile bodies below with BC set
+// (face_sum_bc / face_grad_sum_bc in place of face_sum / face_grad_sum) and step (c) is the separable solve; update,
+// r.z, the k = 0 pass, the freeze rule and finish are the code above, untouched.
+//
 // Adjoint (srpde_div_theta_grad).  D_theta is symmetric, so the adjoint of the solve is the same solve, and the
 // gradient in theta of <lam, D_theta u> is the local pair gradient G(u, lam; theta) of div_theta_grad_kernel.
 #include <cmath>
@@ -79,13 +88,16 @@ struct DivCG {
   double *ff, *resid;                      // [B]
   int *iters, *done;                       // [B]
   void* dst_ws;
+  void* sep_ws;                            // the separable solve's field (carve with bc only)
   int n, nb;
   size_t bytes;
 };
 
 inline size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
 
-DivCG carve(void* ws, int B, int n) {
+// bc: the layout of the *_bc entries -- the same offsets, so srpde_div_cg_finish and the done flags serve both, plus
+// the separable solve's [B][n][n] field at the end where the sine solve's workspace is empty (n up to its LDS limit)
+DivCG carve(void* ws, int B, int n, bool bc = false) {
   DivCG g;
   char* c = static_cast<char*>(ws);
   size_t at = 0;
@@ -113,6 +125,8 @@ DivCG carve(void* ws, int B, int n) {
   g.resid = reinterpret_cast<double*>(take((size_t)B * sizeof(double)));
   g.iters = reinterpret_cast<int*>(take((size_t)B * sizeof(int)));
   g.done = reinterpret_cast<int*>(take((size_t)B * sizeof(int)));
+  g.sep_ws = g.dst_ws;
+  if (bc && srpde_poisson_dst_workspace_size(B, n) == 0) g.sep_ws = take(field);
   g.bytes = at;
   return g;
 }
@@ -122,13 +136,32 @@ DivCG carve(void* ws, int B, int n) {
 
 __device__ __forceinline__ int block_id() { return (int)(blockIdx.y * gridDim.x + blockIdx.x); }
 
+// the face sum / pair-gradient sum of node (gx, gy), whose halo tiles start at LDS offset c; BC: with the side mask bc
+template <bool HARM, bool BC>
+__device__ __forceinline__ double node_face_sum(const double* us, const double* ts, int c, int gx, int gy, int n,
+                                                int bc) {
+  if (BC)
+    return face_sum_bc<HARM>(us + c, ts + c, kDivLX, gx > 0, gx + 1 < n, gy > 0, gy + 1 < n, !(bc & 4), !(bc & 8),
+                             !(bc & 1), !(bc & 2));
+  return face_sum<HARM>(us + c, ts + c, kDivLX, gx > 0, gx + 1 < n, gy > 0, gy + 1 < n);
+}
+
+template <bool HARM, bool BC>
+__device__ __forceinline__ double node_face_grad_sum(const double* us, const double* ls, const double* ts, int c,
+                                                     int gx, int gy, int n, int bc) {
+  if (BC)
+    return face_grad_sum_bc<HARM>(us + c, ls + c, ts + c, kDivLX, gx > 0, gx + 1 < n, gy > 0, gy + 1 < n, !(bc & 4),
+                                  !(bc & 8), !(bc & 1), !(bc & 2));
+  return face_grad_sum<HARM>(us + c, ls + c, ts + c, kDivLX, gx > 0, gx + 1 < n, gy > 0, gy + 1 < n);
+}
+
 // y = D_theta u for one tile.  PCG: u = p = z + beta p_old is formed here (header, launch (a)).
 // SHIFT: y = D_theta u - sigma * u (the product, then the subtraction, after the face sum's * inv_h2).
-template <bool PCG, bool HARM, bool SHIFT>
-__global__ __launch_bounds__(kDivThreads) void div_apply_kernel(const double* __restrict__ u,
-                                                                const double* __restrict__ theta,
-                                                                double* __restrict__ y, DivCG g, double inv_h2,
-                                                                double sigma, int n, int k) {
+// BC: with the side mask bc (the body of div_apply_kernel and div_apply_bc_kernel).
+template <bool PCG, bool HARM, bool SHIFT, bool BC>
+__device__ __forceinline__ void div_apply_tile(const double* __restrict__ u, const double* __restrict__ theta,
+                                               double* __restrict__ y, const DivCG& g, double inv_h2, double sigma,
+                                               int n, int k, int bc) {
   __shared__ double us[kDivLY * kDivLX];
   __shared__ double ts[kDivLY * kDivLX];
   __shared__ double red[4];
@@ -173,7 +206,7 @@ __global__ __launch_bounds__(kDivThreads) void div_apply_kernel(const double* __
       if (gy < n) {
         const int c = ly * kDivLX + lx;
         const double uc = us[c];
-        double yv = face_sum<HARM>(us + c, ts + c, kDivLX, gx > 0, gx + 1 < n, gy > 0, gy + 1 < n) * inv_h2;
+        double yv = node_face_sum<HARM, BC>(us, ts, c, gx, gy, n, bc) * inv_h2;
         if (SHIFT) yv = yv - sigma * uc;
         const long long at = base + (long long)gy * n + gx;
         y[at] = yv;
@@ -188,6 +221,22 @@ __global__ __launch_bounds__(kDivThreads) void div_apply_kernel(const double* __
     const double s = block_sum(acc, red);
     if (tid == 0) g.ppq[(size_t)b * g.nb + block_id()] = s;
   }
+}
+
+template <bool PCG, bool HARM, bool SHIFT>
+__global__ __launch_bounds__(kDivThreads) void div_apply_kernel(const double* __restrict__ u,
+                                                                const double* __restrict__ theta,
+                                                                double* __restrict__ y, DivCG g, double inv_h2,
+                                                                double sigma, int n, int k) {
+  div_apply_tile<PCG, HARM, SHIFT, false>(u, theta, y, g, inv_h2, sigma, n, k, 0);
+}
+
+template <bool PCG, bool HARM, bool SHIFT>
+__global__ __launch_bounds__(kDivThreads) void div_apply_bc_kernel(const double* __restrict__ u,
+                                                                   const double* __restrict__ theta,
+                                                                   double* __restrict__ y, DivCG g, double inv_h2,
+                                                                   double sigma, int n, int k, int bc) {
+  div_apply_tile<PCG, HARM, SHIFT, true>(u, theta, y, g, inv_h2, sigma, n, k, bc);
 }
 
 // launch (b): x += alpha p, r -= alpha q, partial of r.r
@@ -282,11 +331,11 @@ __global__ __launch_bounds__(kDivThreads) void div_init_kernel(const double* __r
 // the halo tiles of u0 and theta; the block's partials of f.f (into the p.q partials, free until iteration 1) and of
 // r.r.  The walk and the sums are div_init_kernel's, so for u0 = 0 (D 0 = +0, f - 0 = f) both partials are its bits.
 // SHIFT: r = f - (D_theta u0 - sigma * u0), the operator as div_apply_kernel<.., SHIFT> forms it (+0 for u0 = 0 too).
-template <bool HARM, bool SHIFT>
-__global__ __launch_bounds__(kDivThreads) void div_init_from_kernel(const double* __restrict__ f,
-                                                                    const double* __restrict__ u0,
-                                                                    const double* __restrict__ theta, DivCG g,
-                                                                    double inv_h2, double sigma) {
+// BC: with the side mask bc (the body of div_init_from_kernel and div_init_from_bc_kernel).
+template <bool HARM, bool SHIFT, bool BC>
+__device__ __forceinline__ void div_init_from_tile(const double* __restrict__ f, const double* __restrict__ u0,
+                                                   const double* __restrict__ theta, const DivCG& g, double inv_h2,
+                                                   double sigma, int bc) {
   __shared__ double us[kDivLY * kDivLX];
   __shared__ double ts[kDivLY * kDivLX];
   __shared__ double red[4];
@@ -316,7 +365,7 @@ __global__ __launch_bounds__(kDivThreads) void div_init_from_kernel(const double
       const int ly = ly0 + r, gy = y0 + ly - 1;
       if (gy < n) {
         const int c = ly * kDivLX + lx;
-        double du = face_sum<HARM>(us + c, ts + c, kDivLX, gx > 0, gx + 1 < n, gy > 0, gy + 1 < n) * inv_h2;
+        double du = node_face_sum<HARM, BC>(us, ts, c, gx, gy, n, bc) * inv_h2;
         if (SHIFT) du = du - sigma * us[c];
         const long long at = base + (long long)gy * n + gx;
         const double fv = f[at];
@@ -334,6 +383,22 @@ __global__ __launch_bounds__(kDivThreads) void div_init_from_kernel(const double
     g.ppq[(size_t)b * g.nb + block_id()] = sf;
     g.prr[(size_t)b * g.nb + block_id()] = sr;
   }
+}
+
+template <bool HARM, bool SHIFT>
+__global__ __launch_bounds__(kDivThreads) void div_init_from_kernel(const double* __restrict__ f,
+                                                                    const double* __restrict__ u0,
+                                                                    const double* __restrict__ theta, DivCG g,
+                                                                    double inv_h2, double sigma) {
+  div_init_from_tile<HARM, SHIFT, false>(f, u0, theta, g, inv_h2, sigma, 0);
+}
+
+template <bool HARM, bool SHIFT>
+__global__ __launch_bounds__(kDivThreads) void div_init_from_bc_kernel(const double* __restrict__ f,
+                                                                       const double* __restrict__ u0,
+                                                                       const double* __restrict__ theta, DivCG g,
+                                                                       double inv_h2, double sigma, int bc) {
+  div_init_from_tile<HARM, SHIFT, true>(f, u0, theta, g, inv_h2, sigma, bc);
 }
 
 // the k = 0 pass after div_init_from_kernel and the sine solve: the block's partial of r.z where iteration 1 reads
@@ -382,12 +447,11 @@ __global__ __launch_bounds__(kDivThreads) void div_rz_from_kernel(DivCG g, doubl
 //   CN true  (Crank-Nicolson, sigma = 2 / dt):  rhs = (2 f - sigma * u) - D_theta u
 // 2 f is exact, D_theta u is div_apply_kernel's (face sum * inv_h2), every other operation is rounded once in the
 // order written; f == nullptr is f = 0.  Backward Euler reads no neighbour and stages nothing in LDS.
-template <bool CN, bool HARM>
-__global__ __launch_bounds__(kDivThreads) void div_step_rhs_kernel(const double* __restrict__ u,
-                                                                   const double* __restrict__ f,
-                                                                   const double* __restrict__ theta,
-                                                                   double* __restrict__ rhs, double inv_h2,
-                                                                   double sigma, int n) {
+// BC: with the side mask bc (the body of div_step_rhs_kernel and div_step_rhs_bc_kernel).
+template <bool CN, bool HARM, bool BC>
+__device__ __forceinline__ void div_step_rhs_tile(const double* __restrict__ u, const double* __restrict__ f,
+                                                  const double* __restrict__ theta, double* __restrict__ rhs,
+                                                  double inv_h2, double sigma, int n, int bc) {
   __shared__ double us[CN ? kDivLY * kDivLX : 1];
   __shared__ double ts[CN ? kDivLY * kDivLX : 1];
   const int tid = threadIdx.x, b = blockIdx.z;
@@ -420,7 +484,7 @@ __global__ __launch_bounds__(kDivThreads) void div_step_rhs_kernel(const double*
       const double fv = f ? f[at] : 0.0;
       if (CN) {
         const int c = ly * kDivLX + lx;
-        const double du = face_sum<HARM>(us + c, ts + c, kDivLX, gx > 0, gx + 1 < n, gy > 0, gy + 1 < n) * inv_h2;
+        const double du = node_face_sum<HARM, BC>(us, ts, c, gx, gy, n, bc) * inv_h2;
         rhs[at] = (2.0 * fv - sigma * us[c]) - du;
       } else {
         rhs[at] = fv - sigma * u[at];
@@ -429,15 +493,33 @@ __global__ __launch_bounds__(kDivThreads) void div_step_rhs_kernel(const double*
   }
 }
 
+template <bool CN, bool HARM>
+__global__ __launch_bounds__(kDivThreads) void div_step_rhs_kernel(const double* __restrict__ u,
+                                                                   const double* __restrict__ f,
+                                                                   const double* __restrict__ theta,
+                                                                   double* __restrict__ rhs, double inv_h2,
+                                                                   double sigma, int n) {
+  div_step_rhs_tile<CN, HARM, false>(u, f, theta, rhs, inv_h2, sigma, n, 0);
+}
+
+// Crank-Nicolson only: backward Euler reads no neighbour, so a pattern changes nothing of it
+template <bool HARM>
+__global__ __launch_bounds__(kDivThreads) void div_step_rhs_bc_kernel(const double* __restrict__ u,
+                                                                      const double* __restrict__ f,
+                                                                      const double* __restrict__ theta,
+                                                                      double* __restrict__ rhs, double inv_h2,
+                                                                      double sigma, int n, int bc) {
+  div_step_rhs_tile<true, HARM, true>(u, f, theta, rhs, inv_h2, sigma, n, bc);
+}
+
 // g = scale * G(u, lam; theta), G_a = inv_h2 * sum over a's faces of dc/dtheta_a (u_b - u_a) (lam_b - lam_a): the
 // gradient in theta of <lam, D_theta u>.  A gather over the halo tiles of u, lam and theta (3 x 34 x 66 doubles of
 // LDS, under the 64 KiB static limit): each node reads its own four faces, nothing is accumulated across nodes.
-template <bool HARM>
-__global__ __launch_bounds__(kDivThreads) void div_theta_grad_kernel(const double* __restrict__ u,
-                                                                     const double* __restrict__ lam,
-                                                                     const double* __restrict__ theta,
-                                                                     double* __restrict__ gout, double inv_h2,
-                                                                     double scale, int n) {
+// BC: with the side mask bc (the body of div_theta_grad_kernel and div_theta_grad_bc_kernel).
+template <bool HARM, bool BC>
+__device__ __forceinline__ void div_theta_grad_tile(const double* __restrict__ u, const double* __restrict__ lam,
+                                                    const double* __restrict__ theta, double* __restrict__ gout,
+                                                    double inv_h2, double scale, int n, int bc) {
   __shared__ double us[kDivLY * kDivLX];
   __shared__ double ls[kDivLY * kDivLX];
   __shared__ double ts[kDivLY * kDivLX];
@@ -468,11 +550,28 @@ __global__ __launch_bounds__(kDivThreads) void div_theta_grad_kernel(const doubl
     const int ly = ly0 + r, gy = y0 + ly - 1;
     if (gy < n) {
       const int c = ly * kDivLX + lx;
-      const double gv =
-          face_grad_sum<HARM>(us + c, ls + c, ts + c, kDivLX, gx > 0, gx + 1 < n, gy > 0, gy + 1 < n) * inv_h2;
+      const double gv = node_face_grad_sum<HARM, BC>(us, ls, ts, c, gx, gy, n, bc) * inv_h2;
       gout[base + (long long)gy * n + gx] = gv * scale;
     }
   }
+}
+
+template <bool HARM>
+__global__ __launch_bounds__(kDivThreads) void div_theta_grad_kernel(const double* __restrict__ u,
+                                                                     const double* __restrict__ lam,
+                                                                     const double* __restrict__ theta,
+                                                                     double* __restrict__ gout, double inv_h2,
+                                                                     double scale, int n) {
+  div_theta_grad_tile<HARM, false>(u, lam, theta, gout, inv_h2, scale, n, 0);
+}
+
+template <bool HARM>
+__global__ __launch_bounds__(kDivThreads) void div_theta_grad_bc_kernel(const double* __restrict__ u,
+                                                                        const double* __restrict__ lam,
+                                                                        const double* __restrict__ theta,
+                                                                        double* __restrict__ gout, double inv_h2,
+                                                                        double scale, int n, int bc) {
+  div_theta_grad_tile<HARM, true>(u, lam, theta, gout, inv_h2, scale, n, bc);
 }
 
 __global__ __launch_bounds__(256) void div_finish_kernel(DivCG g, double* __restrict__ u, int* __restrict__ iters,
@@ -501,25 +600,58 @@ static int div_check(const char* name, int B, int n, int face_mean) {
   return 0;
 }
 
-static int div_check_ws(const char* name, int B, int n, const void* ws, size_t ws_bytes) {
+static int div_check_ws(const char* name, int B, int n, const void* ws, size_t ws_bytes, bool bc = false) {
   if (!ws) SRPDE_FAIL(kErrArg, "%s: null workspace", name);
   if (!aligned16(ws)) SRPDE_FAIL(kErrAlign, "%s: workspace not 16-byte aligned", name);
-  if (ws_bytes < srpde_div_cg_workspace_size(B, n))
-    SRPDE_FAIL(kErrWorkspace, "%s: workspace too small (%zu bytes, needs %zu)", name, ws_bytes,
-               srpde_div_cg_workspace_size(B, n));
+  const size_t need = bc ? srpde_div_cg_workspace_size_bc(B, n) : srpde_div_cg_workspace_size(B, n);
+  if (ws_bytes < need) SRPDE_FAIL(kErrWorkspace, "%s: workspace too small (%zu bytes, needs %zu)", name, ws_bytes, need);
   return 0;
 }
 
-static int div_check_plan(const char* name, int n, const void* plan, size_t plan_bytes) {
+// bc < 0: the sine-transform plan for n; else the separable plan for n and that side mask
+static int div_check_plan(const char* name, int n, const void* plan, size_t plan_bytes, int bc = -1) {
   if (!plan) SRPDE_FAIL(kErrArg, "%s: null plan", name);
   if (reinterpret_cast<uintptr_t>(plan) & 7u) SRPDE_FAIL(kErrAlign, "%s: plan not 8-byte aligned", name);
+  if (bc >= 0) {
+    if (plan_bytes != sep_plan_bytes_for(n, bc))
+      SRPDE_FAIL(kErrWorkspace, "%s: a plan of %zu bytes is not a plan for n=%d and bc=%d (srpde_poisson_sep_plan_size: %zu)",
+                 name, plan_bytes, n, bc, sep_plan_bytes_for(n, bc));
+    return 0;
+  }
   if (plan_bytes != dst_plan_bytes_for(n))
     SRPDE_FAIL(kErrWorkspace, "%s: a plan of %zu bytes is not a plan for n=%d (srpde_poisson_dst_plan_size: %zu)", name,
                plan_bytes, n, dst_plan_bytes_for(n));
   return 0;
 }
 
+// the side mask of a *_bc entry; all four sides zero-flux is singular without a shift
+static int div_check_bc(const char* name, int bc) {
+  if (bc < 0 || bc > 15)
+    SRPDE_FAIL(kErrArg, "%s: bc=%d is not a side mask (bits 0..3: row 0, row n-1, column 0, column n-1; set = zero flux)",
+               name, bc);
+  return 0;
+}
+
+static int div_check_singular(const char* name, int bc, const char* what, double sigma) {
+  if (bc == 15 && sigma == 0.0)
+    SRPDE_FAIL(kErrArg, "%s: four zero-flux sides (bc=15) with %s=0 is singular (the constants): it needs a shift > 0",
+               name, what);
+  return 0;
+}
+
+// step (c): z = M^-1 r -- the sine-transform solve (bc < 0), or the separable solve with that side mask
+static int div_precondition(const char* name, const DivCG& g, int B, int n, int bc, const void* plan,
+                            hipStream_t stream, double sigma_p) {
+  if (bc < 0) return dst_solve_launch(name, g.r, nullptr, g.z, B, n, plan, g.dst_ws, stream, sigma_p);
+  return sep_solve_launch(name, g.r, g.z, B, n, plan, g.sep_ws, stream, sigma_p);
+}
+
 extern "C" {
+
+size_t srpde_div_cg_workspace_size_bc(int B, int n) {
+  if (B <= 0 || B > kDivMaxB || n < 2 || n > kDivMaxN) return 0;
+  return carve(nullptr, B, n, true).bytes;
+}
 
 size_t srpde_div_cg_workspace_size(int B, int n) {
   if (B <= 0 || B > kDivMaxB || n < 2 || n > kDivMaxN) return 0;
@@ -537,11 +669,13 @@ static int div_check_sigma(const char* name, const char* what, double sigma) {
   return 0;
 }
 
-// srpde_div_apply and srpde_div_apply_shift: sigma = 0 is the unshifted kernel
+// srpde_div_apply, srpde_div_apply_shift and srpde_div_apply_bc (bc >= 0): sigma = 0 is the unshifted kernel
 static int div_apply_launch(const char* name, const double* u, const double* theta, double* y, int B, int n,
-                            int face_mean, double inv_h2, double sigma, hipStream_t stream) {
+                            int face_mean, double inv_h2, double sigma, hipStream_t stream, int bc = -1) {
   SRPDE_CHECK_ARG(u && theta && y, "%s: null pointer", name);
   if (int rc = div_check(name, B, n, face_mean)) return rc;
+  if (bc != -1)
+    if (int rc = div_check_bc(name, bc)) return rc;
   if (!(inv_h2 > 0.0) || !std::isfinite(inv_h2))
     SRPDE_FAIL(kErrArg, "%s: inv_h2=%g must be positive and finite", name, inv_h2);
   if (int rc = div_check_sigma(name, "sigma", sigma)) return rc;
@@ -550,7 +684,25 @@ static int div_apply_launch(const char* name, const double* u, const double* the
   if (y == u || y == theta) SRPDE_FAIL(kErrArg, "%s: y aliases an input (a node reads its neighbours)", name);
   DivCG none = {};
   const dim3 grid = div_grid(B, n), block(kDivThreads);
-  if (sigma != 0.0) {
+  if (bc >= 0) {
+    switch ((sigma != 0.0 ? 2 : 0) + (face_mean ? 1 : 0)) {
+      case 0:
+        hipLaunchKernelGGL((div_apply_bc_kernel<false, false, false>), grid, block, 0, stream, u, theta, y, none, inv_h2,
+                           0.0, n, 0, bc);
+        break;
+      case 1:
+        hipLaunchKernelGGL((div_apply_bc_kernel<false, true, false>), grid, block, 0, stream, u, theta, y, none, inv_h2,
+                           0.0, n, 0, bc);
+        break;
+      case 2:
+        hipLaunchKernelGGL((div_apply_bc_kernel<false, false, true>), grid, block, 0, stream, u, theta, y, none, inv_h2,
+                           sigma, n, 0, bc);
+        break;
+      default:
+        hipLaunchKernelGGL((div_apply_bc_kernel<false, true, true>), grid, block, 0, stream, u, theta, y, none, inv_h2,
+                           sigma, n, 0, bc);
+    }
+  } else if (sigma != 0.0) {
     if (face_mean)
       hipLaunchKernelGGL((div_apply_kernel<false, true, true>), grid, block, 0, stream, u, theta, y, none, inv_h2,
                          sigma, n, 0);
@@ -578,21 +730,33 @@ int srpde_div_apply_shift(const double* u, const double* theta, double* y, int B
   return div_apply_launch("srpde_div_apply_shift", u, theta, y, B, n, face_mean, inv_h2, sigma, stream);
 }
 
-int srpde_div_step_rhs(const double* u, const double* f, const double* theta, double* rhs, int B, int n, int face_mean,
-                       double sigma, int cn, hipStream_t stream) {
-  const char* name = "srpde_div_step_rhs";
-  SRPDE_CHECK_ARG(u && theta && rhs, "srpde_div_step_rhs: null pointer");
+int srpde_div_apply_bc(const double* u, const double* theta, double* y, int B, int n, int face_mean, double inv_h2,
+                       double sigma, int bc, hipStream_t stream) {
+  return div_apply_launch("srpde_div_apply_bc", u, theta, y, B, n, face_mean, inv_h2, sigma, stream, bc < 0 ? 16 : bc);
+}
+
+// srpde_div_step_rhs and srpde_div_step_rhs_bc (bc >= 0)
+static int div_step_rhs(const char* name, const double* u, const double* f, const double* theta, double* rhs, int B,
+                        int n, int face_mean, double sigma, int cn, int bc, hipStream_t stream) {
+  SRPDE_CHECK_ARG(u && theta && rhs, "%s: null pointer", name);
   if (int rc = div_check(name, B, n, face_mean)) return rc;
-  if (cn != 0 && cn != 1) SRPDE_FAIL(kErrArg, "srpde_div_step_rhs: cn=%d (0 backward Euler, 1 Crank-Nicolson)", cn);
+  if (bc != -1)
+    if (int rc = div_check_bc(name, bc)) return rc;
+  if (cn != 0 && cn != 1) SRPDE_FAIL(kErrArg, "%s: cn=%d (0 backward Euler, 1 Crank-Nicolson)", name, cn);
   if (int rc = div_check_sigma(name, "sigma", sigma)) return rc;
   if ((reinterpret_cast<uintptr_t>(u) | reinterpret_cast<uintptr_t>(f) | reinterpret_cast<uintptr_t>(theta) |
        reinterpret_cast<uintptr_t>(rhs)) & 7u)
-    SRPDE_FAIL(kErrAlign, "srpde_div_step_rhs: a pointer is not 8-byte aligned");
+    SRPDE_FAIL(kErrAlign, "%s: a pointer is not 8-byte aligned", name);
   if (rhs == u || rhs == theta || rhs == f)
-    SRPDE_FAIL(kErrArg, "srpde_div_step_rhs: rhs aliases an input (a node reads its neighbours)");
+    SRPDE_FAIL(kErrArg, "%s: rhs aliases an input (a node reads its neighbours)", name);
   const double inv_h2 = (double)(n - 1) * (double)(n - 1);
   const dim3 grid = div_grid(B, n), block(kDivThreads);
-  if (!cn)
+  if (cn && bc >= 0) {
+    if (face_mean)
+      hipLaunchKernelGGL(div_step_rhs_bc_kernel<true>, grid, block, 0, stream, u, f, theta, rhs, inv_h2, sigma, n, bc);
+    else
+      hipLaunchKernelGGL(div_step_rhs_bc_kernel<false>, grid, block, 0, stream, u, f, theta, rhs, inv_h2, sigma, n, bc);
+  } else if (!cn)
     hipLaunchKernelGGL((div_step_rhs_kernel<false, false>), grid, block, 0, stream, u, f, theta, rhs, inv_h2, sigma, n);
   else if (face_mean)
     hipLaunchKernelGGL((div_step_rhs_kernel<true, true>), grid, block, 0, stream, u, f, theta, rhs, inv_h2, sigma, n);
@@ -602,19 +766,32 @@ int srpde_div_step_rhs(const double* u, const double* f, const double* theta, do
   return 0;
 }
 
+int srpde_div_step_rhs(const double* u, const double* f, const double* theta, double* rhs, int B, int n, int face_mean,
+                       double sigma, int cn, hipStream_t stream) {
+  return div_step_rhs("srpde_div_step_rhs", u, f, theta, rhs, B, n, face_mean, sigma, cn, -1, stream);
+}
+
+int srpde_div_step_rhs_bc(const double* u, const double* f, const double* theta, double* rhs, int B, int n,
+                          int face_mean, double sigma, int cn, int bc, hipStream_t stream) {
+  return div_step_rhs("srpde_div_step_rhs_bc", u, f, theta, rhs, B, n, face_mean, sigma, cn, bc < 0 ? 16 : bc, stream);
+}
+
 // srpde_div_cg_init and srpde_div_cg_init_shift (the zero start has r = f whatever sigma is: only M changes)
 static int div_cg_init(const char* name, const double* f, int B, int n, double sigma_p, const void* plan,
-                       size_t plan_bytes, void* ws, size_t ws_bytes, hipStream_t stream) {
+                       size_t plan_bytes, void* ws, size_t ws_bytes, hipStream_t stream, int bc = -1) {
   SRPDE_CHECK_ARG(f, "%s: null pointer", name);
   if (int rc = div_check(name, B, n, 0)) return rc;
+  if (bc != -1)
+    if (int rc = div_check_bc(name, bc)) return rc;
   if (int rc = div_check_sigma(name, "sigma_p", sigma_p)) return rc;
+  if (int rc = div_check_singular(name, bc, "sigma_p", sigma_p)) return rc;
   if (reinterpret_cast<uintptr_t>(f) & 7u) SRPDE_FAIL(kErrAlign, "%s: f not 8-byte aligned", name);
-  if (int rc = div_check_plan(name, n, plan, plan_bytes)) return rc;
-  if (int rc = div_check_ws(name, B, n, ws, ws_bytes)) return rc;
-  DivCG g = carve(ws, B, n);
+  if (int rc = div_check_plan(name, n, plan, plan_bytes, bc)) return rc;
+  if (int rc = div_check_ws(name, B, n, ws, ws_bytes, bc >= 0)) return rc;
+  DivCG g = carve(ws, B, n, bc >= 0);
   hipLaunchKernelGGL(div_init_kernel, div_grid(B, n), dim3(kDivThreads), 0, stream, f, g);
   SRPDE_LAUNCH_CHECK(name);
-  if (int rc = dst_solve_launch(name, g.r, nullptr, g.z, B, n, plan, g.dst_ws, stream, sigma_p)) return rc;
+  if (int rc = div_precondition(name, g, B, n, bc, plan, stream, sigma_p)) return rc;
   // rtol 0: only |f| = 0 is done before the first iteration
   hipLaunchKernelGGL(div_rz_kernel, div_grid(B, n), dim3(kDivThreads), 0, stream, g, 0, 0.0);
   SRPDE_LAUNCH_CHECK(name);
@@ -633,20 +810,42 @@ int srpde_div_cg_init_shift(const double* f, int B, int n, double sigma_p, const
 
 static int div_cg_init_from(const char* name, const double* f, const double* u0, const double* theta, int B, int n,
                             int face_mean, double sigma, double sigma_p, double rtol, const void* plan,
-                            size_t plan_bytes, void* ws, size_t ws_bytes, hipStream_t stream) {
+                            size_t plan_bytes, void* ws, size_t ws_bytes, hipStream_t stream, int bc = -1) {
   SRPDE_CHECK_ARG(f && u0 && theta, "%s: null pointer", name);
   if (int rc = div_check(name, B, n, face_mean)) return rc;
+  if (bc != -1)
+    if (int rc = div_check_bc(name, bc)) return rc;
   if (int rc = div_check_sigma(name, "sigma", sigma)) return rc;
   if (int rc = div_check_sigma(name, "sigma_p", sigma_p)) return rc;
+  if (int rc = div_check_singular(name, bc, "sigma", sigma)) return rc;
+  if (int rc = div_check_singular(name, bc, "sigma_p", sigma_p)) return rc;
   if ((reinterpret_cast<uintptr_t>(f) | reinterpret_cast<uintptr_t>(u0) | reinterpret_cast<uintptr_t>(theta)) & 7u)
     SRPDE_FAIL(kErrAlign, "%s: a pointer is not 8-byte aligned", name);
   if (!(rtol >= 0.0)) SRPDE_FAIL(kErrArg, "%s: rtol=%g must be >= 0", name, rtol);
-  if (int rc = div_check_plan(name, n, plan, plan_bytes)) return rc;
-  if (int rc = div_check_ws(name, B, n, ws, ws_bytes)) return rc;
-  DivCG g = carve(ws, B, n);
+  if (int rc = div_check_plan(name, n, plan, plan_bytes, bc)) return rc;
+  if (int rc = div_check_ws(name, B, n, ws, ws_bytes, bc >= 0)) return rc;
+  DivCG g = carve(ws, B, n, bc >= 0);
   const double inv_h2 = (double)(n - 1) * (double)(n - 1);
   const dim3 grid = div_grid(B, n), block(kDivThreads);
-  if (sigma != 0.0) {
+  if (bc >= 0) {
+    switch ((sigma != 0.0 ? 2 : 0) + (face_mean ? 1 : 0)) {
+      case 0:
+        hipLaunchKernelGGL((div_init_from_bc_kernel<false, false>), grid, block, 0, stream, f, u0, theta, g, inv_h2, 0.0,
+                           bc);
+        break;
+      case 1:
+        hipLaunchKernelGGL((div_init_from_bc_kernel<true, false>), grid, block, 0, stream, f, u0, theta, g, inv_h2, 0.0,
+                           bc);
+        break;
+      case 2:
+        hipLaunchKernelGGL((div_init_from_bc_kernel<false, true>), grid, block, 0, stream, f, u0, theta, g, inv_h2,
+                           sigma, bc);
+        break;
+      default:
+        hipLaunchKernelGGL((div_init_from_bc_kernel<true, true>), grid, block, 0, stream, f, u0, theta, g, inv_h2, sigma,
+                           bc);
+    }
+  } else if (sigma != 0.0) {
     if (face_mean)
       hipLaunchKernelGGL((div_init_from_kernel<true, true>), grid, block, 0, stream, f, u0, theta, g, inv_h2, sigma);
     else
@@ -657,7 +856,7 @@ static int div_cg_init_from(const char* name, const double* f, const double* u0,
     hipLaunchKernelGGL((div_init_from_kernel<false, false>), grid, block, 0, stream, f, u0, theta, g, inv_h2, 0.0);
   }
   SRPDE_LAUNCH_CHECK(name);
-  if (int rc = dst_solve_launch(name, g.r, nullptr, g.z, B, n, plan, g.dst_ws, stream, sigma_p)) return rc;
+  if (int rc = div_precondition(name, g, B, n, bc, plan, stream, sigma_p)) return rc;
   hipLaunchKernelGGL(div_rz_from_kernel, grid, block, 0, stream, g, rtol);
   SRPDE_LAUNCH_CHECK(name);
   return 0;
@@ -677,20 +876,28 @@ int srpde_div_cg_init_from_shift(const double* f, const double* u0, const double
                           plan_bytes, ws, ws_bytes, stream);
 }
 
-int srpde_div_theta_grad(const double* u, const double* lam, const double* theta, double* g_out, int B, int n,
-                         int face_mean, double inv_h2, double scale, hipStream_t stream) {
-  const char* name = "srpde_div_theta_grad";
-  SRPDE_CHECK_ARG(u && lam && theta && g_out, "srpde_div_theta_grad: null pointer");
+// srpde_div_theta_grad and srpde_div_theta_grad_bc (bc >= 0)
+static int div_theta_grad(const char* name, const double* u, const double* lam, const double* theta, double* g_out,
+                          int B, int n, int face_mean, double inv_h2, double scale, int bc, hipStream_t stream) {
+  SRPDE_CHECK_ARG(u && lam && theta && g_out, "%s: null pointer", name);
   if (int rc = div_check(name, B, n, face_mean)) return rc;
+  if (bc != -1)
+    if (int rc = div_check_bc(name, bc)) return rc;
   if (!(inv_h2 > 0.0) || !std::isfinite(inv_h2))
-    SRPDE_FAIL(kErrArg, "srpde_div_theta_grad: inv_h2=%g must be positive and finite", inv_h2);
-  if (!std::isfinite(scale)) SRPDE_FAIL(kErrArg, "srpde_div_theta_grad: scale=%g must be finite", scale);
+    SRPDE_FAIL(kErrArg, "%s: inv_h2=%g must be positive and finite", name, inv_h2);
+  if (!std::isfinite(scale)) SRPDE_FAIL(kErrArg, "%s: scale=%g must be finite", name, scale);
   if ((reinterpret_cast<uintptr_t>(u) | reinterpret_cast<uintptr_t>(lam) | reinterpret_cast<uintptr_t>(theta) |
        reinterpret_cast<uintptr_t>(g_out)) & 7u)
-    SRPDE_FAIL(kErrAlign, "srpde_div_theta_grad: a pointer is not 8-byte aligned");
+    SRPDE_FAIL(kErrAlign, "%s: a pointer is not 8-byte aligned", name);
   if (g_out == u || g_out == lam || g_out == theta)
-    SRPDE_FAIL(kErrArg, "srpde_div_theta_grad: g_out aliases an input (a node reads its neighbours)");
-  if (face_mean)
+    SRPDE_FAIL(kErrArg, "%s: g_out aliases an input (a node reads its neighbours)", name);
+  if (bc >= 0 && face_mean)
+    hipLaunchKernelGGL(div_theta_grad_bc_kernel<true>, div_grid(B, n), dim3(kDivThreads), 0, stream, u, lam, theta,
+                       g_out, inv_h2, scale, n, bc);
+  else if (bc >= 0)
+    hipLaunchKernelGGL(div_theta_grad_bc_kernel<false>, div_grid(B, n), dim3(kDivThreads), 0, stream, u, lam, theta,
+                       g_out, inv_h2, scale, n, bc);
+  else if (face_mean)
     hipLaunchKernelGGL(div_theta_grad_kernel<true>, div_grid(B, n), dim3(kDivThreads), 0, stream, u, lam, theta, g_out,
                        inv_h2, scale, n);
   else
@@ -700,25 +907,56 @@ int srpde_div_theta_grad(const double* u, const double* lam, const double* theta
   return 0;
 }
 
+int srpde_div_theta_grad(const double* u, const double* lam, const double* theta, double* g_out, int B, int n,
+                         int face_mean, double inv_h2, double scale, hipStream_t stream) {
+  return div_theta_grad("srpde_div_theta_grad", u, lam, theta, g_out, B, n, face_mean, inv_h2, scale, -1, stream);
+}
+
+int srpde_div_theta_grad_bc(const double* u, const double* lam, const double* theta, double* g_out, int B, int n,
+                            int face_mean, double inv_h2, double scale, int bc, hipStream_t stream) {
+  return div_theta_grad("srpde_div_theta_grad_bc", u, lam, theta, g_out, B, n, face_mean, inv_h2, scale,
+                        bc < 0 ? 16 : bc, stream);
+}
+
 static int div_cg_iterate(const char* name, const double* theta, int B, int n, int face_mean, double sigma,
                           double sigma_p, double rtol, int k_begin, int k_count, const void* plan, size_t plan_bytes,
-                          void* ws, size_t ws_bytes, hipStream_t stream) {
+                          void* ws, size_t ws_bytes, hipStream_t stream, int bc = -1) {
   SRPDE_CHECK_ARG(theta, "%s: null pointer", name);
   if (int rc = div_check(name, B, n, face_mean)) return rc;
+  if (bc != -1)
+    if (int rc = div_check_bc(name, bc)) return rc;
   if (int rc = div_check_sigma(name, "sigma", sigma)) return rc;
   if (int rc = div_check_sigma(name, "sigma_p", sigma_p)) return rc;
+  if (int rc = div_check_singular(name, bc, "sigma", sigma)) return rc;
+  if (int rc = div_check_singular(name, bc, "sigma_p", sigma_p)) return rc;
   if (reinterpret_cast<uintptr_t>(theta) & 7u) SRPDE_FAIL(kErrAlign, "%s: theta not 8-byte aligned", name);
   if (!(rtol >= 0.0)) SRPDE_FAIL(kErrArg, "%s: rtol=%g must be >= 0", name, rtol);
   if (k_begin < 1 || k_count < 0 || k_count > INT32_MAX - k_begin)
     SRPDE_FAIL(kErrArg, "%s: k_begin=%d k_count=%d (iterations count from 1)", name, k_begin, k_count);
-  if (int rc = div_check_plan(name, n, plan, plan_bytes)) return rc;
-  if (int rc = div_check_ws(name, B, n, ws, ws_bytes)) return rc;
-  DivCG g = carve(ws, B, n);
+  if (int rc = div_check_plan(name, n, plan, plan_bytes, bc)) return rc;
+  if (int rc = div_check_ws(name, B, n, ws, ws_bytes, bc >= 0)) return rc;
+  DivCG g = carve(ws, B, n, bc >= 0);
   const double inv_h2 = (double)(n - 1) * (double)(n - 1);
   const dim3 grid = div_grid(B, n), block(kDivThreads);
-  const int variant = (sigma != 0.0 ? 2 : 0) + (face_mean ? 1 : 0);
+  const int variant = (bc >= 0 ? 4 : 0) + (sigma != 0.0 ? 2 : 0) + (face_mean ? 1 : 0);
   for (int k = k_begin; k < k_begin + k_count; ++k) {
     switch (variant) {
+      case 4:
+        hipLaunchKernelGGL((div_apply_bc_kernel<true, false, false>), grid, block, 0, stream, g.z, theta, g.q, g,
+                           inv_h2, 0.0, n, k, bc);
+        break;
+      case 5:
+        hipLaunchKernelGGL((div_apply_bc_kernel<true, true, false>), grid, block, 0, stream, g.z, theta, g.q, g, inv_h2,
+                           0.0, n, k, bc);
+        break;
+      case 6:
+        hipLaunchKernelGGL((div_apply_bc_kernel<true, false, true>), grid, block, 0, stream, g.z, theta, g.q, g, inv_h2,
+                           sigma, n, k, bc);
+        break;
+      case 7:
+        hipLaunchKernelGGL((div_apply_bc_kernel<true, true, true>), grid, block, 0, stream, g.z, theta, g.q, g, inv_h2,
+                           sigma, n, k, bc);
+        break;
       case 0:
         hipLaunchKernelGGL((div_apply_kernel<true, false, false>), grid, block, 0, stream, g.z, theta, g.q, g, inv_h2,
                            0.0, n, k);
@@ -737,7 +975,7 @@ static int div_cg_iterate(const char* name, const double* theta, int B, int n, i
     }
     hipLaunchKernelGGL(div_update_kernel, grid, block, 0, stream, g, k);
     SRPDE_LAUNCH_CHECK(name);
-    if (int rc = dst_solve_launch(name, g.r, nullptr, g.z, B, n, plan, g.dst_ws, stream, sigma_p)) return rc;
+    if (int rc = div_precondition(name, g, B, n, bc, plan, stream, sigma_p)) return rc;
     hipLaunchKernelGGL(div_rz_kernel, grid, block, 0, stream, g, k, rtol);
     SRPDE_LAUNCH_CHECK(name);
   }
@@ -755,6 +993,26 @@ int srpde_div_cg_iterate_shift(const double* theta, int B, int n, int face_mean,
                                size_t ws_bytes, hipStream_t stream) {
   return div_cg_iterate("srpde_div_cg_iterate_shift", theta, B, n, face_mean, sigma, sigma_p, rtol, k_begin, k_count,
                         plan, plan_bytes, ws, ws_bytes, stream);
+}
+
+int srpde_div_cg_init_bc(const double* f, int B, int n, int bc, double sigma_p, const void* plan, size_t plan_bytes,
+                         void* ws, size_t ws_bytes, hipStream_t stream) {
+  return div_cg_init("srpde_div_cg_init_bc", f, B, n, sigma_p, plan, plan_bytes, ws, ws_bytes, stream,
+                     bc < 0 ? 16 : bc);
+}
+
+int srpde_div_cg_init_from_bc(const double* f, const double* u0, const double* theta, int B, int n, int face_mean,
+                              int bc, double sigma, double sigma_p, double rtol, const void* plan, size_t plan_bytes,
+                              void* ws, size_t ws_bytes, hipStream_t stream) {
+  return div_cg_init_from("srpde_div_cg_init_from_bc", f, u0, theta, B, n, face_mean, sigma, sigma_p, rtol, plan,
+                          plan_bytes, ws, ws_bytes, stream, bc < 0 ? 16 : bc);
+}
+
+int srpde_div_cg_iterate_bc(const double* theta, int B, int n, int face_mean, int bc, double sigma, double sigma_p,
+                            double rtol, int k_begin, int k_count, const void* plan, size_t plan_bytes, void* ws,
+                            size_t ws_bytes, hipStream_t stream) {
+  return div_cg_iterate("srpde_div_cg_iterate_bc", theta, B, n, face_mean, sigma, sigma_p, rtol, k_begin, k_count,
+                        plan, plan_bytes, ws, ws_bytes, stream, bc < 0 ? 16 : bc);
 }
 
 int srpde_div_cg_finish(double* u, int* iters, double* resid, int B, int n, void* ws, size_t ws_bytes,

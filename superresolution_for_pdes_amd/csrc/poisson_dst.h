@@ -20,4 +20,12 @@ int dst_solve_launch(const char* name, const double* f, const double* theta, dou
 
 size_t dst_plan_bytes_for(int n);
 
+// The separable solve with mixed sides: u = (L_bc - sigma I)^-1 f for B problems [B][n][n] fp64, sigma >= 0 (> 0 when
+// all four sides are zero-flux), the sides in the plan (srpde_poisson_sep_plan for n and the mask); ws: one [B][n][n]
+// field at every n.  Four launches; u must not alias f.  The caller has checked every argument.
+int sep_solve_launch(const char* name, const double* f, double* u, int B, int n, const void* plan, void* ws,
+                     hipStream_t stream, double sigma);
+
+size_t sep_plan_bytes_for(int n, int bc);
+
 }  // namespace srpde

@@ -29,6 +29,16 @@
 // (L - sigma I) u = f once the scaling h^2 / (lam_i + lam_j) becomes dst_shift_scale's 1 / ((lam_i + lam_j) inv_h2 -
 // sigma).  It is a template argument of the two kernels that scale; sigma = 0 launches the unshifted instantiations.
 //
+// Separable solve with mixed sides (srpde_poisson_sep_*, the preconditioner of the *_bc CG of poisson_div.hip).  A side
+// of the grid is the zero ghost ring (Dirichlet) or zero flux (Neumann: the ghost face is missing), given as the 4-bit
+// mask bc of poisson_div.hip.  The constant-coefficient operator is still L_bc = (T_y (x) I + I (x) T_x) / h^2, each T
+// tridiagonal with 1 off the diagonal and -2 on it, -1 at a Neumann end; its orthogonal eigenvector matrices Q_y, Q_x
+// (sine, quarter-wave sine or cosine: sep_axis_kernel) are no longer symmetric and differ per axis, so the plan holds
+// each with its transpose and
+//     U = Q_y ( (Q_y^T F Q_x) o 1 / ((lam_y,i + lam_x,j) inv_h2 - sigma_p) ) Q_x^T
+// is the four launches of dst_gemm_kernel of the general path at every n (SCALE 3: dst_shift_scale with the row's
+// eigenvalue from lam_y and the column's from lam_x).  The one-workgroup LDS kernel is not extended.
+//
 // The k order of every sum is ascending and fixed by n alone, there are no atomics, and a problem's blocks
 // never see another problem: results are bit-reproducible and independent of B.
 #include <cmath>
@@ -74,6 +84,52 @@ __device__ __forceinline__ double dst_shift_scale(double li, double lj, double i
   return 1.0 / (d - sigma);
 }
 
+// One axis of the separable plan.  Nodes j = 0 .. n - 1, modes k = 0 .. n - 1, column k of Q the unit eigenvector:
+//   Dirichlet both ends (nlo = nhi = 0)   sqrt(2 / (n + 1)) sin(pi (j + 1)(k + 1) / (n + 1)),    s = (k + 1) / (2 (n + 1))
+//   Dirichlet at 0, Neumann at n - 1      (2 / sqrt(2 n + 1)) sin(pi (j + 1)(2 k + 1) / (2 n + 1)), s = (2 k + 1) / (2 (2 n + 1))
+//   Neumann at 0, Dirichlet at n - 1      the same with j -> n - 1 - j
+//   Neumann both ends                     sqrt((k ? 2 : 1) / n) cos(pi (2 j + 1) k / (2 n)),      s = k / (2 n)
+// and lam_k = -4 sin^2(pi s).  The arguments are reduced in integers before sinpi, as dst_plan_kernel does;
+// cos(pi m / (2 n)) is taken as sin(pi (m + n) / (2 n)), still in integers, so every entry is one sinpi of a quotient
+// of two integers.
+__global__ __launch_bounds__(256) void sep_axis_kernel(int n, int nlo, int nhi, double* __restrict__ Q,
+                                                       double* __restrict__ QT, double* __restrict__ lam,
+                                                       double* __restrict__ mask_word, int bc) {
+  const long long total = (long long)n * n;
+  const bool dd = !nlo && !nhi, nn = nlo && nhi;
+  const int den = dd ? n + 1 : (nn ? 2 * n : 2 * n + 1);          // the entries' sinpi(m / den), m mod 2 den
+  const int lden = dd ? n + 1 : (nn ? n : 2 * n + 1);             // the eigenvalues' sinpi(num / (2 lden))
+  const double scale = dd ? sqrt(2.0 / (double)(n + 1)) : (nn ? sqrt(2.0 / (double)n) : 2.0 / sqrt((double)(2 * n + 1)));
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const int j = (int)(i / n), k = (int)(i - (long long)j * n);
+    const int jj = (!nn && nlo) ? n - 1 - j : j;
+    long long m;
+    if (dd)
+      m = (long long)(jj + 1) * (k + 1);
+    else if (nn)
+      m = (long long)(2 * jj + 1) * k + n;
+    else
+      m = (long long)(jj + 1) * (2 * k + 1);
+    m %= 2LL * den;
+    double q = scale * sinpi((double)m / (double)den);
+    if (nn && k == 0) q = sqrt(1.0 / (double)n);                  // the constant mode
+    Q[i] = q;
+    QT[(long long)k * n + j] = q;
+    if (i < n) {
+      const int num = dd ? (int)i + 1 : (nn ? (int)i : 2 * (int)i + 1);
+      const double sv = sinpi((double)num / (2.0 * (double)lden));
+      lam[i] = -4.0 * sv * sv;
+    }
+    if (i == 0 && mask_word) *mask_word = (double)bc;
+  }
+}
+
+// the mask word, then mask more words: a plan is tied to its n AND its mask by its size (the entries see only the
+// device pointer and the size, and read nothing back)
+static size_t sep_plan_bytes(int n, int bc) {
+  return ((size_t)4 * n * n + (size_t)2 * n + 1 + (size_t)bc) * sizeof(double);
+}
+
 // ---- general path ------------------------------------------------------------------------------------------
 constexpr int kGT = 64;            // block tile (rows and columns); four waves, 32 x 32 each
 constexpr int kGK = 16;            // k per LDS stage
@@ -83,7 +139,8 @@ constexpr int kGLdB = kGT + 16;    // Bs[k][c]: the two k rows of a half wave la
 // C[b] = A[b] B[b], all [n][n] row-major, batch strides sA / sB / sC in elements (0: shared by every problem).
 // DIV: A's elements are divided by th's (same indexing as A) as they are loaded.
 // SCALE 1: C[i][j] is multiplied by h2 / (lam[i] + lam[j]) as it is stored; SCALE 2: by dst_shift_scale(lam[i],
-// lam[j], inv_h2, sigma) instead.
+// lam[j], inv_h2, sigma) instead; SCALE 3: by dst_shift_scale(lam[i], lam[n + j], inv_h2, sigma), the row's eigenvalue
+// from the first and the column's from the second of two vectors [n] (the separable solve's lam_y, lam_x).
 template <bool DIV, int SCALE>
 __global__ __launch_bounds__(256) void dst_gemm_kernel(const double* __restrict__ A, long long sA,
                                                        const double* __restrict__ Bm, long long sB,
@@ -161,6 +218,7 @@ __global__ __launch_bounds__(256) void dst_gemm_kernel(const double* __restrict_
             double v = acc[i][j][r];
             if (SCALE == 1) v = v * (h2 / (lam[row] + lam[col]));
             if (SCALE == 2) v = v * dst_shift_scale(lam[row], lam[col], inv_h2, sigma);
+            if (SCALE == 3) v = v * dst_shift_scale(lam[row], lam[n + col], inv_h2, sigma);
             Cb[(long long)row * n + col] = v;
           }
         }
@@ -265,7 +323,7 @@ __global__ __launch_bounds__(768) void dst_fused_kernel(const double* __restrict
   }
 }
 
-// scale: 0 none, 1 h2 / (lam + lam), 2 dst_shift_scale with inv_h2 and sigma
+// scale: 0 none, 1 h2 / (lam + lam), 2 dst_shift_scale with inv_h2 and sigma, 3 the same from two vectors
 static int gemm_launch(bool div, int scale, const double* A, long long sA, const double* Bm, long long sB, double* C,
                        long long sC, const double* th, const double* lam, double h2, int n, int B, hipStream_t stream,
                        double inv_h2 = 0.0, double sigma = 0.0) {
@@ -279,6 +337,9 @@ static int gemm_launch(bool div, int scale, const double* A, long long sA, const
                        sigma, n, B);
   else if (scale == 2)
     hipLaunchKernelGGL((dst_gemm_kernel<false, 2>), grid, block, 0, stream, A, sA, Bm, sB, C, sC, th, lam, h2, inv_h2,
+                       sigma, n, B);
+  else if (scale == 3)
+    hipLaunchKernelGGL((dst_gemm_kernel<false, 3>), grid, block, 0, stream, A, sA, Bm, sB, C, sC, th, lam, h2, inv_h2,
                        sigma, n, B);
   else
     hipLaunchKernelGGL((dst_gemm_kernel<false, 0>), grid, block, 0, stream, A, sA, Bm, sB, C, sC, th, lam, h2, inv_h2,
@@ -324,6 +385,27 @@ int dst_solve_launch(const char* name, const double* f, const double* theta, dou
 }
 
 size_t dst_plan_bytes_for(int n) { return dst_plan_bytes(n); }
+
+// u = (L_bc - sigma I)^-1 f for B problems, the sides in the plan.  Arguments already checked; u must not alias f.
+int sep_solve_launch(const char* name, const double* f, double* u, int B, int n, const void* plan, void* ws,
+                     hipStream_t stream, double sigma) {
+  const long long nn = (long long)n * n;
+  const double* Qx = static_cast<const double*>(plan);
+  const double *QxT = Qx + nn, *Qy = QxT + nn, *QyT = Qy + nn, *lam = QyT + nn;   // lam_y [n] then lam_x [n]
+  const double inv_h2 = (double)(n - 1) * (double)(n - 1);
+  double* w = static_cast<double*>(ws);
+  gemm_launch(false, 0, f, nn, Qx, 0, w, nn, nullptr, lam, 0.0, n, B, stream);                    // w = f Qx
+  SRPDE_LAUNCH_CHECK(name);
+  gemm_launch(false, 3, QyT, 0, w, nn, u, nn, nullptr, lam, 0.0, n, B, stream, inv_h2, sigma);    // u = (Qy^T w) o scale
+  SRPDE_LAUNCH_CHECK(name);
+  gemm_launch(false, 0, u, nn, QxT, 0, w, nn, nullptr, lam, 0.0, n, B, stream);                   // w = u Qx^T
+  SRPDE_LAUNCH_CHECK(name);
+  gemm_launch(false, 0, Qy, 0, w, nn, u, nn, nullptr, lam, 0.0, n, B, stream);                    // u = Qy w
+  SRPDE_LAUNCH_CHECK(name);
+  return 0;
+}
+
+size_t sep_plan_bytes_for(int n, int bc) { return sep_plan_bytes(n, bc); }
 
 }  // namespace srpde
 
@@ -391,6 +473,60 @@ int srpde_poisson_dst_shift_batched(const double* f, double* u, int B, int n, do
     SRPDE_FAIL(kErrAlign, "srpde_poisson_dst_shift_batched: a pointer is not 8-byte aligned");
   if (int rc = dst_check(name, B, n, 2, plan, plan_bytes, ws, ws_bytes)) return rc;
   return dst_solve_launch(name, f, nullptr, u, B, n, plan, ws, stream, sigma_p);
+}
+
+size_t srpde_poisson_sep_plan_size(int n, int bc) {
+  return (n < 2 || n > kDstMaxN || bc < 0 || bc > 15) ? 0 : sep_plan_bytes(n, bc);
+}
+
+size_t srpde_poisson_sep_workspace_size(int B, int n) {
+  if (B <= 0 || n < 2 || n > kDstMaxN) return 0;
+  return (size_t)B * n * n * sizeof(double);
+}
+
+int srpde_poisson_sep_plan(int n, int bc, void* plan, size_t plan_bytes, hipStream_t stream) {
+  SRPDE_CHECK_ARG(plan, "srpde_poisson_sep_plan: null pointer");
+  if (n < 2 || n > kDstMaxN) SRPDE_FAIL(kErrShape, "srpde_poisson_sep_plan: bad shape n=%d (2 .. %d)", n, kDstMaxN);
+  if (bc < 0 || bc > 15) SRPDE_FAIL(kErrArg, "srpde_poisson_sep_plan: bc=%d is not a side mask (0 .. 15)", bc);
+  if (reinterpret_cast<uintptr_t>(plan) & 7u) SRPDE_FAIL(kErrAlign, "srpde_poisson_sep_plan: plan not 8-byte aligned");
+  if (plan_bytes < sep_plan_bytes(n, bc))
+    SRPDE_FAIL(kErrWorkspace, "srpde_poisson_sep_plan: plan buffer too small (%zu bytes, n=%d bc=%d needs %zu)",
+               plan_bytes, n, bc, sep_plan_bytes(n, bc));
+  // plan: Qx, Qx^T, Qy, Qy^T [n][n] each, lam_y [n], lam_x [n], then the mask as a double
+  const size_t nn = (size_t)n * n;
+  double* p = static_cast<double*>(plan);
+  double *lam_y = p + 4 * nn, *lam_x = lam_y + n;
+  const dim3 grid(elementwise_grid((long long)nn)), block(256);
+  hipLaunchKernelGGL(sep_axis_kernel, grid, block, 0, stream, n, (bc >> 2) & 1, (bc >> 3) & 1, p, p + nn, lam_x,
+                     lam_x + n, bc);
+  hipLaunchKernelGGL(sep_axis_kernel, grid, block, 0, stream, n, bc & 1, (bc >> 1) & 1, p + 2 * nn, p + 3 * nn, lam_y,
+                     static_cast<double*>(nullptr), bc);
+  SRPDE_LAUNCH_CHECK("srpde_poisson_sep_plan");
+  return 0;
+}
+
+int srpde_poisson_sep_shift_batched(const double* f, double* u, int B, int n, int bc, double sigma_p, const void* plan,
+                                    size_t plan_bytes, void* ws, size_t ws_bytes, hipStream_t stream) {
+  const char* name = "srpde_poisson_sep_shift_batched";
+  SRPDE_CHECK_ARG(f && u && plan && ws, "srpde_poisson_sep_shift_batched: null pointer");
+  if (B <= 0 || n < 2 || n > kDstMaxN)
+    SRPDE_FAIL(kErrShape, "%s: bad shape B=%d n=%d (B >= 1, n 2 .. %d)", name, B, n, kDstMaxN);
+  if (bc < 0 || bc > 15) SRPDE_FAIL(kErrArg, "%s: bc=%d is not a side mask (0 .. 15)", name, bc);
+  if (!(sigma_p >= 0.0) || !std::isfinite(sigma_p))
+    SRPDE_FAIL(kErrArg, "%s: sigma_p=%g must be >= 0 and finite", name, sigma_p);
+  if (bc == 15 && sigma_p == 0.0)
+    SRPDE_FAIL(kErrArg, "%s: four zero-flux sides (bc=15) with sigma_p=0 is singular (the constants)", name);
+  if ((reinterpret_cast<uintptr_t>(f) | reinterpret_cast<uintptr_t>(u) | reinterpret_cast<uintptr_t>(plan)) & 7u)
+    SRPDE_FAIL(kErrAlign, "%s: a pointer is not 8-byte aligned", name);
+  if (u == f) SRPDE_FAIL(kErrArg, "%s: u aliases f (four launches: f is read after u is first written)", name);
+  if (plan_bytes != sep_plan_bytes(n, bc))
+    SRPDE_FAIL(kErrWorkspace, "%s: a plan of %zu bytes is not a plan for n=%d and bc=%d (srpde_poisson_sep_plan_size: %zu)",
+               name, plan_bytes, n, bc, sep_plan_bytes(n, bc));
+  if (!aligned16(ws)) SRPDE_FAIL(kErrAlign, "%s: workspace not 16-byte aligned", name);
+  if (ws_bytes < srpde_poisson_sep_workspace_size(B, n))
+    SRPDE_FAIL(kErrWorkspace, "%s: workspace too small (%zu bytes, needs %zu)", name, ws_bytes,
+               srpde_poisson_sep_workspace_size(B, n));
+  return sep_solve_launch(name, f, u, B, n, plan, ws, stream, sigma_p);
 }
 
 int srpde_poisson_dst_apply(const double* x, double* y, int B, int n, const void* plan, size_t plan_bytes, void* ws,

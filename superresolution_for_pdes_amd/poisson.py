@@ -25,7 +25,11 @@ differentiable in their fields and in theta (the operator is symmetric, so the s
 ``div_theta_grad`` is the one local pass the theta gradient needs), and ``solve_div(..., u0=)`` starts the iteration
 from a guess.  ``shift=`` on both makes the operator div(theta grad u) - sigma u, preconditioned with the
 sine-transform solve of L - sigma_p I at the same condition bound, and ``diffuse`` steps u_t = div(theta grad u) - f
-implicitly with it (backward Euler or Crank-Nicolson), each solve warm-started from the previous state.
+implicitly with it (backward Euler or Crank-Nicolson), each solve warm-started from the previous state.  ``bc=`` on
+all of these makes chosen sides of the grid zero-flux (insulated, du/dn = 0) instead of the zero ghost ring: a 4-string
+of "d" / "n" for (row 0, row n - 1, column 0, column n - 1), preconditioned with the separable solve of the
+constant-coefficient operator with the same sides at the same condition bound; None (default) and "dddd" are today's
+calls.
 """
 from __future__ import annotations
 
@@ -160,6 +164,43 @@ def face_mean_arg(form: str, face_mean: str):
     return None
 
 
+def check_bc(bc):
+    """The side mask of the C entries' bc argument from a pattern such as "ddnn": one of "d" (the zero ghost ring) or
+    "n" (zero flux) for (row 0 side, row n - 1 side, column 0 side, column n - 1 side), bit i set for an "n" at place
+    i.  None and "dddd" give None: the entries without a mask, today's calls."""
+    if bc is None:
+        return None
+    if not isinstance(bc, str) or len(bc) != 4 or any(c not in "dn" for c in bc):
+        raise ValueError(f'bc must be None or four of "d" / "n" for (row 0, row n-1, column 0, column n-1), got {bc!r}')
+    mask = sum(1 << i for i, c in enumerate(bc) if c == "n")
+    return mask or None
+
+
+_sep_plans = {}   # (n, mask, device) -> the plan buffer of srpde_poisson_sep_plan
+
+
+def sep_plan(n: int, bc, device="cuda"):
+    """The eigenvector matrices and eigenvalues of the separable solve for n and the pattern ``bc`` (a 4-string or a
+    mask) on ``device``, built on first use (two launches) and kept, like ``dst_plan``."""
+    mask = int(bc) if isinstance(bc, int) else (check_bc(bc) or 0)
+    dev = torch.device(device)
+    if dev.index is None:
+        dev = torch.device(dev.type, torch.cuda.current_device())
+    key = (int(n), mask, dev)
+    plan = _sep_plans.get(key)
+    if plan is None:
+        nbytes = int(query("srpde_poisson_sep_plan_size", int(n), mask))
+        if nbytes == 0:
+            raise ValueError(f"no separable plan for n={n}, bc={bc!r}")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"the separable plan for n={n}, bc={bc!r} must exist before stream capture: call "
+                               "poisson.sep_plan(n, bc) first")
+        plan = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        call("srpde_poisson_sep_plan", int(n), mask, plan.data_ptr(), nbytes, stream_ptr(dev))
+        _sep_plans[key] = plan
+    return plan
+
+
 class NotConverged(RuntimeError):
     """solve_div left problems above their tolerance (maxit reached)."""
 
@@ -220,10 +261,14 @@ def precond_shift_for(theta, shift: float) -> float:
     return shift / float(np.sqrt(lo * hi))
 
 
-def _apply_div(u, theta, mean: int, inv_h2: float, shift: float = 0.0):
-    """srpde_div_apply (shift 0: today's call) or srpde_div_apply_shift on prepared fields (_div_fields)."""
+def _apply_div(u, theta, mean: int, inv_h2: float, shift: float = 0.0, bc=None):
+    """srpde_div_apply (shift 0: today's call) or srpde_div_apply_shift on prepared fields (_div_fields); with a side
+    mask ``bc`` srpde_div_apply_bc."""
     y = torch.empty_like(u)
-    if u.shape[0] and shift == 0.0:
+    if u.shape[0] and bc is not None:
+        call("srpde_div_apply_bc", u.data_ptr(), theta.data_ptr(), y.data_ptr(), u.shape[0], u.shape[-1], mean,
+             inv_h2, shift, bc, stream_ptr(u.device))
+    elif u.shape[0] and shift == 0.0:
         call("srpde_div_apply", u.data_ptr(), theta.data_ptr(), y.data_ptr(), u.shape[0], u.shape[-1], mean,
              inv_h2, stream_ptr(u.device))
     elif u.shape[0]:
@@ -232,29 +277,35 @@ def _apply_div(u, theta, mean: int, inv_h2: float, shift: float = 0.0):
     return y
 
 
-def _div_theta_grad(u, lam, theta, mean: int, inv_h2: float, scale: float):
-    """srpde_div_theta_grad on prepared fields."""
+def _div_theta_grad(u, lam, theta, mean: int, inv_h2: float, scale: float, bc=None):
+    """srpde_div_theta_grad on prepared fields; with a side mask ``bc`` srpde_div_theta_grad_bc."""
     g = torch.empty_like(u)
-    if u.shape[0]:
+    if u.shape[0] and bc is not None:
+        call("srpde_div_theta_grad_bc", u.data_ptr(), lam.data_ptr(), theta.data_ptr(), g.data_ptr(), u.shape[0],
+             u.shape[-1], mean, inv_h2, scale, bc, stream_ptr(u.device))
+    elif u.shape[0]:
         call("srpde_div_theta_grad", u.data_ptr(), lam.data_ptr(), theta.data_ptr(), g.data_ptr(), u.shape[0],
              u.shape[-1], mean, inv_h2, scale, stream_ptr(u.device))
     return g
 
 
 def div_theta_grad(u, lam, theta, face_mean: str = "harmonic", inv_h2: float = None, scale: float = 1.0,
-                   device="cuda"):
+                   device="cuda", bc=None):
     """scale * G(u, lam; theta), the pair gradient of the divergence-form operator: a new [B, n, n] fp64 device tensor
     with G_a = inv_h2 * (sum over the four faces of node a of dc_ab/dtheta_a (u_b - u_a) (lam_b - lam_a)), where
     dc/dtheta_a is 0.5 (``"arithmetic"``), 2 tb^2 / (ta + tb)^2 (``"harmonic"``) and 1 towards the ghost ring (u and
     lam are 0 there).  d<lam, D_theta u>/dtheta = -G: the theta gradient of apply_div is -G(u, grad_y), that of
     solve_div +G(u, lam) with lam the adjoint solve.  u, lam [n, n] or [B, n, n]; theta is broadcast; ``inv_h2``
     defaults to (n - 1)^2.  One launch, stream-ordered, no host sync, not itself differentiable
-    (srpde_div_theta_grad; include/srpde.h states the rounding order)."""
+    (srpde_div_theta_grad; include/srpde.h states the rounding order).  ``bc`` (``check_bc``): dc/dtheta_a is 0
+    towards a zero-flux side (srpde_div_theta_grad_bc)."""
     mean = check_face_mean(face_mean)
+    bc = check_bc(bc)
     with torch.no_grad():
         u, theta, B, n = _div_fields(u, theta, device)
         lam = _dev_f64(lam, device).reshape(u.shape)
-        return _div_theta_grad(u, lam, theta, mean, float((n - 1) ** 2 if inv_h2 is None else inv_h2), float(scale))
+        return _div_theta_grad(u, lam, theta, mean, float((n - 1) ** 2 if inv_h2 is None else inv_h2), float(scale),
+                               bc)
 
 
 class _ApplyDiv(torch.autograd.Function):
@@ -262,20 +313,20 @@ class _ApplyDiv(torch.autograd.Function):
     depend on theta, so grad_theta = -G(u, grad_y; theta) as without it."""
 
     @staticmethod
-    def forward(ctx, u, theta, mean, inv_h2, shift=0.0):
+    def forward(ctx, u, theta, mean, inv_h2, shift=0.0, bc=None):
         u, theta = u.detach().contiguous(), theta.detach().contiguous()
         ctx.save_for_backward(u, theta)
-        ctx.mean, ctx.inv_h2, ctx.shift = mean, inv_h2, shift
-        return _apply_div(u, theta, mean, inv_h2, shift)
+        ctx.mean, ctx.inv_h2, ctx.shift, ctx.bc = mean, inv_h2, shift, bc
+        return _apply_div(u, theta, mean, inv_h2, shift, bc)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gy):
         u, theta = ctx.saved_tensors
         gy = gy.contiguous()
-        gu = _apply_div(gy, theta, ctx.mean, ctx.inv_h2, ctx.shift) if ctx.needs_input_grad[0] else None
-        gth = _div_theta_grad(u, gy, theta, ctx.mean, ctx.inv_h2, -1.0) if ctx.needs_input_grad[1] else None
-        return gu, gth, None, None, None
+        gu = _apply_div(gy, theta, ctx.mean, ctx.inv_h2, ctx.shift, ctx.bc) if ctx.needs_input_grad[0] else None
+        gth = _div_theta_grad(u, gy, theta, ctx.mean, ctx.inv_h2, -1.0, ctx.bc) if ctx.needs_input_grad[1] else None
+        return gu, gth, None, None, None, None
 
 
 class _SolveDiv(torch.autograd.Function):
@@ -284,11 +335,11 @@ class _SolveDiv(torch.autograd.Function):
     grad_theta = +G(u, lam; theta), the shift not depending on theta.  Nothing depends on u0."""
 
     @staticmethod
-    def forward(ctx, f, theta, u0, mean, rtol, maxit, check_every, check, shift=0.0, pshift=0.0):
+    def forward(ctx, f, theta, u0, mean, rtol, maxit, check_every, check, shift=0.0, pshift=0.0, bc=None):
         f, theta = f.detach().contiguous(), theta.detach().contiguous()
-        u, iters, resid = _solve_div(f, theta, u0, mean, rtol, maxit, check_every, check, shift, pshift)
+        u, iters, resid = _solve_div(f, theta, u0, mean, rtol, maxit, check_every, check, shift, pshift, bc=bc)
         ctx.save_for_backward(u, theta)
-        ctx.args = (mean, rtol, maxit, check_every, check, shift, pshift)
+        ctx.args, ctx.bc = (mean, rtol, maxit, check_every, check, shift, pshift), bc
         ctx.mark_non_differentiable(iters, resid)
         return u, iters, resid
 
@@ -297,14 +348,15 @@ class _SolveDiv(torch.autograd.Function):
     def backward(ctx, gu, _giters, _gresid):
         u, theta = ctx.saved_tensors
         mean = ctx.args[0]
-        lam = _solve_div(gu.contiguous(), theta, None, *ctx.args)[0]     # NotConverged propagates
+        lam = _solve_div(gu.contiguous(), theta, None, *ctx.args, bc=ctx.bc)[0]     # NotConverged propagates
         gth = None
         if ctx.needs_input_grad[1]:
-            gth = _div_theta_grad(u, lam, theta, mean, float((u.shape[-1] - 1) ** 2), 1.0)
-        return (lam if ctx.needs_input_grad[0] else None), gth, None, None, None, None, None, None, None, None
+            gth = _div_theta_grad(u, lam, theta, mean, float((u.shape[-1] - 1) ** 2), 1.0, ctx.bc)
+        return (lam if ctx.needs_input_grad[0] else None), gth, None, None, None, None, None, None, None, None, None
 
 
-def apply_div(u, theta, face_mean: str = "harmonic", inv_h2: float = None, device="cuda", shift: float = 0.0):
+def apply_div(u, theta, face_mean: str = "harmonic", inv_h2: float = None, device="cuda", shift: float = 0.0,
+              bc=None):
     """y = div(theta grad u) on the project's grid (zero ghost ring, h = 1 / (n - 1)): a new [B, n, n] fp64 device
     tensor.  The face coefficient between nodes a and b is 0.5 (ta + tb) (``"arithmetic"``) or 2 ta tb / (ta + tb)
     (``"harmonic"``), theta_a towards the ghost ring; ``inv_h2`` defaults to (n - 1)^2.  One launch, stream-ordered,
@@ -315,19 +367,24 @@ def apply_div(u, theta, face_mean: str = "harmonic", inv_h2: float = None, devic
 
     ``shift`` (sigma >= 0, finite): y = div(theta grad u) - sigma u, the operator of an implicit time step, in the
     same launch (srpde_div_apply_shift: the product sigma * u, then one subtraction).  The gradient in u carries the
-    shift, the one in theta does not change, the shift itself gets none.  0.0 (default) is exactly today's call."""
+    shift, the one in theta does not change, the shift itself gets none.  0.0 (default) is exactly today's call.
+
+    ``bc`` (``check_bc``, e.g. ``"ddnn"``): an "n" side is zero-flux -- its ghost faces have coefficient 0 instead of
+    theta_a -- in the same launch (srpde_div_apply_bc); both gradients carry the pattern.  None (default) and
+    ``"dddd"`` are exactly today's calls."""
     mean = check_face_mean(face_mean)
     shift = check_shift(shift)
+    bc = check_bc(bc)
     u, theta, B, n = _div_fields(u, theta, device)
     inv_h2 = float((n - 1) ** 2 if inv_h2 is None else inv_h2)
     if _wants_grad(u, theta):
-        return _ApplyDiv.apply(u, theta, mean, inv_h2, shift)
-    return _apply_div(u, theta, mean, inv_h2, shift)
+        return _ApplyDiv.apply(u, theta, mean, inv_h2, shift, bc)
+    return _apply_div(u, theta, mean, inv_h2, shift, bc)
 
 
 def solve_div(f, theta, face_mean: str = "harmonic", rtol: float = DEFAULT_RTOL, maxit: int = None,
               check_every: int = 8, check: bool = True, return_info: bool = False, device="cuda", u0=None,
-              shift: float = 0.0, precond_shift: float = None):
+              shift: float = 0.0, precond_shift: float = None, bc=None):
     """u[B, n, n] (float64, on device) with div(theta grad u) = f per problem, by CG preconditioned with the
     sine-transform solve of the constant-coefficient operator (srpde_div_cg_*).  Convergence, |r| <= rtol |f|, is
     decided per problem on the device, and a converged problem is frozen, so a problem's u / iters / resid are the
@@ -356,9 +413,21 @@ def solve_div(f, theta, face_mean: str = "harmonic", rtol: float = DEFAULT_RTOL,
     in fixed-iteration mode (``check_every=0``) and under stream capture it must be given.  Any sigma_p = sigma /
     theta_g with theta_g in theta's range keeps cond <= theta_max / theta_min, so the iteration count is at most the
     unshifted one's bound (``pcg_iterations``) for every sigma.  The adjoint solve uses the same two shifts; the shift
-    gets no gradient.  ``shift=0.0`` (default; ``precond_shift`` must then be None or 0) makes exactly today's calls."""
+    gets no gradient.  ``shift=0.0`` (default; ``precond_shift`` must then be None or 0) makes exactly today's calls.
+
+    ``bc`` (``check_bc``, e.g. ``"ddnn"``): "n" sides are zero-flux (srpde_div_cg_*_bc), and the preconditioner is the
+    separable solve of the constant-coefficient operator with the same sides (``sep_plan(n, bc)``, four launches at
+    every n), so the bound theta_max / theta_min and ``pcg_iterations`` hold for every pattern.  ``"nnnn"`` is singular
+    without a shift and refused (ValueError); with one it is the insulated box.  u0, shift, precond_shift, both modes,
+    capture (once ``sep_plan(n, bc)`` exists) and the gradients work as without.  None (default) and ``"dddd"`` make
+    exactly today's calls."""
     mean = check_face_mean(face_mean)
     shift = check_shift(shift)
+    bc = check_bc(bc)
+    if bc == 15 and shift == 0.0:
+        raise ValueError('solve_div: bc="nnnn" with shift=0 is singular (the constants): it needs a shift > 0')
+    if bc == 15 and precond_shift is not None and float(precond_shift) == 0.0:
+        raise ValueError('solve_div: bc="nnnn" needs a precond_shift > 0 (the unshifted preconditioner is singular)')
     if precond_shift is not None:
         precond_shift = check_shift(precond_shift, "precond_shift")
         if shift == 0.0 and precond_shift != 0.0:
@@ -384,16 +453,17 @@ def solve_div(f, theta, face_mean: str = "harmonic", rtol: float = DEFAULT_RTOL,
     else:
         pshift = precond_shift_for(theta, shift) if precond_shift is None else precond_shift
     if _wants_grad(f, theta):
-        out = _SolveDiv.apply(f, theta, u0, mean, float(rtol), maxit, check_every, bool(check), shift, pshift)
+        out = _SolveDiv.apply(f, theta, u0, mean, float(rtol), maxit, check_every, bool(check), shift, pshift, bc)
     else:
-        out = _solve_div(f, theta, u0, mean, float(rtol), maxit, check_every, bool(check), shift, pshift)
+        out = _solve_div(f, theta, u0, mean, float(rtol), maxit, check_every, bool(check), shift, pshift, bc=bc)
     return out if return_info else out[0]
 
 
 def _solve_div(f, theta, u0, mean: int, rtol: float, maxit: int, check_every: int, check: bool, shift: float = 0.0,
-               pshift: float = 0.0, ws=None, out=None):
+               pshift: float = 0.0, ws=None, out=None, bc=None):
     """The srpde_div_cg_* call sequence on prepared fields -> (u, iters, resid); shift 0 is the unshifted entries'
-    sequence, call for call.  ``ws`` / ``out`` = (u, iters, resid): the caller's buffers (diffuse reuses them)."""
+    sequence, call for call; a side mask ``bc`` the *_bc entries' with the separable plan.  ``ws`` / ``out`` = (u,
+    iters, resid): the caller's buffers (diffuse reuses them)."""
     B, n = f.shape[0], f.shape[-1]
     if out is None:
         u = torch.empty_like(f)
@@ -406,12 +476,19 @@ def _solve_div(f, theta, u0, mean: int, rtol: float, maxit: int, check_every: in
     capturing = torch.cuda.is_current_stream_capturing()
     if check_every and capturing:
         raise RuntimeError("solve_div: reading the done flags synchronises the host; capture with check_every=0")
-    plan = dst_plan(n, f.device)
-    ws_bytes = int(query("srpde_div_cg_workspace_size", B, n))
+    plan = dst_plan(n, f.device) if bc is None else sep_plan(n, bc, f.device)
+    ws_bytes = int(query("srpde_div_cg_workspace_size" if bc is None else "srpde_div_cg_workspace_size_bc", B, n))
     if ws is None:
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=f.device)
     sp = stream_ptr(f.device)
-    if shift != 0.0:
+    if bc is not None:
+        if u0 is None:
+            call("srpde_div_cg_init_bc", f.data_ptr(), B, n, bc, pshift, plan.data_ptr(), plan.numel(), ws.data_ptr(),
+                 ws_bytes, sp)
+        else:
+            call("srpde_div_cg_init_from_bc", f.data_ptr(), u0.data_ptr(), theta.data_ptr(), B, n, mean, bc, shift,
+                 pshift, rtol, plan.data_ptr(), plan.numel(), ws.data_ptr(), ws_bytes, sp)
+    elif shift != 0.0:
         if u0 is None:
             call("srpde_div_cg_init_shift", f.data_ptr(), B, n, pshift, plan.data_ptr(), plan.numel(), ws.data_ptr(),
                  ws_bytes, sp)
@@ -430,7 +507,10 @@ def _solve_div(f, theta, u0, mean: int, rtol: float, maxit: int, check_every: in
         k = maxit
     while k < maxit:
         count = min(check_every, maxit - k) if check_every else maxit
-        if shift != 0.0:
+        if bc is not None:
+            call("srpde_div_cg_iterate_bc", theta.data_ptr(), B, n, mean, bc, shift, pshift, rtol, k + 1, count,
+                 plan.data_ptr(), plan.numel(), ws.data_ptr(), ws_bytes, sp)
+        elif shift != 0.0:
             call("srpde_div_cg_iterate_shift", theta.data_ptr(), B, n, mean, shift, pshift, rtol, k + 1, count,
                  plan.data_ptr(), plan.numel(), ws.data_ptr(), ws_bytes, sp)
         else:
@@ -454,7 +534,7 @@ SCHEMES = ("be", "cn")
 
 def diffuse(u0, theta, f=None, dt: float = None, steps: int = 1, scheme: str = "be", face_mean: str = "harmonic",
             rtol: float = DEFAULT_RTOL, maxit: int = None, pcg_iters: int = None, precond_shift: float = None,
-            save_every: int = None, check: bool = False, check_every: int = 8, device="cuda"):
+            save_every: int = None, check: bool = False, check_every: int = 8, device="cuda", bc=None):
     """``steps`` implicit time steps of u_t = div(theta grad u) - f from u0, the forcing constant in time (None: 0),
     on the project's grid (zero ghost ring).  Each step solves (D_theta - sigma I) u+ = rhs by the shifted
     sine-preconditioned CG, warm-started from the current state:
@@ -475,7 +555,13 @@ def diffuse(u0, theta, f=None, dt: float = None, steps: int = 1, scheme: str = "
     Differentiable in theta, u0 and f when grad mode is on and one of them requires grad: the steps are then composed
     from the autograd ``solve_div(shift=, u0=)`` and ``apply_div`` plus torch arithmetic for rhs (same solves, a few
     more launches and one adjoint solve per step in the backward; once differentiable).  dt and the shift get no
-    gradient.  Otherwise the direct ABI path above."""
+    gradient.  Otherwise the direct ABI path above.
+
+    ``bc`` (``check_bc``, e.g. ``"nnnn"``, the insulated box: with f = None the sum of u is conserved up to the solves'
+    tolerance): "n" sides are zero-flux in the operator, in Crank-Nicolson's right-hand side (srpde_div_step_rhs_bc)
+    and in every solve (``solve_div(bc=)``); capture needs ``sep_plan(n, bc)`` first.  None (default) and ``"dddd"``
+    make exactly today's calls."""
+    pattern, bc = bc, check_bc(bc)
     if scheme not in SCHEMES:
         raise ValueError(f"unknown time scheme {scheme!r}: one of {SCHEMES}")
     mean = check_face_mean(face_mean)
@@ -493,6 +579,8 @@ def diffuse(u0, theta, f=None, dt: float = None, steps: int = 1, scheme: str = "
         raise ValueError("diffuse: pcg_iters must be >= 1")
     if precond_shift is not None:
         precond_shift = check_shift(precond_shift, "precond_shift")
+        if bc == 15 and precond_shift == 0.0:
+            raise ValueError('diffuse: bc="nnnn" needs a precond_shift > 0 (the unshifted preconditioner is singular)')
     elif fixed or torch.cuda.is_current_stream_capturing():
         raise ValueError("diffuse: precond_shift=None reads theta's range back (a host sync): give precond_shift "
                          "in fixed mode (pcg_iters) and under stream capture")
@@ -517,10 +605,10 @@ def diffuse(u0, theta, f=None, dt: float = None, steps: int = 1, scheme: str = "
         for s in range(steps):
             rhs = -sigma * u if f is None else (2.0 * f if cn else f) - sigma * u
             if cn:
-                rhs = rhs - apply_div(u, theta, face_mean, device=device)
+                rhs = rhs - apply_div(u, theta, face_mean, device=device, bc=pattern)
             u, it, _ = solve_div(rhs, theta, face_mean=face_mean, rtol=rtol, maxit=it_max, check_every=chunk,
                                  check=not fixed, return_info=True, device=device, u0=u.detach(), shift=sigma,
-                                 precond_shift=pshift)
+                                 precond_shift=pshift, bc=pattern)
             counts[s] = it
             if save_every and (s + 1) % int(save_every) == 0:
                 frames.append(u)
@@ -528,17 +616,21 @@ def diffuse(u0, theta, f=None, dt: float = None, steps: int = 1, scheme: str = "
         u = u.detach().clone()           # the state, advanced in place: u0 is left as it was
         theta = theta.detach()
         if B and steps:
-            plan = dst_plan(n, u.device)
-            ws = torch.empty(int(query("srpde_div_cg_workspace_size", B, n)), dtype=torch.uint8, device=u.device)
+            ws_query = "srpde_div_cg_workspace_size" if bc is None else "srpde_div_cg_workspace_size_bc"
+            ws = torch.empty(int(query(ws_query, B, n)), dtype=torch.uint8, device=u.device)
             rhs = torch.empty_like(u)
             resid = torch.empty(B, dtype=torch.float64, device=u.device)
             fp = 0 if f is None else f.data_ptr()
         for s in range(steps if B else 0):
-            call("srpde_div_step_rhs", u.data_ptr(), fp, theta.data_ptr(), rhs.data_ptr(), B, n, mean, sigma, cn,
-                 stream_ptr(u.device))
+            if bc is None:
+                call("srpde_div_step_rhs", u.data_ptr(), fp, theta.data_ptr(), rhs.data_ptr(), B, n, mean, sigma, cn,
+                     stream_ptr(u.device))
+            else:
+                call("srpde_div_step_rhs_bc", u.data_ptr(), fp, theta.data_ptr(), rhs.data_ptr(), B, n, mean, sigma,
+                     cn, bc, stream_ptr(u.device))
             # init_from copies the state into the workspace before finish overwrites it with the new one
             _solve_div(rhs, theta, u, mean, float(rtol), it_max, chunk, not fixed, sigma, pshift, ws=ws,
-                       out=(u, counts[s], resid))
+                       out=(u, counts[s], resid), bc=bc)
             if save_every and (s + 1) % int(save_every) == 0:
                 frames.append(u.clone())
     out = (u,)
@@ -550,7 +642,7 @@ def diffuse(u0, theta, f=None, dt: float = None, steps: int = 1, scheme: str = "
 
 
 def residual_metrics(u, f, theta, interior_only: bool = False, inv_h2: float = None, device="cuda",
-                     form: str = "pointwise", face_mean: str = "harmonic"):
+                     form: str = "pointwise", face_mean: str = "harmonic", bc=None):
     """How well raw fields satisfy the discrete equation: [E, 2] fp64 device tensor of (RMS, max abs) of
     theta * A u / h^2 - f per example (A the 5-point stencil with a zero ghost ring).  u [E, n, n] fp32 or fp64
     (a tensor keeps its precision), f and theta fp64.  ``inv_h2`` defaults to (n - 1)^2, the whole-domain operator
@@ -558,15 +650,17 @@ def residual_metrics(u, f, theta, interior_only: bool = False, inv_h2: float = N
     larger solve, whose ring is not zero).  Stream-ordered, no host sync (srpde_pde_residual_metrics).
     ``form="divergence"``: (RMS, max abs) of div(theta grad u) - f with ``face_mean`` instead, through apply_div, in
     fp64 whatever u's precision -- and, through apply_div, differentiable in u, f and theta when one of them requires
-    grad (the pointwise metric is not)."""
+    grad (the pointwise metric is not); ``bc`` is apply_div's side pattern and belongs to that form."""
     if check_form(form) == "divergence":
         f, theta, E, n = _div_fields(f, theta, device)
         u = _dev_f64(u, device).reshape(f.shape)
-        res = apply_div(u, theta, face_mean, inv_h2, device) - f
+        res = apply_div(u, theta, face_mean, inv_h2, device, bc=bc) - f
         if interior_only:
             res = res[:, 1:-1, 1:-1]
         res = res.reshape(E, -1)
         return torch.stack([res.pow(2).mean(1).sqrt(), res.abs().amax(1)], dim=1)
+    if bc is not None:
+        raise ValueError('bc belongs to form="divergence" (apply_div): the pointwise operator has the zero ghost ring')
     from . import hipops as H
     if isinstance(u, torch.Tensor) and u.dtype == torch.float32:
         u = u.to(device).contiguous()
@@ -613,14 +707,14 @@ def relax(u, f, theta, sweeps: int, omega: float = 0.8, interior_only: bool = Fa
 def solve_batched(f, theta, rtol: float = DEFAULT_RTOL, maxit: int = None, device="cuda",
                   return_iters: bool = False, check: bool = True, _start_aborted: bool = False,
                   method: str = "cg", form: str = "pointwise", face_mean: str = "harmonic", u0=None,
-                  shift: float = 0.0, precond_shift: float = None):
+                  shift: float = 0.0, precond_shift: float = None, bc=None):
     """u[B, n, n] (float64, on device) with theta*Lap(u) = f per problem.
 
     ``form="divergence"`` solves div(theta grad u) = f instead (solve_div, which has one solver: ``method`` and
     ``_start_aborted`` are refused; ``return_iters`` gives its iteration counts; ``u0`` is its initial guess, which
     the pointwise form and ``method="dst"`` refuse; ``shift`` / ``precond_shift`` solve div(theta grad u) - shift u
     = f, as solve_div does -- the pointwise forms refuse them too: theta * L - shift is not diagonalised by the sine
-    transform and their CG kernels have no shift).
+    transform and their CG kernels have no shift; ``bc`` is solve_div's side pattern, refused likewise).
 
     ``method="dst"`` solves directly (solve_direct): there is nothing to iterate, so ``return_iters`` gives
     zeros and non-default ``rtol`` / ``maxit`` / ``check`` / ``_start_aborted`` are refused.
@@ -634,8 +728,10 @@ def solve_batched(f, theta, rtol: float = DEFAULT_RTOL, maxit: int = None, devic
         if method != "cg" or _start_aborted:
             raise ValueError('form="divergence" has one solver (solve_div): method and _start_aborted do not apply')
         u, iters, _ = solve_div(f, theta, face_mean=face_mean, rtol=rtol, maxit=maxit, check=check, return_info=True,
-                                device=device, u0=u0, shift=shift, precond_shift=precond_shift)
+                                device=device, u0=u0, shift=shift, precond_shift=precond_shift, bc=bc)
         return (u, iters) if return_iters else u
+    if bc is not None:
+        raise ValueError('bc belongs to form="divergence" (solve_div): the pointwise solvers have the zero ghost ring')
     if check_shift(shift) != 0.0 or precond_shift is not None:
         raise ValueError('shift and precond_shift belong to form="divergence" (solve_div): the pointwise solvers '
                          "have no shifted operator")

@@ -683,7 +683,13 @@ size_t srpde_poisson_workspace_size(int B, int n);
  * workspace (srpde_poisson_workspace_size bytes), run as cooperative launches (Chronopoulos-Gear CG,
  * one grid barrier per iteration, block size chosen per (B, n)) -- stream-ordered, the host never
  * waits.  Only when srpde_poisson_coop_problems(n) is 0 (n > 1024) the call drives the split entry
- * points below (textbook CG) and polls convergence every 128 iterations, synchronising `stream`. */
+ * points below (textbook CG) and polls convergence every 128 iterations, synchronising `stream`.
+ * Magnitude range: the solve is equivariant under scaling of f (by a power of two: bit for bit, iteration counts
+ * included) while gamma0 = |f / theta|^2 summed over the grid and rtol^2 gamma0, where the iteration stops, are
+ * normal fp64 numbers, and delta0 <= 8 (n - 1)^2 gamma0 finite -- for rtol = 1e-12 and n <= 1024 about
+ * 2^-470 < |f / theta| < 2^490 per node.  (The Chronopoulos-Gear
+ * scalars are formed from inner products scaled by the power of two of gamma0's exponent, so no product of them
+ * leaves the range before gamma itself does.)  Outside it, and for non-finite f or theta <= 0, u is undefined. */
 int srpde_poisson_cg_batched(const double* f, const double* theta, double* u, int B, int n, double rtol, int maxit,
                              int* iters_out, void* workspace, size_t ws_bytes, hipStream_t stream);
 /* (Test hook: rtol < 0 solves to |rtol| but every cooperative grid-CG launch starts aborted -- iters_out = -1 for

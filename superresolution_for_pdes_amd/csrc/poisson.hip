@@ -80,13 +80,27 @@ __device__ __forceinline__ void block_sum2(double& a, double& b, double* slots) 
 // beta = gamma_new / gamma, alpha = gamma_new / (delta_new - beta gamma_new / alpha) = gn c / D with
 // c = gamma alpha, D = delta_new c - gamma_new^2; both from ONE division, 1 / (gamma D) (the three
 // chained divisions were ~35 of an iteration's ~200 VALU instructions per wave, all on its critical
-// path).  Magnitudes: gamma D ~ gamma^3, far inside fp64's range for rtol >= 1e-30.
-__device__ __forceinline__ void cg_scalars(double gn, double dn, double& gamma, double& alpha, double& beta) {
-  const double c = gamma * alpha;
-  const double D = dn * c - gn * gn;
-  const double rr = 1.0 / (gamma * D);
-  beta = gn * D * rr;
-  alpha = gn * c * gamma * rr;
+// path).  Magnitudes: gamma D ~ gamma^3 with gamma0 ~ n^2 |f / theta|^2 and gamma falling to rtol^2 gamma0, which
+// leaves fp64's range 2^+-1022 far from O(1) forcings (n = 100, rtol = 1e-12: |f / theta| below about 2^-145 or above
+// about 2^164): there the product underflows to 0 or overflows, and alpha, beta come out NaN.  So the three inner
+// products enter scaled by 2^e, e = cg_scale_exp(gamma0): gamma 2^e runs from [1, 2) down to rtol^2, the cube is far
+// inside the range for rtol >= 1e-30, and the solver is equivariant under power-of-two scalings of f wherever gamma0
+// and rtol^2 gamma0 themselves are normal numbers (include/srpde.h states that range).  The scaling is exact, and
+// beta and alpha are ratios in which the power of two cancels (c 2^e, D 2^2e, rr 2^-3e, every product rounded at the
+// same bit), so they are the unscaled formulas' bits wherever those were in range.
+// (gamma0 is the same in every lane: the exponent lives in a scalar register, not in one more vector register.
+// cg_lds_kernel forms the scalars behind a sched_barrier: with their arithmetic scheduled into the reduction's tail,
+// cg_lds_kernel<16> spilled four more registers.)
+__device__ __forceinline__ int cg_scale_exp(double gamma0) {
+  return __builtin_amdgcn_readfirstlane(gamma0 > 0.0 ? -ilogb(gamma0) : 0);
+}
+__device__ __forceinline__ void cg_scalars(double gn, double dn, int e, double& gamma, double& alpha, double& beta) {
+  const double gs = ldexp(gn, e), g = ldexp(gamma, e);
+  const double c = g * alpha;
+  const double D = ldexp(dn, e) * c - gs * gs;
+  const double rr = 1.0 / (g * D);
+  beta = gs * D * rr;
+  alpha = gs * c * g * rr;
   gamma = gn;
 }
 
@@ -153,6 +167,7 @@ __global__ __launch_bounds__(CG_MAXT) void cg_lds_kernel(const double* __restric
   __syncthreads();
   double gamma, delta;
   apply_reduce(gamma, delta);
+  const int sexp = cg_scale_exp(gamma);
   const double stop = rtol * rtol * gamma;
   const double g0 = gamma;
   double alpha = gamma / delta, beta = 0.0;
@@ -171,7 +186,8 @@ __global__ __launch_bounds__(CG_MAXT) void cg_lds_kernel(const double* __restric
                        // they precede the reduction barrier every thread has passed)
     double gn, dn;
     apply_reduce(gn, dn);
-    cg_scalars(gn, dn, gamma, alpha, beta);
+    __builtin_amdgcn_sched_barrier(0);
+    cg_scalars(gn, dn, sexp, gamma, alpha, beta);
   };
   // two iterations per trip: one per trip rotated the loop-carried vectors through register copies
   while (gamma > stop && it < maxit) {
@@ -240,6 +256,7 @@ __global__ __launch_bounds__(T) void cg_lds_n_kernel(const double* __restrict__ 
   __syncthreads();
   double gamma, delta;
   apply_reduce(gamma, delta);
+  const int sexp = cg_scale_exp(gamma);
   const double stop = rtol * rtol * gamma;
   const double g0 = gamma;
   double alpha = gamma / delta, beta = 0.0;
@@ -257,7 +274,7 @@ __global__ __launch_bounds__(T) void cg_lds_n_kernel(const double* __restrict__ 
     __syncthreads();
     double gn, dn;
     apply_reduce(gn, dn);
-    cg_scalars(gn, dn, gamma, alpha, beta);
+    cg_scalars(gn, dn, sexp, gamma, alpha, beta);
   };
   // two iterations per trip: the loop-carried vectors keep their registers (one iteration per trip
   // rotated them through copies, ~45 moves per iteration)
@@ -645,7 +662,7 @@ __global__ __launch_bounds__(GCC_T) void gcg_coop_kernel(const double* __restric
   ok = ok && coop_sync(g, ++epoch, &sflag);
   double gamma = 0.0, stop = 0.0, alpha = 0.0, beta = 0.0;
   bool done = false;
-  int it_done = maxit;
+  int it_done = maxit, sexp = 0;
   for (int k = 0; ok; ++k) {
     const int par = k & 1;
     // per-thread offsets re-derived every iteration: hoisted, they were 64-bit addresses per array and
@@ -690,10 +707,11 @@ __global__ __launch_bounds__(GCC_T) void gcg_coop_kernel(const double* __restric
     const double gn = sh[2 * NW], dn = sh[2 * NW + 1];
     if (k == 0) {
       stop = g.rtol * g.rtol * gn;
+      sexp = cg_scale_exp(gn);
       alpha = gn / dn;
       beta = 0.0;
     } else if (!done) {
-      cg_scalars(gn, dn, gamma, alpha, beta);   // the LDS kernels' one-division form (same rounding)
+      cg_scalars(gn, dn, sexp, gamma, alpha, beta);   // the LDS kernels' one-division form (same rounding)
     }
     if (!done) gamma = gn;
     if (!done && (gamma <= stop || k >= maxit)) {

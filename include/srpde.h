@@ -81,8 +81,9 @@ typedef struct ihipStream_t* hipStream_t;
  *  22  zero-flux (Neumann) sides for the divergence-form operator and its CG: srpde_div_apply_bc,
  *      srpde_div_step_rhs_bc, srpde_div_theta_grad_bc, srpde_div_cg_workspace_size_bc, srpde_div_cg_init_bc,
  *      srpde_div_cg_init_from_bc, srpde_div_cg_iterate_bc, srpde_poisson_sep_plan(_size),
- *      srpde_poisson_sep_workspace_size, srpde_poisson_sep_shift_batched */
-#define SRPDE_ABI_VERSION 22
+ *      srpde_poisson_sep_workspace_size, srpde_poisson_sep_shift_batched
+ *  23  zero-flux sides in the smoother and the physics loss: srpde_div_relax_bc, srpde_physics_loss_div_fwd_bc */
+#define SRPDE_ABI_VERSION 23
 
 /* Kernel-family bits (per call; bit 0 of the same argument is the accumulate flag): the forward / dgrad
  * families compute the same outputs, statistics and stored splits bit for bit, so these only route a call to
@@ -920,6 +921,40 @@ int srpde_div_cg_init_from_bc(const double* f, const double* u0, const double* t
 int srpde_div_cg_iterate_bc(const double* theta, int B, int n, int face_mean, int bc, double sigma, double sigma_p,
                             double rtol, int k_begin, int k_count, const void* plan, size_t plan_bytes, void* ws,
                             size_t ws_bytes, hipStream_t stream);
+/* srpde_div_relax with the sides bc (ABI 23; csrc/relax.hip, relax_kernel<DivOp<HARM, true>>: the same tiles, halo and
+ * sweeps per launch).  Only the face coefficients, formed once per launch, differ: a face with exactly one end inside
+ * the grid carries theta of that end on a ghost-ring side and 0.0 on a zero-flux side; nodes outside the grid stay
+ * fixed at 0.  One sweep, every operation rounded once in this order (no contraction), from the previous sweep's u:
+ *     once per node:  g = f / inv_h2
+ *                     w = omega / ((cE + cW) + (cS + cN))            a missing face enters as the coefficient 0.0
+ *     per sweep:      a  = (cE*(uE - u) + cW*(uW - u)) + (cS*(uS - u) + cN*(uN - u))
+ *                     u' = u + w * (a - g)
+ * a is the face sum of srpde_div_apply_bc in its order: the missing face is a coefficient 0 in its place, not a
+ * skipped term, so its product 0 * (0 - u) = -+0 is added like any other.  A host restatement in that order reproduces
+ * the result bit for bit, whatever the tiling or the launch split; bc = 0 runs srpde_div_relax's kernels and gives its
+ * bits.  The error operator is I - omega diag(-D)^-1 (-D) with D the operator with the sides bc: -D is still a
+ * symmetric, weakly diagonally dominant M-matrix (singular for bc = 15, where the constants are a fixed point of
+ * every sweep with f = 0), so for 0 < omega <= 1 no error component grows, and bc = 15 is allowed: a sweep never
+ * inverts D.  Refused: bc outside 0 .. 15; bc != 0 with interior_only != 0 (the ring is held and no ghost face is ever
+ * read); bc != 0 with n < 2 (a lone node with both faces of an axis missing can have cE + cW + cS + cN = 0).  The
+ * workspace is srpde_div_relax_workspace_size's; every other rule is srpde_div_relax's. */
+int srpde_div_relax_bc(const double* u_in, const double* f, const double* theta, double* u_out, int E, int n,
+                       int face_mean, int bc, double inv_h2, int sweeps, double omega, int interior_only,
+                       void* workspace, size_t ws_bytes, hipStream_t stream);
+/* srpde_physics_loss_div_fwd with the sides bc on the kind-0 (whole-domain) samples (ABI 23).  There a(y) and the
+ * adjoint Dt(m r) are the face sum with the sides bc (coefficient 0 for a missing ghost face, in its place; the
+ * operator stays symmetric), and D_theta 1 = -k_d theta with k_d the number of the node's ghost faces on ghost-ring
+ * sides only:
+ *     r = ((u_std a(y) + u_mean (-k_d theta)) / h^2 - f) / f_std          (fp32, in this split form)
+ * With bc = 15, k_d = 0 everywhere and the term does not see u_mean: D_theta 1 = 0.  A kind-1 sample (a crop, interior
+ * nodes counted) never reads a ghost face with a non-zero factor: it is computed with bc = 0, bit for bit as
+ * srpde_physics_loss_div_fwd computes it.  bc = 0 runs that entry's kernels.  bc outside 0 .. 15 is refused.  LDS,
+ * samples per workgroup, the fp64 partials in fixed order, the workspace (srpde_physics_loss_div_workspace_size) and
+ * the launches are srpde_physics_loss_div_fwd's; the gradient is scaled by srpde_physics_loss_bwd. */
+int srpde_physics_loss_div_fwd_bc(const float* y, const float* t, const float* x, const int* kind, const float* stats,
+                                  int B, int n, int face_mean, int bc, float weight, float inv_h2_std,
+                                  float inv_h2_sub, float* loss, float* dy_unit, void* workspace, size_t ws_bytes,
+                                  hipStream_t stream);
 
 /* ---- Row-sharded CG for ONE n x n problem over `world` ranks (the 640^2 ground
  *      truth of solve_multi_resolution, src/resolution_comparison.py:62-73).  Rank `rank` owns the

@@ -75,9 +75,15 @@ struct PointwiseLoss {
 // -- 51 KiB at n = 64, one sample per workgroup there, inside the 64 KiB that a kernel gets without raising its limit.
 // The y - t plane is not kept: the gradient pass reads t again (the workgroup's own lines, just read).  theta's halo
 // is 1: every face towards it is replaced by the ghost rule, so the mean never divides by 0.
-template <bool HARM>
+//
+// BC (srpde_physics_loss_div_fwd_bc): with the side mask bc (bit 0 the row 0 side, 1 row n - 1, 2 column 0, 3 column
+// n - 1; set: zero flux) on the kind-0 samples.  The residual and the adjoint take face_sum_bc -- the operator with
+// missing ghost faces is still symmetric -- and D_theta 1 = -k_d theta, k_d the number of the node's Dirichlet ghost
+// faces.  A kind-1 sample counts interior nodes only: its m r is 0 on the ring, so no ghost coefficient reaches its
+// loss or its gradient, and it is computed with mask 0, as DivLoss<HARM, false> computes it.
+template <bool HARM, bool BC = false>
 struct DivLoss {
-  static constexpr bool kDiv = true, kHarm = HARM;
+  static constexpr bool kDiv = true, kHarm = HARM, kBc = BC;
   static size_t lds_floats(int n) { return 3 * (size_t)(n + 2) * (n + 2); }
 };
 
@@ -86,13 +92,38 @@ template <bool HARM>
 __device__ __forceinline__ float loss_face_sum(const float* v, const float* th, int pitch, int i, int j, int n) {
   return face_sum<HARM>(v, th, pitch, j > 0, j < n - 1, i > 0, i < n - 1);
 }
+template <bool HARM>
+__device__ __forceinline__ float loss_face_sum_bc(const float* v, const float* th, int pitch, int i, int j, int n,
+                                                  int bc) {
+  return face_sum_bc<HARM>(v, th, pitch, j > 0, j < n - 1, i > 0, i < n - 1, !(bc & 4), !(bc & 8), !(bc & 1),
+                           !(bc & 2));
+}
 
-// grid: ceil(B / spw) workgroups; dynamic LDS: spw * Op::lds_floats(n) floats
+// what differs between DivLoss<HARM, false> and <HARM, true> at a node: the face sum, and the number of its ghost
+// faces that exist (all of the missing neighbours without a mask; those on ghost-ring sides with the mask sb)
+template <class Op>
+__device__ __forceinline__ float loss_face_sum_op(const float* v, const float* th, int pitch, int i, int j, int n,
+                                                  int sb) {
+  if constexpr (Op::kBc)
+    return loss_face_sum_bc<Op::kHarm>(v, th, pitch, i, j, n, sb);
+  else
+    return loss_face_sum<Op::kHarm>(v, th, pitch, i, j, n);
+}
+template <class Op>
+__device__ __forceinline__ int loss_ghost_count(int miss, int i, int j, int n, int sb) {
+  if constexpr (Op::kBc)
+    return (i == 0 && !(sb & 1)) + (i == n - 1 && !(sb & 2)) + (j == 0 && !(sb & 4)) + (j == n - 1 && !(sb & 8));
+  else
+    return miss;
+}
+
+// grid: ceil(B / spw) workgroups; dynamic LDS: spw * Op::lds_floats(n) floats; bc: the side mask, read by
+// DivLoss<HARM, true> alone
 template <class Op>
 __global__ __launch_bounds__(kPhysThreads) void physics_loss_kernel(
     const float* __restrict__ y, const float* __restrict__ t, const float* __restrict__ x,
     const int* __restrict__ kind, const float* __restrict__ stats, int B, int n, int spw, float weight, float ih2_std,
-    float ih2_sub, float* __restrict__ dy, double* __restrict__ part) {
+    float ih2_sub, float* __restrict__ dy, double* __restrict__ part, int bc) {
   extern __shared__ float lds[];
   __shared__ double sh[4];
   __shared__ long long shM;
@@ -152,10 +183,11 @@ __global__ __launch_bounds__(kPhysThreads) void physics_loss_kernel(
       const float tv = t[b * nn + rem];
       const int kd = kind[b];
       const float ih2 = kd ? ih2_sub : ih2_std;
-      const float ay = loss_face_sum<Op::kHarm>(ytile + c, ttile + c, P, i, j, n);
+      const int sb = Op::kBc && !kd ? bc : 0;   // a crop's ring is never counted: no pattern there
+      const float ay = loss_face_sum_op<Op>(ytile + c, ttile + c, P, i, j, n, sb);
       const int miss = (i == 0) + (i == n - 1) + (j == 0) + (j == n - 1);
       m = !kd || miss == 0;
-      const float d1 = -(float)miss * ttile[c];
+      const float d1 = -(float)loss_ghost_count<Op>(miss, i, j, n, sb) * ttile[c];
       const float lap = fmaf(sg_u, ay, mu_u * d1);
       r = (lap * ih2 - f) / sg_f;
       d = ytile[c] - tv;
@@ -201,7 +233,7 @@ __global__ __launch_bounds__(kPhysThreads) void physics_loss_kernel(
       const long long b = b0 + s;
       if constexpr (Op::kDiv) {
         const int c = s * T2 + (i + 1) * P + (j + 1);
-        const float aq = loss_face_sum<Op::kHarm>(qtile + c, ttile + c, P, i, j, n);
+        const float aq = loss_face_sum_op<Op>(qtile + c, ttile + c, P, i, j, n, Op::kBc && !kind[b] ? bc : 0);
         const float d = ytile[c] - t[b * nn + rem];
         dy[b * nn + rem] = fmaf(kind[b] ? c_sub : c_std, aq, c_mse * d);
       } else {
@@ -319,22 +351,26 @@ static size_t phys_workspace_size(int B, int n, size_t lds_floats) {
 }
 
 // the checks and the two launches of both loss entries; name: the entry's, kernel and lds_floats: its operator's,
-// face_mean: the divergence entry's argument (checked in its place among the others), null for the pointwise entry
+// face_mean: the divergence entries' argument (checked in its place among the others), null for the pointwise entry;
+// bc: srpde_physics_loss_div_fwd_bc's side mask, 0 for the other entries
 static int phys_loss_launch(const char* name, PhysLossKernel kernel, size_t lds_floats, const int* face_mean,
                             const float* y, const float* t, const float* x, const int* kind, const float* stats, int B,
                             int n, float weight, float inv_h2_std, float inv_h2_sub, float* loss, float* dy_unit,
-                            void* workspace, size_t ws_bytes, hipStream_t stream) {
+                            void* workspace, size_t ws_bytes, hipStream_t stream, int bc = 0) {
   SRPDE_CHECK_ARG(y && t && x && kind && stats && loss && workspace, "%s: null pointer", name);
   if (B <= 0 || n < kPhysMinN || n > kPhysMaxN)
     SRPDE_FAIL(kErrShape, "%s: bad shape B=%d n=%d (B >= 1, %d <= n <= %d)", name, B, n, kPhysMinN, kPhysMaxN);
   if (face_mean && *face_mean != 0 && *face_mean != 1)
     SRPDE_FAIL(kErrArg, "%s: face_mean=%d (0 arithmetic, 1 harmonic)", name, *face_mean);
+  if (bc < 0 || bc > 15)
+    SRPDE_FAIL(kErrArg, "%s: bc=%d is not a side mask (bits 0..3: row 0, row n-1, column 0, column n-1; set = zero flux)",
+               name, bc);
   if (reinterpret_cast<uintptr_t>(workspace) & 7u) SRPDE_FAIL(kErrAlign, "%s: workspace not 8-byte aligned", name);
   if (ws_bytes < phys_workspace_size(B, n, lds_floats)) SRPDE_FAIL(kErrWorkspace, "%s: workspace too small", name);
   const int spw = phys_spw(lds_floats), nb = phys_blocks(B, lds_floats);
   double* part = static_cast<double*>(workspace);
   hipLaunchKernelGGL(kernel, dim3(nb), dim3(kPhysThreads), (size_t)spw * lds_floats * sizeof(float), stream, y, t, x,
-                     kind, stats, B, n, spw, weight, inv_h2_std, inv_h2_sub, dy_unit, part);
+                     kind, stats, B, n, spw, weight, inv_h2_std, inv_h2_sub, dy_unit, part, bc);
   SRPDE_LAUNCH_CHECK(name);
   hipLaunchKernelGGL(physics_loss_final_kernel, dim3(1), dim3(kPhysThreads), 0, stream, part, nb,
                      (long long)B * n * n, weight, loss);
@@ -367,6 +403,19 @@ int srpde_physics_loss_div_fwd(const float* y, const float* t, const float* x, c
                           face_mean == 1 ? physics_loss_kernel<DivLoss<true>> : physics_loss_kernel<DivLoss<false>>,
                           DivLoss<false>::lds_floats(n), &face_mean, y, t, x, kind, stats, B, n, weight, inv_h2_std,
                           inv_h2_sub, loss, dy_unit, workspace, ws_bytes, stream);
+}
+
+// bc = 0 is srpde_physics_loss_div_fwd, kernel for kernel
+int srpde_physics_loss_div_fwd_bc(const float* y, const float* t, const float* x, const int* kind, const float* stats,
+                                  int B, int n, int face_mean, int bc, float weight, float inv_h2_std,
+                                  float inv_h2_sub, float* loss, float* dy_unit, void* workspace, size_t ws_bytes,
+                                  hipStream_t stream) {
+  PhysLossKernel kernel = face_mean == 1 ? physics_loss_kernel<DivLoss<true>> : physics_loss_kernel<DivLoss<false>>;
+  if (bc != 0)
+    kernel = face_mean == 1 ? physics_loss_kernel<DivLoss<true, true>> : physics_loss_kernel<DivLoss<false, true>>;
+  return phys_loss_launch("srpde_physics_loss_div_fwd_bc", kernel, DivLoss<false>::lds_floats(n), &face_mean, y, t, x,
+                          kind, stats, B, n, weight, inv_h2_std, inv_h2_sub, loss, dy_unit, workspace, ws_bytes, stream,
+                          bc);
 }
 
 int srpde_physics_loss_bwd(const float* dy_unit, long long count, const float* gout, float* dy, hipStream_t stream) {

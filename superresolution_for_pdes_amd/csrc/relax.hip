@@ -37,7 +37,8 @@
 //                   cV[9]               cV[r] is the face between rows r - 1 and r: cN of row r and cS of row r - 1
 //                                       49 doubles with u = 98 VGPRs
 // A face with exactly one end inside the grid carries theta of that end (the ghost-face rule of the in-grid node; the
-// outside node is fixed at 0 and never reads it), a face with no end inside carries 1.
+// outside node is fixed at 0 and never reads it), a face with no end inside carries 1.  DivOp<HARM, true>
+// (srpde_div_relax_bc): 0.0 instead of theta of that end when the outside end lies beyond a zero-flux side.
 //
 // Every u' is a pure function of its five u values and the node's constants in a fixed order, so the result does not
 // depend on T, K or how the sweeps are split over launches: it is bit-equal to one plain pass per sweep.
@@ -74,7 +75,11 @@ struct PointwiseOp {
   }
 };
 
-template <bool HARM>
+// BC: with the side mask bc of srpde_div_relax_bc (bit 0 the row 0 side, 1 row n - 1, 2 column 0, 3 column n - 1; set:
+// zero flux).  Only form() differs: a face with one end inside the grid carries 0.0 instead of theta of that end when
+// that side is zero-flux -- face_sum_bc's coefficient -- so the sweep multiplies the zero in (0 * (0 - u) = -+0) and
+// keeps face_sum_bc's order.  The mask is a kernel argument (uniform, scalar registers) read only in form().
+template <bool HARM, bool BC = false>
 struct DivOp {
   static constexpr bool kFaces = true;
   double omega, g[kRelaxR], w[kRelaxR], cE[kRelaxR], cW[kRelaxR], cV[kRelaxR + 1];
@@ -86,10 +91,19 @@ struct DivOp {
     const double m = face_mean<HARM>(ta, tb);
     return in_a && in_b ? m : (in_a ? ta : tb);
   }
+  // ghost_a: the ghost face that a has when b is outside the grid exists (that side is Dirichlet); ghost_b likewise
+  static __device__ __forceinline__ double face(double ta, double tb, bool in_a, bool in_b, bool ghost_a,
+                                                bool ghost_b) {
+    const double m = face_mean<HARM>(ta, tb);
+    return in_a && in_b ? m : (in_a ? (ghost_a ? ta : 0.0) : (in_b ? (ghost_b ? tb : 0.0) : tb));
+  }
 
   // the faces and w of the thread's strip from the staged theta plane
-  __device__ __forceinline__ void form(const double* th, int x, int y0, int gx, int gy0, int n) {
+  __device__ __forceinline__ void form(const double* th, int x, int y0, int gx, int gy0, int n, int bc) {
     constexpr int P = kRelaxP, R = kRelaxR;
+    // the outside end of a one-ended face lies above row 0 (N), below row n - 1 (S), left of column 0 (W) or right of
+    // column n - 1 (E); at a patch edge the rule also meets in-grid ends, on positions that are never live
+    const bool gh_n = !(bc & 1), gh_s = !(bc & 2), gh_w = !(bc & 4), gh_e = !(bc & 8);
     const bool col_in = gx >= 0 && gx < n, col_in_e = gx + 1 >= 0 && gx + 1 < n;
     // the face above the strip's first row; a strip at the patch's top edge has none (that row is never live)
     double t_prev = y0 > 0 ? th[(y0 - 1) * P + x] : 1.0;
@@ -101,14 +115,22 @@ struct DivOp {
       const bool in_c = col_in && row_in;
       const double tc = th[y * P + x];
       const double te = x + 1 < P ? th[y * P + x + 1] : 1.0;
-      cV[r] = face(tc, t_prev, in_c, in_prev);
-      cE[r] = face(tc, te, in_c, col_in_e && row_in && x + 1 < P);
+      if constexpr (BC) {
+        cV[r] = face(tc, t_prev, in_c, in_prev, gh_n, gh_s);
+        cE[r] = face(tc, te, in_c, col_in_e && row_in && x + 1 < P, gh_e, gh_w);
+      } else {
+        cV[r] = face(tc, t_prev, in_c, in_prev);
+        cE[r] = face(tc, te, in_c, col_in_e && row_in && x + 1 < P);
+      }
       t_prev = tc;
       in_prev = in_c;
     }
     const bool below_in = y0 + R < P && col_in && gy0 + R >= 0 && gy0 + R < n;
     const double t_below = y0 + R < P ? th[(y0 + R) * P + x] : 1.0;
-    cV[R] = face(t_prev, t_below, in_prev, below_in);
+    if constexpr (BC)
+      cV[R] = face(t_prev, t_below, in_prev, below_in, gh_s, gh_n);
+    else
+      cV[R] = face(t_prev, t_below, in_prev, below_in);
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       cW[r] = __shfl_up(cE[r], 1, 64);                 // lane 0 keeps its own: patch column 0 is never live
@@ -122,13 +144,14 @@ struct DivOp {
   }
 };
 
-// grid (tiles, tiles, E); ks <= K sweeps from u_in to u_out (ks = 0: a copy); wt: 0.25 * omega (PointwiseOp) or omega
+// grid (tiles, tiles, E); ks <= K sweeps from u_in to u_out (ks = 0: a copy); wt: 0.25 * omega (PointwiseOp) or omega;
+// bc: the side mask, read by DivOp<HARM, true> alone
 template <class Op>
 __global__ __launch_bounds__(kRelaxThreads) void relax_kernel(const double* __restrict__ u_in,
                                                               const double* __restrict__ f,
                                                               const double* __restrict__ theta,
                                                               double* __restrict__ u_out, int n, double inv_h2,
-                                                              double wt, int ks, int interior_only) {
+                                                              double wt, int ks, int interior_only, int bc) {
   constexpr int P = kRelaxP, K = kRelaxK, T = kRelaxT, R = kRelaxR;
   __shared__ double plane[2][P * P];
   const int x = threadIdx.x & 63, y0 = (threadIdx.x >> 6) * R;
@@ -160,7 +183,7 @@ __global__ __launch_bounds__(kRelaxThreads) void relax_kernel(const double* __re
   }
   __syncthreads();
   if constexpr (Op::kFaces) {
-    op.form(plane[1], x, y0, gx, gy0, n);
+    op.form(plane[1], x, y0, gx, gy0, n, bc);
     __syncthreads();                                   // sweep 1 writes the plane theta was staged in
   }
 
@@ -209,16 +232,24 @@ size_t relax_workspace_size(int E, int n, int sweeps) {
 }
 
 // the checks and launches of both entries; name: the entry's, kernel and wt: its relax_kernel instance and weight,
-// face_mean: the divergence entry's argument (checked in its place among the others), null for the pointwise entry
+// face_mean: the divergence entries' argument (checked in its place among the others), null for the pointwise entry;
+// bc: srpde_div_relax_bc's side mask, 0 for the other entries
 int relax_run(const char* name, RelaxKernel kernel, double wt, const int* face_mean, const double* u_in,
               const double* f, const double* theta, double* u_out, int E, int n, double inv_h2, int sweeps, double omega,
-              int interior_only, void* workspace, size_t ws_bytes, hipStream_t stream) {
+              int interior_only, void* workspace, size_t ws_bytes, hipStream_t stream, int bc = 0) {
   SRPDE_CHECK_ARG(u_in && f && theta && u_out, "%s: null pointer", name);
   if (E <= 0 || E > 65535 || n < 1 || n > kRelaxMaxN || (interior_only && n < 3))
     SRPDE_FAIL(kErrShape, "%s: bad shape E=%d n=%d (1 <= E <= 65535, 1 <= n <= %d, interior_only needs n >= 3)", name,
                E, n, kRelaxMaxN);
   if (face_mean && *face_mean != 0 && *face_mean != 1)
     SRPDE_FAIL(kErrArg, "%s: face_mean=%d (0 arithmetic, 1 harmonic)", name, *face_mean);
+  if (bc < 0 || bc > 15)
+    SRPDE_FAIL(kErrArg, "%s: bc=%d is not a side mask (bits 0..3: row 0, row n-1, column 0, column n-1; set = zero flux)",
+               name, bc);
+  if (bc && interior_only)
+    SRPDE_FAIL(kErrArg, "%s: bc=%d with interior_only: the ring is held and no ghost face is read", name, bc);
+  if (bc && n < 2)
+    SRPDE_FAIL(kErrShape, "%s: bc=%d needs n >= 2 (a lone node's face coefficients can all be 0)", name, bc);
   if (sweeps < 0) SRPDE_FAIL(kErrArg, "%s: sweeps=%d is negative", name, sweeps);
   if (!(omega > 0.0 && omega <= 1.0)) SRPDE_FAIL(kErrArg, "%s: omega=%g outside (0, 1]", name, omega);
   if (!(inv_h2 > 0.0) || !std::isfinite(inv_h2))
@@ -246,7 +277,7 @@ int relax_run(const char* name, RelaxKernel kernel, double wt, const int* face_m
     double* dst = ((launches - 1 - j) & 1) ? ws : u_out;
     const int ks = std::min(kRelaxK, sweeps - j * kRelaxK);
     hipLaunchKernelGGL(kernel, dim3(tiles, tiles, E), dim3(kRelaxThreads), 0, stream, src, f, theta, dst, n, inv_h2, wt,
-                       ks, interior_only);
+                       ks, interior_only, bc);
     SRPDE_LAUNCH_CHECK(name);
     src = dst;
   }
@@ -278,6 +309,16 @@ int srpde_div_relax(const double* u_in, const double* f, const double* theta, do
   return relax_run("srpde_div_relax", face_mean == 1 ? relax_kernel<DivOp<true>> : relax_kernel<DivOp<false>>, omega,
                    &face_mean, u_in, f, theta, u_out, E, n, inv_h2, sweeps, omega, interior_only, workspace, ws_bytes,
                    stream);
+}
+
+// bc = 0 is srpde_div_relax, kernel for kernel
+int srpde_div_relax_bc(const double* u_in, const double* f, const double* theta, double* u_out, int E, int n,
+                       int face_mean, int bc, double inv_h2, int sweeps, double omega, int interior_only,
+                       void* workspace, size_t ws_bytes, hipStream_t stream) {
+  RelaxKernel kernel = face_mean == 1 ? relax_kernel<DivOp<true>> : relax_kernel<DivOp<false>>;
+  if (bc != 0) kernel = face_mean == 1 ? relax_kernel<DivOp<true, true>> : relax_kernel<DivOp<false, true>>;
+  return relax_run("srpde_div_relax_bc", kernel, omega, &face_mean, u_in, f, theta, u_out, E, n, inv_h2, sweeps, omega,
+                   interior_only, workspace, ws_bytes, stream, bc);
 }
 
 }  // extern "C"

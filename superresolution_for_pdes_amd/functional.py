@@ -9,7 +9,15 @@ import torch
 import torch.nn as nn
 
 from . import hipops as H
-from .poisson import face_mean_arg
+from .poisson import check_bc, face_mean_arg
+
+
+def _bc_arg(form, bc):
+    """The side mask of ``bc`` (poisson.check_bc) for the divergence form's loss, None for none."""
+    mask = check_bc(bc)
+    if mask is not None and form != "divergence":
+        raise ValueError('bc belongs to form="divergence": the pointwise residual has the zero ghost ring')
+    return mask
 
 
 class _MSEFn(torch.autograd.Function):
@@ -51,8 +59,8 @@ class _PhysicsMSEFn(torch.autograd.Function):
     pass emits the gradient for grad_out = 1 (when one is wanted), the backward pass scales it."""
 
     @staticmethod
-    def forward(ctx, y, t, x, kind, stats, weight, inv_h2, want_grad, face_mean=None):
-        terms, unit = H.physics_loss_fwd(y, t, x, kind, stats, weight, inv_h2, want_grad, face_mean)
+    def forward(ctx, y, t, x, kind, stats, weight, inv_h2, want_grad, face_mean=None, bc=None):
+        terms, unit = H.physics_loss_fwd(y, t, x, kind, stats, weight, inv_h2, want_grad, face_mean, bc)
         ctx.unit = unit
         return terms
 
@@ -61,13 +69,15 @@ class _PhysicsMSEFn(torch.autograd.Function):
         if ctx.unit is None:
             raise RuntimeError("physics_mse_loss: backward through a loss evaluated without a gradient")
         dy = H.physics_loss_bwd(ctx.unit, gterms.contiguous())   # reads gterms[0], the total's grad_out
-        return dy, None, None, None, None, None, None, None, None
+        return dy, None, None, None, None, None, None, None, None, None
 
 
-def physics_loss_terms(y, t, x, kind, stats, weight, inv_h2=DEFAULT_INV_H2, form="pointwise", face_mean="harmonic"):
+def physics_loss_terms(y, t, x, kind, stats, weight, inv_h2=DEFAULT_INV_H2, form="pointwise", face_mean="harmonic",
+                       bc=None):
     """The device tensor (mse + weight * pde, mse, pde) behind ``physics_mse_loss``; differentiable through its
     first element only (the other two are reports of the same pass)."""
     mean = face_mean_arg(form, face_mean)
+    mask = _bc_arg(form, bc)
     if y.shape != t.shape:
         raise ValueError(f"physics_mse_loss: shape mismatch {tuple(y.shape)} vs {tuple(t.shape)}")
     if y.dim() != 4 or y.shape[1] != 1 or y.shape[2] != y.shape[3]:
@@ -91,18 +101,20 @@ def physics_loss_terms(y, t, x, kind, stats, weight, inv_h2=DEFAULT_INV_H2, form
     want_grad = torch.is_grad_enabled() and y.requires_grad
     return _PhysicsMSEFn.apply(y.contiguous(), t.contiguous(), x.contiguous(), kind.contiguous(),
                                stats.contiguous(), float(weight), (float(inv_h2[0]), float(inv_h2[1])), want_grad,
-                               mean)
+                               mean, mask)
 
 
 def physics_mse_loss(y, t, x, kind, stats, weight, inv_h2=DEFAULT_INV_H2, form="pointwise",
-                     face_mean="harmonic") -> torch.Tensor:
+                     face_mean="harmonic", bc=None) -> torch.Tensor:
     """mean((y - t)^2) + weight * L_pde: the MSE plus the mean squared residual of the discrete equation
     theta * L u = f that the samples solve, evaluated from the normalised fields (include/srpde.h,
     srpde_physics_loss_fwd).  x: the model input (theta and f are its channels 1 and 2), kind [B] int32: 0 for a
     whole-domain sample, 1 for a crop; stats: the dataset's six statistics on the device.
     ``form="divergence"``: the residual of div(theta grad u) = f with ``face_mean`` on the faces instead
-    (srpde_physics_loss_div_fwd), for samples that solve the conservative problem."""
-    return physics_loss_terms(y, t, x, kind, stats, weight, inv_h2, form, face_mean)[0]
+    (srpde_physics_loss_div_fwd), for samples that solve the conservative problem.  ``bc`` (poisson.check_bc, e.g.
+    ``"ddnn"``), with that form: the whole-domain (kind 0) samples solve the problem with those zero-flux sides
+    (srpde_physics_loss_div_fwd_bc); crops count interior nodes only and are scored as without it."""
+    return physics_loss_terms(y, t, x, kind, stats, weight, inv_h2, form, face_mean, bc)[0]
 
 
 class PhysicsMSELoss(nn.Module):
@@ -113,12 +125,13 @@ class PhysicsMSELoss(nn.Module):
     needs_inputs = True
 
     def __init__(self, weight: float, stats: torch.Tensor, inv_h2=DEFAULT_INV_H2, form: str = "pointwise",
-                 face_mean: str = "harmonic"):
+                 face_mean: str = "harmonic", bc=None):
         super().__init__()
         if weight < 0:
             raise ValueError("PhysicsMSELoss: weight >= 0")
         face_mean_arg(form, face_mean)
-        self.form, self.face_mean = form, face_mean
+        _bc_arg(form, bc)
+        self.form, self.face_mean, self.bc = form, face_mean, bc
         self.weight = float(weight)
         self.inv_h2 = (float(inv_h2[0]), float(inv_h2[1]))
         self.register_buffer("stats", stats.detach().float().contiguous().clone(), persistent=False)
@@ -126,6 +139,6 @@ class PhysicsMSELoss(nn.Module):
 
     def forward(self, input, target, x, kind):  # noqa: A002
         terms = physics_loss_terms(input, target, x, kind, self.stats, self.weight, self.inv_h2, self.form,
-                                   self.face_mean)
+                                   self.face_mean, self.bc)
         self.last_terms = terms.detach()
         return terms[0]

@@ -1214,12 +1214,25 @@ def mse_bwd(y, t, gout):
 
 
 # ------------------------------ MSE + PDE residual ---------------------------------
-def physics_loss_fwd(y, t, x, kind, stats, weight, inv_h2, want_grad=True, face_mean=None):
+def _side_mask(name, bc, face_mean):
+    """The side mask of the *_bc entries (0 .. 15) or None / 0 for the entries without one; host-only checks."""
+    if bc is None:
+        return 0
+    if isinstance(bc, bool) or not isinstance(bc, int) or not 0 <= bc <= 15:
+        raise ValueError(f"{name}: bc must be None or a side mask 0..15 (poisson.check_bc), got {bc!r}")
+    if bc and face_mean is None:
+        raise ValueError(f"{name}: bc belongs to the divergence form (face_mean 0 / 1)")
+    return bc
+
+
+def physics_loss_fwd(y, t, x, kind, stats, weight, inv_h2, want_grad=True, face_mean=None, bc=None):
     """srpde_physics_loss_fwd: y, t [B, 1, n, n] and x [B, 3, n, n] fp32, kind [B] int32, stats 6 floats, all on one
     device -> (loss [3] = (mse + weight * pde, mse, pde), the gradient for grad_out = 1 or None).  ``inv_h2``: the
     1 / h^2 of (kind 0, kind 1).  Without ``want_grad`` no gradient is computed or written.  ``face_mean`` None: the
     pointwise residual theta * L u - f; 0 (arithmetic) or 1 (harmonic): the divergence-form residual
-    div(theta grad u) - f through srpde_physics_loss_div_fwd."""
+    div(theta grad u) - f through srpde_physics_loss_div_fwd.  ``bc``: a side mask (poisson.check_bc) for the
+    kind-0 samples of the divergence form, through srpde_physics_loss_div_fwd_bc; None / 0: the entry without one."""
+    mask = _side_mask("physics_loss_fwd", bc, face_mean)
     _fields("physics_loss_fwd", F32, y, t, x, stats)
     _fields("physics_loss_fwd", torch.int32, kind)
     if y.dim() != 4 or y.shape[1] != 1 or y.shape[2] != y.shape[3] or t.shape != y.shape:
@@ -1234,6 +1247,11 @@ def physics_loss_fwd(y, t, x, kind, stats, weight, inv_h2, want_grad=True, face_
     ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=y.device)
     loss = torch.empty(3, dtype=F32, device=y.device)
     unit = torch.empty_like(y) if want_grad else None
+    if mask:
+        call("srpde_physics_loss_div_fwd_bc", y.data_ptr(), t.data_ptr(), x.data_ptr(), kind.data_ptr(),
+             stats.data_ptr(), B, n, int(face_mean), mask, float(weight), float(inv_h2[0]), float(inv_h2[1]),
+             loss.data_ptr(), _p(unit), ws.data_ptr(), nbytes, stream_ptr())
+        return loss, unit
     if div:
         call("srpde_physics_loss_div_fwd", y.data_ptr(), t.data_ptr(), x.data_ptr(), kind.data_ptr(),
              stats.data_ptr(), B, n, int(face_mean), float(weight), float(inv_h2[0]), float(inv_h2[1]),
@@ -1278,11 +1296,18 @@ def pde_relax_sweeps_per_launch():
     return int(query("srpde_pde_relax_sweeps_per_launch"))
 
 
-def pde_relax(u, f, theta, inv_h2, sweeps, omega=0.8, interior_only=False, face_mean=None):
+def pde_relax(u, f, theta, inv_h2, sweeps, omega=0.8, interior_only=False, face_mean=None, bc=None):
     """``sweeps`` weighted-Jacobi sweeps on fp64 fields [E, n, n] -> a new [E, n, n] fp64 tensor (the inputs are left
     alone); over all nodes against a zero ghost ring, or with the ring of the fields held (``interior_only``).
     ``face_mean`` None: srpde_pde_relax, the sweeps of theta * A u * inv_h2 = f; 0 arithmetic / 1 harmonic:
-    srpde_div_relax, the sweeps of div(theta grad u) * inv_h2 = f with that mean on the faces."""
+    srpde_div_relax, the sweeps of div(theta grad u) * inv_h2 = f with that mean on the faces.  ``bc``: a side mask
+    (poisson.check_bc) of that form, through srpde_div_relax_bc: zero-flux sides have no ghost face.  None / 0: the
+    entry without one.  A mask goes with neither ``interior_only`` nor n < 2."""
+    mask = _side_mask("pde_relax", bc, face_mean)
+    if mask and interior_only:
+        raise ValueError("pde_relax: bc with interior_only: the ring is held and no ghost face is read")
+    if mask and f.dim() == 3 and f.shape[-1] < 2:
+        raise ValueError("pde_relax: bc needs n >= 2")
     _fields("pde_relax", torch.float64, u, f, theta)
     if f.dim() != 3 or f.shape[1] != f.shape[2] or u.shape != f.shape or theta.shape != f.shape:
         raise ValueError("pde_relax: u, f and theta must share one [E, n, n] shape")
@@ -1292,6 +1317,10 @@ def pde_relax(u, f, theta, inv_h2, sweeps, omega=0.8, interior_only=False, face_
     out = torch.empty_like(u)
     nbytes = int(query("srpde_div_relax_workspace_size" if div else "srpde_pde_relax_workspace_size", E, n, sweeps))
     ws = torch.empty(nbytes // 8, dtype=torch.float64, device=f.device) if nbytes else None
+    if mask:
+        call("srpde_div_relax_bc", u.data_ptr(), f.data_ptr(), theta.data_ptr(), out.data_ptr(), E, n, int(face_mean),
+             mask, float(inv_h2), sweeps, float(omega), 0, _p(ws), nbytes, stream_ptr())
+        return out
     call("srpde_div_relax" if div else "srpde_pde_relax", u.data_ptr(), f.data_ptr(), theta.data_ptr(), out.data_ptr(),
          E, n, *((int(face_mean),) if div else ()), float(inv_h2), sweeps, float(omega), int(bool(interior_only)),
          _p(ws), nbytes, stream_ptr())

@@ -24,6 +24,13 @@ fine / coarse, the super-fine subdomain solves, the calibration set) by poisson.
 iterations, so a batch still needs no host sync.  It needs a ``theta_range``: with theta = 1 the two forms coincide.
 Draws, crop starts, statistics arithmetic and sample identity are the same for both.
 
+Sides.  ``bc`` (poisson.check_bc, e.g. ``"ddnn"``), with ``form="divergence"``: the three solves take zero-flux sides
+(solve_div(bc=), the same fixed iteration count; the separable plans are built in the constructor).  ``"nnnn"`` is
+singular without a shift and refused; ``"dddd"`` is no pattern.  ``describe()`` always carries ``bc``.
+``state_dict()`` carries it only for a stream that has a pattern -- a stream without one keeps the two-key state it
+always had, so earlier checkpoints still load -- and ``load_state_dict`` refuses a state whose pattern (or lack of
+one) differs from the stream's: resuming under other sides would silently change the samples.
+
 Global sample indices.  Local slot i of step t on rank r of ``world`` is sample
     s = (t * world + r) * B + i,
 so a world of W ranks at step t consumes exactly the samples of the single-process steps t*W .. t*W + W - 1.  The
@@ -108,10 +115,16 @@ class FrozenSet:
 class SampleStream:
     def __init__(self, seed, batch_size, sub_fraction=0.5, k_std=(0.5, 5.0), k_sub=(0.5, 12.0), theta_range=None,
                  solver="dst", rank=0, world=1, device="cuda", n_coarse=20, n_fine=40, n_superfine=80, n_calib=2048,
-                 form="pointwise", face_mean="harmonic", pcg_iters=None):
+                 form="pointwise", face_mean="harmonic", pcg_iters=None, bc=None):
         # (checked first: these refusals need no device)
         self.form = P.check_form(form)
         P.check_face_mean(face_mean)
+        self.bc = None if P.check_bc(bc) is None else bc     # the pattern; "dddd" is no pattern
+        if self.bc is not None and self.form != "divergence":
+            raise ValueError('SampleStream: bc belongs to form="divergence" (the pointwise solvers have the zero '
+                             "ghost ring)")
+        if self.bc == "nnnn":
+            raise ValueError('SampleStream: bc="nnnn" is singular without a shift (the constants): no unique sample')
         if self.form == "divergence":
             if theta_range is None:
                 raise ValueError('SampleStream: form="divergence" needs a theta_range -- with theta = 1 it is the '
@@ -143,6 +156,8 @@ class SampleStream:
         if self.solver == "dst" or self.form == "divergence":   # the plans are built here, never inside a step (or a stream capture)
             for n in (n_coarse, n_fine, n_superfine):
                 P.dst_plan(n, device)
+                if self.bc is not None:
+                    P.sep_plan(n, self.bc, device)
         # frozen statistics, PDEDataset's arithmetic on the calibration set (the one host read of the stream)
         cal = self.fixed_set(n_calib, CALIB_FIRST)
         u_mean, u_std = cal["u_fine"].mean(), cal["u_fine"].std()
@@ -160,6 +175,9 @@ class SampleStream:
 
     # ---- generation -------------------------------------------------------------------------------------------
     def _solve(self, f, theta):
+        if self.bc is not None:         # the same fixed mode with the separable preconditioner of those sides
+            return P.solve_div(f, theta, face_mean=self.face_mean, bc=self.bc, precond_shift=0.0, maxit=self.pcg_iters,
+                               check_every=0, check=False, device=self.device)
         if self.form == "divergence":   # fixed mode: pcg_iters iterations, no host sync, nothing read back
             return P.solve_div(f, theta, face_mean=self.face_mean, maxit=self.pcg_iters, check_every=0, check=False,
                                device=self.device)
@@ -170,7 +188,7 @@ class SampleStream:
         return {"seed": self.seed, "batch_size": self.batch_size, "sub_fraction": self.sub_fraction,
                 "k_std": list(self.k_std), "k_sub": list(self.k_sub),
                 "theta_range": None if self.theta_range is None else list(self.theta_range), "solver": self.solver,
-                "form": self.form, "face_mean": self.face_mean, "pcg_iters": self.pcg_iters,
+                "form": self.form, "face_mean": self.face_mean, "pcg_iters": self.pcg_iters, "bc": self.bc,
                 "rank": self.rank, "world": self.world,
                 "n_coarse": self.n_coarse, "n_fine": self.n_fine, "n_superfine": self.n_superfine}
 
@@ -256,9 +274,14 @@ class SampleStream:
 
     # ---- resuming ---------------------------------------------------------------------------------------------
     def state_dict(self) -> dict:
-        return {"seed": self.seed, "step": self.step}
+        state = {"seed": self.seed, "step": self.step}
+        if self.bc is not None:             # a stream without a pattern keeps the state it always had
+            state["bc"] = self.bc
+        return state
 
     def load_state_dict(self, state: dict):
+        if state.get("bc") != self.bc:
+            raise ValueError(f"SampleStream: the state belongs to bc={state.get('bc')!r}, this stream has {self.bc!r}")
         if int(state["seed"]) != self.seed:
             raise ValueError(f"SampleStream: the state belongs to seed {state['seed']}, this stream has {self.seed}")
         self.step = int(state["step"])

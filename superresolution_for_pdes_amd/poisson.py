@@ -676,7 +676,7 @@ def residual_metrics(u, f, theta, interior_only: bool = False, inv_h2: float = N
 
 
 def relax(u, f, theta, sweeps: int, omega: float = 0.8, interior_only: bool = False, inv_h2: float = None,
-          device="cuda", form: str = "pointwise", face_mean: str = "harmonic"):
+          device="cuda", form: str = "pointwise", face_mean: str = "harmonic", bc=None):
     """``sweeps`` weighted-Jacobi sweeps of theta * A u / h^2 = f (A the 5-point stencil with a zero ghost ring):
     u <- u + (omega / 4) (A u - h^2 f / theta), each from the previous sweep's u.  It damps the error at the grid
     scale (for omega = 0.8 every component with a wavenumber >= pi / 2 shrinks by at least 0.6 per sweep) and, for
@@ -687,9 +687,21 @@ def relax(u, f, theta, sweeps: int, omega: float = 0.8, interior_only: bool = Fa
     Stream-ordered, no host sync (srpde_pde_relax).
     ``form="divergence"``: the sweeps of div(theta grad u) = f with ``face_mean`` on the faces instead,
     u <- u + omega (D_theta u - f) / sum of the node's four face coefficients (srpde_div_relax; include/srpde.h states
-    the rounding order); the same guarantee for 0 < omega <= 1.  ``face_mean`` belongs to that form."""
+    the rounding order); the same guarantee for 0 < omega <= 1.  ``face_mean`` belongs to that form.
+    ``bc`` (``check_bc``, e.g. ``"ddnn"``), with that form: an "n" side is zero-flux -- its ghost faces have coefficient
+    0, in the sum that divides as well (srpde_div_relax_bc) -- so a solve_div(bc=) solution is a fixed point of its own
+    smoother.  ``"nnnn"`` is allowed (a sweep inverts nothing); ``interior_only`` and n < 2 are refused with a pattern.
+    None (default) and ``"dddd"`` make today's call."""
     from . import hipops as H
     mean = face_mean_arg(form, face_mean)
+    bc = check_bc(bc)
+    if bc is not None:
+        if mean is None:
+            raise ValueError('bc belongs to form="divergence": the pointwise operator has the zero ghost ring')
+        if interior_only:
+            raise ValueError("relax: bc with interior_only: the ring is held and no ghost face is read")
+        if (u.shape if hasattr(u, "shape") else np.shape(u))[-1] < 2:
+            raise ValueError("relax: bc needs n >= 2 (a lone node's face coefficients can all be 0)")
     if int(sweeps) < 0:
         raise ValueError(f"relax: sweeps must be >= 0, got {sweeps}")
     if not 0.0 < float(omega) <= 1.0:
@@ -701,7 +713,7 @@ def relax(u, f, theta, sweeps: int, omega: float = 0.8, interior_only: bool = Fa
         theta = theta.expand_as(f).contiguous()
     n = u.shape[-1]
     inv_h2 = float((n - 1) ** 2 if inv_h2 is None else inv_h2)
-    return H.pde_relax(u, f, theta, inv_h2, int(sweeps), float(omega), interior_only, mean)
+    return H.pde_relax(u, f, theta, inv_h2, int(sweeps), float(omega), interior_only, mean, bc)
 
 
 def solve_batched(f, theta, rtol: float = DEFAULT_RTOL, maxit: int = None, device="cuda",

@@ -56,7 +56,7 @@ def _f64(a, device) -> torch.Tensor:
     return (t[None] if t.dim() == 2 else t).contiguous()
 
 
-def _check_polish(name, polish, polish_omega, polish_form="pointwise", polish_face_mean="harmonic"):
+def _check_polish(name, polish, polish_omega, polish_form="pointwise", polish_face_mean="harmonic", polish_bc=None):
     if not isinstance(polish, numbers.Integral) or polish < 0:
         raise ValueError(f"{name}: polish must be an integer >= 0, got {polish!r}")
     if not 0.0 < float(polish_omega) <= 1.0:
@@ -64,6 +64,8 @@ def _check_polish(name, polish, polish_omega, polish_form="pointwise", polish_fa
     P.check_face_mean(polish_face_mean)
     if P.check_form(polish_form) == "pointwise" and polish_face_mean != "harmonic":
         raise ValueError(f'{name}: polish_face_mean belongs to polish_form="divergence"')
+    if P.check_bc(polish_bc) is not None and polish_form != "divergence":
+        raise ValueError(f'{name}: polish_bc belongs to polish_form="divergence"')
 
 
 def _level_stats(stats, u_cur, f_next, theta_next, u_next):
@@ -88,15 +90,16 @@ def _level_stats(stats, u_cur, f_next, theta_next, u_next):
 def upscale_level(model, u_cur, f_next, theta_next, *, tile: int = 20, stride: int = 10, window: str = "linear",
                   stats="input", max_batch: int = MAX_BATCH, graphs: bool = True, u_next=None, polish: int = 0,
                   polish_omega: float = 0.8, polish_form: str = "pointwise",
-                  polish_face_mean: str = "harmonic") -> torch.Tensor:
+                  polish_face_mean: str = "harmonic", polish_bc=None) -> torch.Tensor:
     """One level: u_cur [E, S, S] with f_next / theta_next [E, 2S, 2S] -> [E, 2S, 2S] fp64 on the model's device.
 
     ``stats``: "input" (no ground truth), "truth" (needs ``u_next``: cascade_level_stats of the next level's
     solution, as the reference) or an [E, 6] / [6] fp32 tensor {u_mean, u_std, f_mean, f_std, theta_mean, theta_std}.
     The U-Net runs through eval_forward in chunks of ``max_batch`` windows.  ``polish`` > 0: that many
     weighted-Jacobi sweeps (``polish_omega`` in (0, 1]) of the whole-domain equation on the blended field:
-    theta * L u = f, or div(theta grad u) = f with ``polish_form="divergence"`` and ``polish_face_mean``."""
-    _check_polish("upscale_level", polish, polish_omega, polish_form, polish_face_mean)
+    theta * L u = f, or div(theta grad u) = f with ``polish_form="divergence"`` and ``polish_face_mean``;
+    ``polish_bc`` (poisson.check_bc, e.g. ``"ddnn"``) gives that form's sweeps zero-flux sides."""
+    _check_polish("upscale_level", polish, polish_omega, polish_form, polish_face_mean, polish_bc)
     model.eval()
     device = next(model.parameters()).device
     u_cur, f_next, theta_next = (_f64(a, device) for a in (u_cur, f_next, theta_next))
@@ -111,7 +114,7 @@ def upscale_level(model, u_cur, f_next, theta_next, *, tile: int = 20, stride: i
     u = H.tiled_blend_denorm(y.contiguous(), st, E, S, tile, stride, window)
     if polish > 0:
         u = P.relax(u, f_next, theta_next, polish, polish_omega, inv_h2=float((2 * S - 1) ** 2), device=device,
-                    form=polish_form, face_mean=polish_face_mean)
+                    form=polish_form, face_mean=polish_face_mean, bc=polish_bc)
     return u
 
 
@@ -120,12 +123,13 @@ def upscale_cascade(model, u_start, f: Dict[int, object], theta: Dict[int, objec
                     tile: int = 20, stride: int = 10, window: str = "linear", stats="input", max_batch: int = MAX_BATCH,
                     graphs: bool = True, u_truth: Dict[int, object] = None, polish: int = 0,
                     polish_omega: float = 0.8, polish_form: str = "pointwise",
-                    polish_face_mean: str = "harmonic") -> torch.Tensor:
+                    polish_face_mean: str = "harmonic", polish_bc=None) -> torch.Tensor:
     """The level loop: from u_start [E, S0, S0] by doublings to ``target_resolution``; ``f`` and ``theta`` are
     {res: [E, res, res]} for every resolution above S0 on the way.  ``u_truth`` {res: [E, res, res]} is needed for
-    stats="truth" only.  ``polish`` / ``polish_omega`` / ``polish_form`` / ``polish_face_mean``: as upscale_level, at
-    every level, so the next level reads the polished field.  -> [E, target, target] fp64 (device tensor)."""
-    _check_polish("upscale_cascade", polish, polish_omega, polish_form, polish_face_mean)
+    stats="truth" only.  ``polish`` / ``polish_omega`` / ``polish_form`` / ``polish_face_mean`` / ``polish_bc``: as
+    upscale_level, at every level, so the next level reads the polished field.  -> [E, target, target] fp64 (device
+    tensor)."""
+    _check_polish("upscale_cascade", polish, polish_omega, polish_form, polish_face_mean, polish_bc)
     device = next(model.parameters()).device
     cur = _f64(u_start, device)
     res = cur.shape[-1]
@@ -139,6 +143,6 @@ def upscale_cascade(model, u_start, f: Dict[int, object], theta: Dict[int, objec
         cur = upscale_level(model, cur, f[nxt], theta[nxt], tile=tile, stride=stride, window=window, stats=stats,
                             max_batch=max_batch, graphs=graphs, u_next=None if u_truth is None else u_truth[nxt],
                             polish=polish, polish_omega=polish_omega, polish_form=polish_form,
-                            polish_face_mean=polish_face_mean)
+                            polish_face_mean=polish_face_mean, polish_bc=polish_bc)
         res = nxt
     return cur

@@ -353,11 +353,26 @@ def arg_parser():
                          "div(theta grad u) = f (poisson.solve_div; needs --online and --online-theta)")
     ap.add_argument("--face-mean", choices=("arithmetic", "harmonic"), default="harmonic",
                     help="with --operator divergence: the mean of the two nodal theta on a cell face")
+    ap.add_argument("--bc", default=None, metavar="PATTERN",
+                    help='with --online and --operator divergence: the sides of the samples\' problem, four of "d" '
+                         '(zero ghost ring) / "n" (zero flux) for (row 0, row n-1, column 0, column n-1), e.g. ddnn; '
+                         "it reaches the stream, the validation set and the --pde-div-weight term")
     return ap
 
 
 def check_operator_args(args):
-    """The refusals of --operator / --face-mean / --pde-div-weight, before any device work."""
+    """The refusals of --operator / --face-mean / --pde-div-weight / --bc, before any device work."""
+    if args.bc is not None:
+        from .poisson import check_bc
+        try:
+            mask = check_bc(args.bc)
+        except ValueError as e:
+            raise SystemExit(f"--bc: {e}")
+        if args.online is None or args.operator != "divergence":
+            raise SystemExit("--bc needs --online and --operator divergence (the pointwise solvers and the fixed "
+                             "dataset generators have the zero ghost ring)")
+        if mask == 15:
+            raise SystemExit("--bc nnnn is singular without a shift (the constants): no unique sample")
     if args.pde_div_weight < 0:
         raise SystemExit("--pde-div-weight: a weight >= 0")
     if args.pde_div_weight > 0:
@@ -389,22 +404,23 @@ def online_loaders(args, config, rank, world, device):
     if args.online < 1:
         raise SystemExit("--online: at least one step per epoch")
     stream = SampleStream(42, config["batch_size"], theta_range=args.online_theta, solver=args.solver, rank=rank,
-                          world=world, device=device, form=args.operator, face_mean=args.face_mean)
+                          world=world, device=device, form=args.operator, face_mean=args.face_mean, bc=args.bc)
     with_kind = args.pde_weight > 0 or args.pde_div_weight > 0
     return (OnlineBatchLoader(stream, args.online, with_kind=with_kind),
             stream.validation_loader(ONLINE_VAL_SAMPLES, config["batch_size"], with_kind=with_kind))
 
 
-def physics_criterion(weight, stats, save_dir=None, form="pointwise", face_mean="harmonic"):
+def physics_criterion(weight, stats, save_dir=None, form="pointwise", face_mean="harmonic", bc=None):
     """The criterion of --pde-weight (``form="pointwise"``) or --pde-div-weight (``"divergence"``, with the run's
-    ``face_mean``); with ``save_dir`` its settings go to physics_loss.json beside config.json."""
+    ``face_mean`` and ``bc``); with ``save_dir`` its settings go to physics_loss.json beside config.json."""
     from .functional import PhysicsMSELoss
-    criterion = PhysicsMSELoss(weight, stats, form=form, face_mean=face_mean)
+    criterion = PhysicsMSELoss(weight, stats, form=form, face_mean=face_mean, bc=bc)
     if save_dir is not None:
         with open(Path(save_dir) / "physics_loss.json", "w") as f:
             json.dump({"weight": criterion.weight, "inv_h2": list(criterion.inv_h2),
                        "stats": [float(v) for v in stats.detach().cpu()], "form": criterion.form,
-                       "face_mean": criterion.face_mean if form == "divergence" else None}, f, indent=4)
+                       "face_mean": criterion.face_mean if form == "divergence" else None, "bc": criterion.bc},
+                      f, indent=4)
     return criterion
 
 
@@ -440,6 +456,8 @@ def main(argv=None):
         recorded = dict(config)
         if args.operator != "pointwise":   # (the pointwise run's config.json keeps the reference's keys)
             recorded.update(operator=args.operator, face_mean=args.face_mean)
+        if args.bc is not None:
+            recorded.update(bc=args.bc)
         with open(save_dir / "config.json", "w") as f:
             json.dump(recorded, f, indent=4)
     writer = ScalarWriter(str(save_dir / "tensorboard")) if rank == 0 else None
@@ -469,7 +487,7 @@ def main(argv=None):
         net = DataParallel(model)
     if args.pde_div_weight > 0:
         criterion = physics_criterion(args.pde_div_weight, stats, save_dir if rank == 0 else None, "divergence",
-                                      args.face_mean)
+                                      args.face_mean, args.bc)
     elif with_kind:
         criterion = physics_criterion(args.pde_weight, stats, save_dir if rank == 0 else None)
     else:

@@ -82,7 +82,11 @@ typedef struct ihipStream_t* hipStream_t;
  *      srpde_div_step_rhs_bc, srpde_div_theta_grad_bc, srpde_div_cg_workspace_size_bc, srpde_div_cg_init_bc,
  *      srpde_div_cg_init_from_bc, srpde_div_cg_iterate_bc, srpde_poisson_sep_plan(_size),
  *      srpde_poisson_sep_workspace_size, srpde_poisson_sep_shift_batched
- *  23  zero-flux sides in the smoother and the physics loss: srpde_div_relax_bc, srpde_physics_loss_div_fwd_bc */
+ *  23  zero-flux sides in the smoother and the physics loss: srpde_div_relax_bc, srpde_physics_loss_div_fwd_bc
+ *      extended, the number kept (entries were added, none changed: a binding built against the earlier 23 header
+ *      reads every argument as before): boundary values and prescribed fluxes for the divergence-form operator,
+ *      srpde_div_apply_bd, srpde_div_step_rhs_bd, srpde_div_cg_init_from_bd, srpde_div_theta_grad_bd,
+ *      srpde_div_bd_grad, srpde_div_relax_bd */
 #define SRPDE_ABI_VERSION 23
 
 /* Kernel-family bits (per call; bit 0 of the same argument is the accumulate flag): the forward / dgrad
@@ -955,6 +959,73 @@ int srpde_physics_loss_div_fwd_bc(const float* y, const float* t, const float* x
                                   int B, int n, int face_mean, int bc, float weight, float inv_h2_std,
                                   float inv_h2_sub, float* loss, float* dy_unit, void* workspace, size_t ws_bytes,
                                   hipStream_t stream);
+
+/* ---- Boundary values and prescribed fluxes (ABI 23, extended).  The entries above are homogeneous: a Dirichlet side's ghost
+ *      ring holds 0, a zero-flux side's flux is 0.  The entries here take the side mask bc, 0 .. 15 as above (0: four
+ *      Dirichlet sides), and boundary data bd, fp64 [Bd][4][n], 8-byte aligned, with bd_stride = 4 n doubles between
+ *      problems (Bd = B) or 0 (Bd = 1, one [4][n] for every problem).  The sides are in the mask's order -- row 0,
+ *      row n - 1, column 0, column n - 1 -- entry k of a row side belongs to column k, entry k of a column side to
+ *      row k; a corner node receives data from both of its sides.
+ *          Dirichlet side (bit clear): bd is the value g of the ghost node beyond the edge node a.  The ghost face
+ *              keeps its coefficient theta_a and contributes theta_a * (g - u_a) to the face sum: the term of the
+ *              entries above with g in place of 0.
+ *          flux side (bit set): bd is the outward flux q = theta du/dn through the face half a cell beyond the edge
+ *              node.  The ghost face keeps the coefficient 0; the node's divergence gains q / h.
+ *      A_bd u, every operation rounded once in this order (no contraction):
+ *          1. the face sum of srpde_div_apply_bc on halo tiles whose out-of-grid entries beyond Dirichlet sides hold g
+ *             (beyond flux sides and in the halo's corners they hold 0 as before);
+ *          2. * inv_h2;
+ *          3. only at a node with at least one flux-side ghost face: + ((qE + qW) + (qS + qN)) * inv_h, an absent term
+ *             0.0, inv_h = sqrt(inv_h2) formed once on the host;
+ *          4. - sigma * u as srpde_div_apply_shift (sigma = 0: the unshifted kernel).
+ *      So A_bd u = D_bc u - sigma u + b(bd, theta) with b = A_bd 0 at sigma = 0, non-zero on edge nodes only: an affine
+ *      extension.  (D_bc - sigma I) u = f - b is the problem solved; the iteration, the preconditioner, the bound
+ *      cond <= theta_max / theta_min and the adjoint solve are the homogeneous ones.  bd = 0 gives the numbers of the
+ *      *_bc namesakes (a zero may differ in sign).  The data is read for out-of-grid halo entries and edge nodes only.
+ *      Every kernel is one launch on the namesake's tiles: vector stores, no atomics, no grid barrier, no scratch.
+ *      bc = 15 with sigma = 0 stays singular and refused; the compatibility of its data is the caller's business. ---- */
+/* y = A_bd u: srpde_div_apply_bc's arguments and launch plus the data; y must not alias u, theta or bd. */
+int srpde_div_apply_bd(const double* u, const double* theta, double* y, int B, int n, int face_mean, double inv_h2,
+                       double sigma, int bc, const double* bd, long long bd_stride, hipStream_t stream);
+/* srpde_div_step_rhs_bc with A_bd u (sigma = 0, inv_h2 = (n - 1)^2, inv_h = n - 1) in place of D_theta u in
+ * Crank-Nicolson's right-hand side, for data constant in time: rhs = (2 f - sigma * u) - A_bd u.  Backward Euler reads
+ * no neighbour: its launch and bits are srpde_div_step_rhs's. */
+int srpde_div_step_rhs_bd(const double* u, const double* f, const double* theta, double* rhs, int B, int n,
+                          int face_mean, double sigma, int cn, int bc, const double* bd, long long bd_stride,
+                          hipStream_t stream);
+/* The start of the CG for A_bd u = f, i.e. (D_bc - sigma I) u = f - b: x = u0 (u0 == NULL: zeros, the bits of a zero
+ * field), r = f - A_bd u0 in one fused pass, z = M^-1 r, then srpde_div_cg_init_from's k = 0 pass at the real rtol.
+ * The stop rule's reference norm is |f - b|: per node b = (ghost faces' terms theta_a * g, summed (E + W) + (S + N),
+ * 0.0 for a face to a grid node) * inv_h2, then + ((qE + qW) + (qS + qN)) * inv_h on a flux-side node, then the one
+ * subtraction f - b; its square is summed in the same pass with srpde_div_cg_init_from's partials for |f|^2 (per-block
+ * partials, fixed order).  resid becomes |r| / |f - b|, and |f - b| = 0 returns u = 0, which then is the solution.  So
+ * Laplace's equation, f = 0 with g != 0, iterates: |f| alone would stop it at u = 0 after no iteration.
+ * bc = 0 takes the sine-transform plan and a workspace of srpde_div_cg_workspace_size -- all-Dirichlet data keeps the
+ * one-launch transform at small n -- and is followed by srpde_div_cg_iterate(_shift); bc != 0 takes the separable plan
+ * for bc and srpde_div_cg_workspace_size_bc, followed by srpde_div_cg_iterate_bc.  Those and srpde_div_cg_finish run
+ * unchanged: the iteration is homogeneous. */
+int srpde_div_cg_init_from_bd(const double* f, const double* u0, const double* theta, int B, int n, int face_mean,
+                              int bc, double sigma, double sigma_p, double rtol, const double* bd, long long bd_stride,
+                              const void* plan, size_t plan_bytes, void* ws, size_t ws_bytes, hipStream_t stream);
+/* srpde_div_theta_grad_bc with g in u's out-of-grid halo beyond Dirichlet sides and 0 in lam's: such a ghost face gives
+ * (1 * (g - u_a)) * (0 - lam_a).  The prescribed flux does not depend on theta. */
+int srpde_div_theta_grad_bd(const double* u, const double* lam, const double* theta, double* g_out, int B, int n,
+                            int face_mean, double inv_h2, double scale, int bc, const double* bd, long long bd_stride,
+                            hipStream_t stream);
+/* out [B][4][n] = d<lam, A_bd u>/d bd, with a the side's edge node of entry k: (inv_h2 * theta_a) * lam_a on a Dirichlet
+ * side, inv_h * lam_a (inv_h = sqrt(inv_h2)) on a flux side.  It depends on neither u nor the face mean.  One
+ * edge-gather launch; out must not alias lam or theta.  A caller with Bd = 1 sums out over the batch. */
+int srpde_div_bd_grad(const double* lam, const double* theta, double* out, int B, int n, double inv_h2, int bc,
+                      hipStream_t stream);
+/* srpde_div_relax_bc with boundary data (no interior_only; n >= 2; bc = 0: four Dirichlet sides with values).  An
+ * out-of-grid position straight beyond a Dirichlet side's edge node holds g and stays fixed at it through every sweep;
+ * a node on a flux side forms, once per launch,
+ *     g = (f - ((qE + qW) + (qS + qN)) * inv_h) / inv_h2                 (every other node: g = f / inv_h2)
+ * and the sweep is srpde_div_relax_bc's, untouched: a fixed point satisfies A_bd u = f.  Bit-equal to one plain host
+ * pass per sweep in this order, whatever the tiling and the launch split. */
+int srpde_div_relax_bd(const double* u_in, const double* f, const double* theta, double* u_out, int E, int n,
+                       int face_mean, int bc, double inv_h2, int sweeps, double omega, const double* bd,
+                       long long bd_stride, void* workspace, size_t ws_bytes, hipStream_t stream);
 
 /* ---- Row-sharded CG for ONE n x n problem over `world` ranks (the 640^2 ground
  *      truth of solve_multi_resolution, src/resolution_comparison.py:62-73).  Rank `rank` owns the

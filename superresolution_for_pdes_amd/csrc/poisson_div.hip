@@ -58,6 +58,13 @@
 // (face_sum_bc / face_grad_sum_bc in place of face_sum / face_grad_sum) and step (c) is the separable solve; update,
 // r.z, the k = 0 pass, the freeze rule and finish are the code above, untouched.
 //
+// Boundary data (the *_bd entries).  bd [Bd][4][n] gives the sides values: the ghost value g beyond a Dirichlet side's
+// edge node, the outward flux q through a zero-flux side's ghost face (div_stencil.h).  A_bd u = D_bc u - sigma u + b:
+// the tile bodies with BD set stage g into the out-of-grid halo of u (bd_halo, reached only by entries outside the
+// grid) and add ((qE + qW) + (qS + qN)) * inv_h at flux-side nodes after the face sum's * inv_h2.  The solve is
+// (D_bc - sigma I) u = f - b: srpde_div_cg_init_from_bd forms r = f - A_bd u0 and the partials of (f - b)^2, the stop
+// rule's reference, in one pass on either workspace (mask 0: the sine plan's), and the iteration above runs unchanged.
+//
 // Adjoint (srpde_div_theta_grad).  D_theta is symmetric, so the adjoint of the solve is the same solve, and the
 // gradient in theta of <lam, D_theta u> is the local pair gradient G(u, lam; theta) of div_theta_grad_kernel.
 #include <cmath>
@@ -158,10 +165,13 @@ __device__ __forceinline__ double node_face_grad_sum(const double* us, const dou
 // y = D_theta u for one tile.  PCG: u = p = z + beta p_old is formed here (header, launch (a)).
 // SHIFT: y = D_theta u - sigma * u (the product, then the subtraction, after the face sum's * inv_h2).
 // BC: with the side mask bc (the body of div_apply_kernel and div_apply_bc_kernel).
-template <bool PCG, bool HARM, bool SHIFT, bool BC>
+// BD (with BC, of div_apply_bd_kernel): bd is the problem's boundary data; the out-of-grid halo of u holds g beyond
+// Dirichlet sides (bd_halo) and a node on a flux side gains bd_flux_sum * inv_h after the face sum's * inv_h2.
+template <bool PCG, bool HARM, bool SHIFT, bool BC, bool BD = false>
 __device__ __forceinline__ void div_apply_tile(const double* __restrict__ u, const double* __restrict__ theta,
                                                double* __restrict__ y, const DivCG& g, double inv_h2, double sigma,
-                                               int n, int k, int bc) {
+                                               int n, int k, int bc, const double* __restrict__ bd = nullptr,
+                                               double inv_h = 0.0) {
   __shared__ double us[kDivLY * kDivLX];
   __shared__ double ts[kDivLY * kDivLX];
   __shared__ double red[4];
@@ -190,6 +200,8 @@ __device__ __forceinline__ void div_apply_tile(const double* __restrict__ u, con
       uv = u[at];
       tv = theta[at];
       if (PCG && k > 1) uv = uv + beta * pold[at];
+    } else if (BD) {
+      uv = bd_halo(bd, gy, gx, n, bc);
     }
     us[i] = uv;
     ts[i] = tv;
@@ -207,6 +219,7 @@ __device__ __forceinline__ void div_apply_tile(const double* __restrict__ u, con
         const int c = ly * kDivLX + lx;
         const double uc = us[c];
         double yv = node_face_sum<HARM, BC>(us, ts, c, gx, gy, n, bc) * inv_h2;
+        if (BD && bd_flux_node(gy, gx, n, bc)) yv = yv + bd_flux_sum(bd, gy, gx, n, bc) * inv_h;
         if (SHIFT) yv = yv - sigma * uc;
         const long long at = base + (long long)gy * n + gx;
         y[at] = yv;
@@ -237,6 +250,18 @@ __global__ __launch_bounds__(kDivThreads) void div_apply_bc_kernel(const double*
                                                                    double* __restrict__ y, DivCG g, double inv_h2,
                                                                    double sigma, int n, int k, int bc) {
   div_apply_tile<PCG, HARM, SHIFT, true>(u, theta, y, g, inv_h2, sigma, n, k, bc);
+}
+
+// y = A_bd u = D_theta u - sigma * u + b(bd, theta) (srpde_div_apply_bd); bd_stride: 4 n, or 0 for one [4][n] shared
+template <bool HARM, bool SHIFT>
+__global__ __launch_bounds__(kDivThreads) void div_apply_bd_kernel(const double* __restrict__ u,
+                                                                   const double* __restrict__ theta,
+                                                                   double* __restrict__ y, double inv_h2, double sigma,
+                                                                   int n, int bc, const double* __restrict__ bd,
+                                                                   long long bd_stride, double inv_h) {
+  const DivCG none = {};
+  div_apply_tile<false, HARM, SHIFT, true, true>(u, theta, y, none, inv_h2, sigma, n, 0, bc,
+                                                 bd + (long long)blockIdx.z * bd_stride, inv_h);
 }
 
 // launch (b): x += alpha p, r -= alpha q, partial of r.r
@@ -332,10 +357,14 @@ __global__ __launch_bounds__(kDivThreads) void div_init_kernel(const double* __r
 // r.r.  The walk and the sums are div_init_kernel's, so for u0 = 0 (D 0 = +0, f - 0 = f) both partials are its bits.
 // SHIFT: r = f - (D_theta u0 - sigma * u0), the operator as div_apply_kernel<.., SHIFT> forms it (+0 for u0 = 0 too).
 // BC: with the side mask bc (the body of div_init_from_kernel and div_init_from_bc_kernel).
-template <bool HARM, bool SHIFT, bool BC>
+// BD (with BC, of div_init_from_bd_kernel): r = f - A_bd u0 with the halo and the flux term of div_apply_tile<BD>; u0
+// may be null (zeros: the same operations on 0.0); the first partial is of (f - b)^2, b = A_bd 0 at sigma = 0, i.e.
+// b = face_ghost_sum * inv_h2, + bd_flux_sum * inv_h on a flux-side node, then the one subtraction f - b.
+template <bool HARM, bool SHIFT, bool BC, bool BD = false>
 __device__ __forceinline__ void div_init_from_tile(const double* __restrict__ f, const double* __restrict__ u0,
                                                    const double* __restrict__ theta, const DivCG& g, double inv_h2,
-                                                   double sigma, int bc) {
+                                                   double sigma, int bc, const double* __restrict__ bd = nullptr,
+                                                   double inv_h = 0.0) {
   __shared__ double us[kDivLY * kDivLX];
   __shared__ double ts[kDivLY * kDivLX];
   __shared__ double red[4];
@@ -348,8 +377,10 @@ __device__ __forceinline__ void div_init_from_tile(const double* __restrict__ f,
     double uv = 0.0, tv = 1.0;
     if (gy >= 0 && gy < n && gx >= 0 && gx < n) {
       const long long at = base + (long long)gy * n + gx;
-      uv = u0[at];
+      uv = (BD && !u0) ? 0.0 : u0[at];
       tv = theta[at];
+    } else if (BD) {
+      uv = bd_halo(bd, gy, gx, n, bc);
     }
     us[i] = uv;
     ts[i] = tv;
@@ -366,12 +397,23 @@ __device__ __forceinline__ void div_init_from_tile(const double* __restrict__ f,
       if (gy < n) {
         const int c = ly * kDivLX + lx;
         double du = node_face_sum<HARM, BC>(us, ts, c, gx, gy, n, bc) * inv_h2;
+        double bv = 0.0;
+        if (BD) {
+          bv = face_ghost_sum(us + c, ts + c, kDivLX, gx > 0, gx + 1 < n, gy > 0, gy + 1 < n, !(bc & 4), !(bc & 8),
+                              !(bc & 1), !(bc & 2)) * inv_h2;
+          if (bd_flux_node(gy, gx, n, bc)) {
+            const double q = bd_flux_sum(bd, gy, gx, n, bc) * inv_h;
+            du = du + q;
+            bv = bv + q;
+          }
+        }
         if (SHIFT) du = du - sigma * us[c];
         const long long at = base + (long long)gy * n + gx;
-        const double fv = f[at];
+        double fv = f[at];
         const double rv = fv - du;
         g.x[at] = us[c];
         g.r[at] = rv;
+        if (BD) fv = fv - bv;
         accf = accf + fv * fv;
         accr = accr + rv * rv;
       }
@@ -399,6 +441,17 @@ __global__ __launch_bounds__(kDivThreads) void div_init_from_bc_kernel(const dou
                                                                        const double* __restrict__ theta, DivCG g,
                                                                        double inv_h2, double sigma, int bc) {
   div_init_from_tile<HARM, SHIFT, true>(f, u0, theta, g, inv_h2, sigma, bc);
+}
+
+template <bool HARM, bool SHIFT>
+__global__ __launch_bounds__(kDivThreads) void div_init_from_bd_kernel(const double* __restrict__ f,
+                                                                       const double* __restrict__ u0,
+                                                                       const double* __restrict__ theta, DivCG g,
+                                                                       double inv_h2, double sigma, int bc,
+                                                                       const double* __restrict__ bd,
+                                                                       long long bd_stride, double inv_h) {
+  div_init_from_tile<HARM, SHIFT, true, true>(f, u0, theta, g, inv_h2, sigma, bc,
+                                              bd + (long long)blockIdx.z * bd_stride, inv_h);
 }
 
 // the k = 0 pass after div_init_from_kernel and the sine solve: the block's partial of r.z where iteration 1 reads
@@ -448,10 +501,12 @@ __global__ __launch_bounds__(kDivThreads) void div_rz_from_kernel(DivCG g, doubl
 // 2 f is exact, D_theta u is div_apply_kernel's (face sum * inv_h2), every other operation is rounded once in the
 // order written; f == nullptr is f = 0.  Backward Euler reads no neighbour and stages nothing in LDS.
 // BC: with the side mask bc (the body of div_step_rhs_kernel and div_step_rhs_bc_kernel).
-template <bool CN, bool HARM, bool BC>
+// BD (with BC and CN, of div_step_rhs_bd_kernel): A_bd u at sigma = 0 in place of D_theta u, as div_apply_tile<BD>.
+template <bool CN, bool HARM, bool BC, bool BD = false>
 __device__ __forceinline__ void div_step_rhs_tile(const double* __restrict__ u, const double* __restrict__ f,
                                                   const double* __restrict__ theta, double* __restrict__ rhs,
-                                                  double inv_h2, double sigma, int n, int bc) {
+                                                  double inv_h2, double sigma, int n, int bc,
+                                                  const double* __restrict__ bd = nullptr, double inv_h = 0.0) {
   __shared__ double us[CN ? kDivLY * kDivLX : 1];
   __shared__ double ts[CN ? kDivLY * kDivLX : 1];
   const int tid = threadIdx.x, b = blockIdx.z;
@@ -466,6 +521,8 @@ __device__ __forceinline__ void div_step_rhs_tile(const double* __restrict__ u, 
         const long long at = base + (long long)gy * n + gx;
         uv = u[at];
         tv = theta[at];
+      } else if (BD) {
+        uv = bd_halo(bd, gy, gx, n, bc);
       }
       us[i] = uv;
       ts[i] = tv;
@@ -484,7 +541,8 @@ __device__ __forceinline__ void div_step_rhs_tile(const double* __restrict__ u, 
       const double fv = f ? f[at] : 0.0;
       if (CN) {
         const int c = ly * kDivLX + lx;
-        const double du = node_face_sum<HARM, BC>(us, ts, c, gx, gy, n, bc) * inv_h2;
+        double du = node_face_sum<HARM, BC>(us, ts, c, gx, gy, n, bc) * inv_h2;
+        if (BD && bd_flux_node(gy, gx, n, bc)) du = du + bd_flux_sum(bd, gy, gx, n, bc) * inv_h;
         rhs[at] = (2.0 * fv - sigma * us[c]) - du;
       } else {
         rhs[at] = fv - sigma * u[at];
@@ -512,14 +570,29 @@ __global__ __launch_bounds__(kDivThreads) void div_step_rhs_bc_kernel(const doub
   div_step_rhs_tile<true, HARM, true>(u, f, theta, rhs, inv_h2, sigma, n, bc);
 }
 
+template <bool HARM>
+__global__ __launch_bounds__(kDivThreads) void div_step_rhs_bd_kernel(const double* __restrict__ u,
+                                                                      const double* __restrict__ f,
+                                                                      const double* __restrict__ theta,
+                                                                      double* __restrict__ rhs, double inv_h2,
+                                                                      double sigma, int n, int bc,
+                                                                      const double* __restrict__ bd,
+                                                                      long long bd_stride, double inv_h) {
+  div_step_rhs_tile<true, HARM, true, true>(u, f, theta, rhs, inv_h2, sigma, n, bc,
+                                            bd + (long long)blockIdx.z * bd_stride, inv_h);
+}
+
 // g = scale * G(u, lam; theta), G_a = inv_h2 * sum over a's faces of dc/dtheta_a (u_b - u_a) (lam_b - lam_a): the
 // gradient in theta of <lam, D_theta u>.  A gather over the halo tiles of u, lam and theta (3 x 34 x 66 doubles of
 // LDS, under the 64 KiB static limit): each node reads its own four faces, nothing is accumulated across nodes.
 // BC: with the side mask bc (the body of div_theta_grad_kernel and div_theta_grad_bc_kernel).
-template <bool HARM, bool BC>
+// BD (with BC, of div_theta_grad_bd_kernel): u's out-of-grid halo holds g beyond Dirichlet sides, lam's stays 0, so a
+// ghost face gives (1 * (g - u_a)) * (0 - lam_a); the prescribed flux does not depend on theta and adds nothing.
+template <bool HARM, bool BC, bool BD = false>
 __device__ __forceinline__ void div_theta_grad_tile(const double* __restrict__ u, const double* __restrict__ lam,
                                                     const double* __restrict__ theta, double* __restrict__ gout,
-                                                    double inv_h2, double scale, int n, int bc) {
+                                                    double inv_h2, double scale, int n, int bc,
+                                                    const double* __restrict__ bd = nullptr) {
   __shared__ double us[kDivLY * kDivLX];
   __shared__ double ls[kDivLY * kDivLX];
   __shared__ double ts[kDivLY * kDivLX];
@@ -535,6 +608,8 @@ __device__ __forceinline__ void div_theta_grad_tile(const double* __restrict__ u
       uv = u[at];
       lv = lam[at];
       tv = theta[at];
+    } else if (BD) {
+      uv = bd_halo(bd, gy, gx, n, bc);
     }
     us[i] = uv;
     ls[i] = lv;
@@ -572,6 +647,32 @@ __global__ __launch_bounds__(kDivThreads) void div_theta_grad_bc_kernel(const do
                                                                         double* __restrict__ gout, double inv_h2,
                                                                         double scale, int n, int bc) {
   div_theta_grad_tile<HARM, true>(u, lam, theta, gout, inv_h2, scale, n, bc);
+}
+
+template <bool HARM>
+__global__ __launch_bounds__(kDivThreads) void div_theta_grad_bd_kernel(const double* __restrict__ u,
+                                                                        const double* __restrict__ lam,
+                                                                        const double* __restrict__ theta,
+                                                                        double* __restrict__ gout, double inv_h2,
+                                                                        double scale, int n, int bc,
+                                                                        const double* __restrict__ bd,
+                                                                        long long bd_stride) {
+  div_theta_grad_tile<HARM, true, true>(u, lam, theta, gout, inv_h2, scale, n, bc,
+                                        bd + (long long)blockIdx.z * bd_stride);
+}
+
+// out [B][4][n] = d<lam, A_bd u>/d bd: (inv_h2 * theta_a) * lam_a on a Dirichlet side, inv_h * lam_a on a flux side,
+// a the side's edge node of entry k.  grid (ceil(n / 256), 4 sides, B): an edge gather, no node is shared.
+__global__ __launch_bounds__(256) void div_bd_grad_kernel(const double* __restrict__ lam,
+                                                          const double* __restrict__ theta, double* __restrict__ out,
+                                                          int n, int bc, double inv_h2, double inv_h) {
+  const int k = (int)blockIdx.x * 256 + threadIdx.x, side = blockIdx.y, b = blockIdx.z;
+  if (k >= n) return;
+  const int gy = side == 0 ? 0 : (side == 1 ? n - 1 : k);
+  const int gx = side == 2 ? 0 : (side == 3 ? n - 1 : k);
+  const long long at = (long long)b * n * n + (long long)gy * n + gx;
+  const double lv = lam[at];
+  out[((long long)b * 4 + side) * n + k] = ((bc >> side) & 1) ? inv_h * lv : (inv_h2 * theta[at]) * lv;
 }
 
 __global__ __launch_bounds__(256) void div_finish_kernel(DivCG g, double* __restrict__ u, int* __restrict__ iters,
@@ -1013,6 +1114,166 @@ int srpde_div_cg_iterate_bc(const double* theta, int B, int n, int face_mean, in
                             size_t ws_bytes, hipStream_t stream) {
   return div_cg_iterate("srpde_div_cg_iterate_bc", theta, B, n, face_mean, sigma, sigma_p, rtol, k_begin, k_count,
                         plan, plan_bytes, ws, ws_bytes, stream, bc < 0 ? 16 : bc);
+}
+
+// ---- boundary data (the *_bd entries): the side mask 0 .. 15 (0: four Dirichlet sides with values), bd [Bd][4][n]
+static int div_check_bd(const char* name, int n, int bc, const double* bd, long long bd_stride) {
+  if (int rc = div_check_bc(name, bc < 0 ? 16 : bc)) return rc;
+  if (!bd) SRPDE_FAIL(kErrArg, "%s: null boundary data", name);
+  if (reinterpret_cast<uintptr_t>(bd) & 7u) SRPDE_FAIL(kErrAlign, "%s: bd not 8-byte aligned", name);
+  if (bd_stride != 0 && bd_stride != 4LL * n)
+    SRPDE_FAIL(kErrArg, "%s: bd_stride=%lld is neither 4 n = %lld ([B][4][n]) nor 0 (one [4][n] for every problem)", name,
+               bd_stride, 4LL * n);
+  return 0;
+}
+
+int srpde_div_apply_bd(const double* u, const double* theta, double* y, int B, int n, int face_mean, double inv_h2,
+                       double sigma, int bc, const double* bd, long long bd_stride, hipStream_t stream) {
+  const char* name = "srpde_div_apply_bd";
+  SRPDE_CHECK_ARG(u && theta && y, "%s: null pointer", name);
+  if (int rc = div_check(name, B, n, face_mean)) return rc;
+  if (int rc = div_check_bd(name, n, bc, bd, bd_stride)) return rc;
+  if (!(inv_h2 > 0.0) || !std::isfinite(inv_h2))
+    SRPDE_FAIL(kErrArg, "%s: inv_h2=%g must be positive and finite", name, inv_h2);
+  if (int rc = div_check_sigma(name, "sigma", sigma)) return rc;
+  if ((reinterpret_cast<uintptr_t>(u) | reinterpret_cast<uintptr_t>(theta) | reinterpret_cast<uintptr_t>(y)) & 7u)
+    SRPDE_FAIL(kErrAlign, "%s: a pointer is not 8-byte aligned", name);
+  if (y == u || y == theta || y == bd) SRPDE_FAIL(kErrArg, "%s: y aliases an input (a node reads its neighbours)", name);
+  const double inv_h = std::sqrt(inv_h2);
+  const dim3 grid = div_grid(B, n), block(kDivThreads);
+  switch ((sigma != 0.0 ? 2 : 0) + (face_mean ? 1 : 0)) {
+    case 0:
+      hipLaunchKernelGGL((div_apply_bd_kernel<false, false>), grid, block, 0, stream, u, theta, y, inv_h2, 0.0, n, bc,
+                         bd, bd_stride, inv_h);
+      break;
+    case 1:
+      hipLaunchKernelGGL((div_apply_bd_kernel<true, false>), grid, block, 0, stream, u, theta, y, inv_h2, 0.0, n, bc,
+                         bd, bd_stride, inv_h);
+      break;
+    case 2:
+      hipLaunchKernelGGL((div_apply_bd_kernel<false, true>), grid, block, 0, stream, u, theta, y, inv_h2, sigma, n, bc,
+                         bd, bd_stride, inv_h);
+      break;
+    default:
+      hipLaunchKernelGGL((div_apply_bd_kernel<true, true>), grid, block, 0, stream, u, theta, y, inv_h2, sigma, n, bc,
+                         bd, bd_stride, inv_h);
+  }
+  SRPDE_LAUNCH_CHECK(name);
+  return 0;
+}
+
+int srpde_div_step_rhs_bd(const double* u, const double* f, const double* theta, double* rhs, int B, int n,
+                          int face_mean, double sigma, int cn, int bc, const double* bd, long long bd_stride,
+                          hipStream_t stream) {
+  const char* name = "srpde_div_step_rhs_bd";
+  if (int rc = div_check_bd(name, n, bc, bd, bd_stride)) return rc;
+  // backward Euler reads no neighbour, so no data either: srpde_div_step_rhs_bc's checks and launch
+  if (cn != 1) return div_step_rhs(name, u, f, theta, rhs, B, n, face_mean, sigma, cn, bc, stream);
+  SRPDE_CHECK_ARG(u && theta && rhs, "%s: null pointer", name);
+  if (int rc = div_check(name, B, n, face_mean)) return rc;
+  if (int rc = div_check_sigma(name, "sigma", sigma)) return rc;
+  if ((reinterpret_cast<uintptr_t>(u) | reinterpret_cast<uintptr_t>(f) | reinterpret_cast<uintptr_t>(theta) |
+       reinterpret_cast<uintptr_t>(rhs)) & 7u)
+    SRPDE_FAIL(kErrAlign, "%s: a pointer is not 8-byte aligned", name);
+  if (rhs == u || rhs == theta || rhs == f || rhs == bd)
+    SRPDE_FAIL(kErrArg, "%s: rhs aliases an input (a node reads its neighbours)", name);
+  const double inv_h = (double)(n - 1), inv_h2 = inv_h * inv_h;
+  const dim3 grid = div_grid(B, n), block(kDivThreads);
+  if (face_mean)
+    hipLaunchKernelGGL(div_step_rhs_bd_kernel<true>, grid, block, 0, stream, u, f, theta, rhs, inv_h2, sigma, n, bc, bd,
+                       bd_stride, inv_h);
+  else
+    hipLaunchKernelGGL(div_step_rhs_bd_kernel<false>, grid, block, 0, stream, u, f, theta, rhs, inv_h2, sigma, n, bc, bd,
+                       bd_stride, inv_h);
+  SRPDE_LAUNCH_CHECK(name);
+  return 0;
+}
+
+int srpde_div_cg_init_from_bd(const double* f, const double* u0, const double* theta, int B, int n, int face_mean,
+                              int bc, double sigma, double sigma_p, double rtol, const double* bd, long long bd_stride,
+                              const void* plan, size_t plan_bytes, void* ws, size_t ws_bytes, hipStream_t stream) {
+  const char* name = "srpde_div_cg_init_from_bd";
+  SRPDE_CHECK_ARG(f && theta, "%s: null pointer", name);
+  if (int rc = div_check(name, B, n, face_mean)) return rc;
+  if (int rc = div_check_bd(name, n, bc, bd, bd_stride)) return rc;
+  if (int rc = div_check_sigma(name, "sigma", sigma)) return rc;
+  if (int rc = div_check_sigma(name, "sigma_p", sigma_p)) return rc;
+  if (int rc = div_check_singular(name, bc, "sigma", sigma)) return rc;
+  if (int rc = div_check_singular(name, bc, "sigma_p", sigma_p)) return rc;
+  if ((reinterpret_cast<uintptr_t>(f) | reinterpret_cast<uintptr_t>(u0) | reinterpret_cast<uintptr_t>(theta)) & 7u)
+    SRPDE_FAIL(kErrAlign, "%s: a pointer is not 8-byte aligned", name);
+  if (!(rtol >= 0.0)) SRPDE_FAIL(kErrArg, "%s: rtol=%g must be >= 0", name, rtol);
+  // mask 0: the sine plan and the workspace of srpde_div_cg_workspace_size; else the separable plan and the _bc one
+  const int pbc = bc ? bc : -1;
+  if (int rc = div_check_plan(name, n, plan, plan_bytes, pbc)) return rc;
+  if (int rc = div_check_ws(name, B, n, ws, ws_bytes, bc != 0)) return rc;
+  DivCG g = carve(ws, B, n, bc != 0);
+  const double inv_h = (double)(n - 1), inv_h2 = inv_h * inv_h;
+  const dim3 grid = div_grid(B, n), block(kDivThreads);
+  switch ((sigma != 0.0 ? 2 : 0) + (face_mean ? 1 : 0)) {
+    case 0:
+      hipLaunchKernelGGL((div_init_from_bd_kernel<false, false>), grid, block, 0, stream, f, u0, theta, g, inv_h2, 0.0,
+                         bc, bd, bd_stride, inv_h);
+      break;
+    case 1:
+      hipLaunchKernelGGL((div_init_from_bd_kernel<true, false>), grid, block, 0, stream, f, u0, theta, g, inv_h2, 0.0,
+                         bc, bd, bd_stride, inv_h);
+      break;
+    case 2:
+      hipLaunchKernelGGL((div_init_from_bd_kernel<false, true>), grid, block, 0, stream, f, u0, theta, g, inv_h2, sigma,
+                         bc, bd, bd_stride, inv_h);
+      break;
+    default:
+      hipLaunchKernelGGL((div_init_from_bd_kernel<true, true>), grid, block, 0, stream, f, u0, theta, g, inv_h2, sigma,
+                         bc, bd, bd_stride, inv_h);
+  }
+  SRPDE_LAUNCH_CHECK(name);
+  if (int rc = div_precondition(name, g, B, n, pbc, plan, stream, sigma_p)) return rc;
+  hipLaunchKernelGGL(div_rz_from_kernel, grid, block, 0, stream, g, rtol);
+  SRPDE_LAUNCH_CHECK(name);
+  return 0;
+}
+
+int srpde_div_theta_grad_bd(const double* u, const double* lam, const double* theta, double* g_out, int B, int n,
+                            int face_mean, double inv_h2, double scale, int bc, const double* bd, long long bd_stride,
+                            hipStream_t stream) {
+  const char* name = "srpde_div_theta_grad_bd";
+  SRPDE_CHECK_ARG(u && lam && theta && g_out, "%s: null pointer", name);
+  if (int rc = div_check(name, B, n, face_mean)) return rc;
+  if (int rc = div_check_bd(name, n, bc, bd, bd_stride)) return rc;
+  if (!(inv_h2 > 0.0) || !std::isfinite(inv_h2))
+    SRPDE_FAIL(kErrArg, "%s: inv_h2=%g must be positive and finite", name, inv_h2);
+  if (!std::isfinite(scale)) SRPDE_FAIL(kErrArg, "%s: scale=%g must be finite", name, scale);
+  if ((reinterpret_cast<uintptr_t>(u) | reinterpret_cast<uintptr_t>(lam) | reinterpret_cast<uintptr_t>(theta) |
+       reinterpret_cast<uintptr_t>(g_out)) & 7u)
+    SRPDE_FAIL(kErrAlign, "%s: a pointer is not 8-byte aligned", name);
+  if (g_out == u || g_out == lam || g_out == theta || g_out == bd)
+    SRPDE_FAIL(kErrArg, "%s: g_out aliases an input (a node reads its neighbours)", name);
+  if (face_mean)
+    hipLaunchKernelGGL(div_theta_grad_bd_kernel<true>, div_grid(B, n), dim3(kDivThreads), 0, stream, u, lam, theta,
+                       g_out, inv_h2, scale, n, bc, bd, bd_stride);
+  else
+    hipLaunchKernelGGL(div_theta_grad_bd_kernel<false>, div_grid(B, n), dim3(kDivThreads), 0, stream, u, lam, theta,
+                       g_out, inv_h2, scale, n, bc, bd, bd_stride);
+  SRPDE_LAUNCH_CHECK(name);
+  return 0;
+}
+
+int srpde_div_bd_grad(const double* lam, const double* theta, double* out, int B, int n, double inv_h2, int bc,
+                      hipStream_t stream) {
+  const char* name = "srpde_div_bd_grad";
+  SRPDE_CHECK_ARG(lam && theta && out, "%s: null pointer", name);
+  if (int rc = div_check(name, B, n, 0)) return rc;
+  if (int rc = div_check_bc(name, bc < 0 ? 16 : bc)) return rc;
+  if (!(inv_h2 > 0.0) || !std::isfinite(inv_h2))
+    SRPDE_FAIL(kErrArg, "%s: inv_h2=%g must be positive and finite", name, inv_h2);
+  if ((reinterpret_cast<uintptr_t>(lam) | reinterpret_cast<uintptr_t>(theta) | reinterpret_cast<uintptr_t>(out)) & 7u)
+    SRPDE_FAIL(kErrAlign, "%s: a pointer is not 8-byte aligned", name);
+  if (out == lam || out == theta) SRPDE_FAIL(kErrArg, "%s: out aliases an input", name);
+  hipLaunchKernelGGL(div_bd_grad_kernel, dim3(ceil_div(n, 256), 4, B), dim3(256), 0, stream, lam, theta, out, n, bc,
+                     inv_h2, std::sqrt(inv_h2));
+  SRPDE_LAUNCH_CHECK(name);
+  return 0;
 }
 
 int srpde_div_cg_finish(double* u, int* iters, double* resid, int B, int n, void* ws, size_t ws_bytes,

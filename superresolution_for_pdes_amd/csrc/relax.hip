@@ -40,6 +40,10 @@
 // outside node is fixed at 0 and never reads it), a face with no end inside carries 1.  DivOp<HARM, true>
 // (srpde_div_relax_bc): 0.0 instead of theta of that end when the outside end lies beyond a zero-flux side.
 //
+// srpde_div_relax_bd (relax_tile<DivOp<HARM, true>, true>): the positions straight beyond a Dirichlet side's edge nodes
+// hold the boundary value g instead of 0 (fixed, like every position outside the grid) and a node on a flux side forms
+// g = (f - ((qE + qW) + (qS + qN)) * inv_h) / inv_h2; both once per launch, the sweep is the same code.
+//
 // Every u' is a pure function of its five u values and the node's constants in a fixed order, so the result does not
 // depend on T, K or how the sweeps are split over launches: it is bit-equal to one plain pass per sweep.
 #include <cmath>
@@ -145,13 +149,16 @@ struct DivOp {
 };
 
 // grid (tiles, tiles, E); ks <= K sweeps from u_in to u_out (ks = 0: a copy); wt: 0.25 * omega (PointwiseOp) or omega;
-// bc: the side mask, read by DivOp<HARM, true> alone
-template <class Op>
-__global__ __launch_bounds__(kRelaxThreads) void relax_kernel(const double* __restrict__ u_in,
-                                                              const double* __restrict__ f,
-                                                              const double* __restrict__ theta,
-                                                              double* __restrict__ u_out, int n, double inv_h2,
-                                                              double wt, int ks, int interior_only, int bc) {
+// bc: the side mask, read by DivOp<HARM, true> alone.  The body of relax_kernel and relax_bd_kernel.
+// BD (srpde_div_relax_bd, with DivOp<HARM, true>): bd is the example's boundary data (div_stencil.h).  Staging alone
+// differs: an out-of-grid position straight beyond a Dirichlet side's edge node holds g instead of 0 -- it is fixed, so
+// it keeps g through every sweep -- and a node on a flux side forms its right-hand-side register as
+// g = (f - ((qE + qW) + (qS + qN)) * inv_h) / inv_h2.  The sweep loop is the same code.
+template <class Op, bool BD = false>
+__device__ __forceinline__ void relax_tile(const double* __restrict__ u_in, const double* __restrict__ f,
+                                           const double* __restrict__ theta, double* __restrict__ u_out, int n,
+                                           double inv_h2, double wt, int ks, int interior_only, int bc,
+                                           const double* __restrict__ bd = nullptr, double inv_h = 0.0) {
   constexpr int P = kRelaxP, K = kRelaxK, T = kRelaxT, R = kRelaxR;
   __shared__ double plane[2][P * P];
   const int x = threadIdx.x & 63, y0 = (threadIdx.x >> 6) * R;
@@ -171,8 +178,9 @@ __global__ __launch_bounds__(kRelaxThreads) void relax_kernel(const double* __re
     if (col_in && row_in) {
       const long long k = base + (long long)gy * n + gx;
       uv = u_in[k];
-      const double fv = f[k];
+      double fv = f[k];
       tv = theta[k];
+      if (BD && bd_flux_node(gy, gx, n, bc)) fv = fv - bd_flux_sum(bd, gy, gx, n, bc) * inv_h;
       gv = Op::rhs(fv, tv, inv_h2);
     }
     uc[r] = uv;
@@ -181,7 +189,20 @@ __global__ __launch_bounds__(kRelaxThreads) void relax_kernel(const double* __re
     plane[0][(y0 + r) * P + x] = uv;
     if constexpr (Op::kFaces) plane[1][(y0 + r) * P + x] = tv;
   }
+  if constexpr (BD) {
+    // the ghost values go through the plane, in a loop that is not unrolled (its row tests are scalar and would
+    // otherwise be live for all R rows at once), and come back into uc with the strip's own positions below
+#pragma unroll 1
+    for (int r = 0; r < R; ++r) {
+      const int gy = gy0 + r;
+      if (!(col_in && gy >= 0 && gy < n)) plane[0][(y0 + r) * P + x] = bd_halo(bd, gy, gx, n, bc);
+    }
+  }
   __syncthreads();
+  if constexpr (BD) {
+#pragma unroll
+    for (int r = 0; r < R; ++r) uc[r] = plane[0][(y0 + r) * P + x];
+  }
   if constexpr (Op::kFaces) {
     op.form(plane[1], x, y0, gx, gy0, n, bc);
     __syncthreads();                                   // sweep 1 writes the plane theta was staged in
@@ -219,7 +240,29 @@ __global__ __launch_bounds__(kRelaxThreads) void relax_kernel(const double* __re
   }
 }
 
+template <class Op>
+__global__ __launch_bounds__(kRelaxThreads) void relax_kernel(const double* __restrict__ u_in,
+                                                              const double* __restrict__ f,
+                                                              const double* __restrict__ theta,
+                                                              double* __restrict__ u_out, int n, double inv_h2,
+                                                              double wt, int ks, int interior_only, int bc) {
+  relax_tile<Op>(u_in, f, theta, u_out, n, inv_h2, wt, ks, interior_only, bc);
+}
+
+// bd_stride: 4 n, or 0 for one [4][n] shared by every example
+template <class Op>
+__global__ __launch_bounds__(kRelaxThreads) void relax_bd_kernel(const double* __restrict__ u_in,
+                                                                 const double* __restrict__ f,
+                                                                 const double* __restrict__ theta,
+                                                                 double* __restrict__ u_out, int n, double inv_h2,
+                                                                 double wt, int ks, int bc,
+                                                                 const double* __restrict__ bd, long long bd_stride,
+                                                                 double inv_h) {
+  relax_tile<Op, true>(u_in, f, theta, u_out, n, inv_h2, wt, ks, 0, bc, bd + (long long)blockIdx.z * bd_stride, inv_h);
+}
+
 using RelaxKernel = decltype(&relax_kernel<PointwiseOp>);
+using RelaxBdKernel = decltype(&relax_bd_kernel<DivOp<true, true>>);
 
 inline bool relax_overlap(const void* a, const void* b, size_t bytes) {
   const uintptr_t p = reinterpret_cast<uintptr_t>(a), q = reinterpret_cast<uintptr_t>(b);
@@ -233,10 +276,12 @@ size_t relax_workspace_size(int E, int n, int sweeps) {
 
 // the checks and launches of both entries; name: the entry's, kernel and wt: its relax_kernel instance and weight,
 // face_mean: the divergence entries' argument (checked in its place among the others), null for the pointwise entry;
-// bc: srpde_div_relax_bc's side mask, 0 for the other entries
+// bc: srpde_div_relax_bc's side mask, 0 for the other entries; bd_kernel (srpde_div_relax_bd): launched in place of
+// kernel, with the boundary data bd / bd_stride
 int relax_run(const char* name, RelaxKernel kernel, double wt, const int* face_mean, const double* u_in,
               const double* f, const double* theta, double* u_out, int E, int n, double inv_h2, int sweeps, double omega,
-              int interior_only, void* workspace, size_t ws_bytes, hipStream_t stream, int bc = 0) {
+              int interior_only, void* workspace, size_t ws_bytes, hipStream_t stream, int bc = 0,
+              RelaxBdKernel bd_kernel = nullptr, const double* bd = nullptr, long long bd_stride = 0) {
   SRPDE_CHECK_ARG(u_in && f && theta && u_out, "%s: null pointer", name);
   if (E <= 0 || E > 65535 || n < 1 || n > kRelaxMaxN || (interior_only && n < 3))
     SRPDE_FAIL(kErrShape, "%s: bad shape E=%d n=%d (1 <= E <= 65535, 1 <= n <= %d, interior_only needs n >= 3)", name,
@@ -250,6 +295,14 @@ int relax_run(const char* name, RelaxKernel kernel, double wt, const int* face_m
     SRPDE_FAIL(kErrArg, "%s: bc=%d with interior_only: the ring is held and no ghost face is read", name, bc);
   if (bc && n < 2)
     SRPDE_FAIL(kErrShape, "%s: bc=%d needs n >= 2 (a lone node's face coefficients can all be 0)", name, bc);
+  if (bd_kernel) {
+    if (!bd) SRPDE_FAIL(kErrArg, "%s: null boundary data", name);
+    if (reinterpret_cast<uintptr_t>(bd) & 7u) SRPDE_FAIL(kErrAlign, "%s: bd not 8-byte aligned", name);
+    if (bd_stride != 0 && bd_stride != 4LL * n)
+      SRPDE_FAIL(kErrArg, "%s: bd_stride=%lld is neither 4 n = %lld ([E][4][n]) nor 0 (one [4][n] for every example)",
+                 name, bd_stride, 4LL * n);
+    if (n < 2) SRPDE_FAIL(kErrShape, "%s: boundary data needs n >= 2 (a side has an edge node per end)", name);
+  }
   if (sweeps < 0) SRPDE_FAIL(kErrArg, "%s: sweeps=%d is negative", name, sweeps);
   if (!(omega > 0.0 && omega <= 1.0)) SRPDE_FAIL(kErrArg, "%s: omega=%g outside (0, 1]", name, omega);
   if (!(inv_h2 > 0.0) || !std::isfinite(inv_h2))
@@ -276,8 +329,12 @@ int relax_run(const char* name, RelaxKernel kernel, double wt, const int* face_m
     // the last launch writes u_out, the one before it the workspace, and so on backwards
     double* dst = ((launches - 1 - j) & 1) ? ws : u_out;
     const int ks = std::min(kRelaxK, sweeps - j * kRelaxK);
-    hipLaunchKernelGGL(kernel, dim3(tiles, tiles, E), dim3(kRelaxThreads), 0, stream, src, f, theta, dst, n, inv_h2, wt,
-                       ks, interior_only, bc);
+    if (bd_kernel)
+      hipLaunchKernelGGL(bd_kernel, dim3(tiles, tiles, E), dim3(kRelaxThreads), 0, stream, src, f, theta, dst, n, inv_h2,
+                         wt, ks, bc, bd, bd_stride, std::sqrt(inv_h2));
+    else
+      hipLaunchKernelGGL(kernel, dim3(tiles, tiles, E), dim3(kRelaxThreads), 0, stream, src, f, theta, dst, n, inv_h2,
+                         wt, ks, interior_only, bc);
     SRPDE_LAUNCH_CHECK(name);
     src = dst;
   }
@@ -319,6 +376,16 @@ int srpde_div_relax_bc(const double* u_in, const double* f, const double* theta,
   if (bc != 0) kernel = face_mean == 1 ? relax_kernel<DivOp<true, true>> : relax_kernel<DivOp<false, true>>;
   return relax_run("srpde_div_relax_bc", kernel, omega, &face_mean, u_in, f, theta, u_out, E, n, inv_h2, sweeps, omega,
                    interior_only, workspace, ws_bytes, stream, bc);
+}
+
+// srpde_div_relax_bc with boundary data: bc = 0 is four Dirichlet sides with values; no interior_only
+int srpde_div_relax_bd(const double* u_in, const double* f, const double* theta, double* u_out, int E, int n,
+                       int face_mean, int bc, double inv_h2, int sweeps, double omega, const double* bd,
+                       long long bd_stride, void* workspace, size_t ws_bytes, hipStream_t stream) {
+  return relax_run("srpde_div_relax_bd", nullptr, omega, &face_mean, u_in, f, theta, u_out, E, n, inv_h2, sweeps, omega,
+                   0, workspace, ws_bytes, stream, bc,
+                   face_mean == 1 ? relax_bd_kernel<DivOp<true, true>> : relax_bd_kernel<DivOp<false, true>>, bd,
+                   bd_stride);
 }
 
 }  // extern "C"

@@ -1296,14 +1296,35 @@ def pde_relax_sweeps_per_launch():
     return int(query("srpde_pde_relax_sweeps_per_launch"))
 
 
-def pde_relax(u, f, theta, inv_h2, sweeps, omega=0.8, interior_only=False, face_mean=None, bc=None):
+def pde_relax(u, f, theta, inv_h2, sweeps, omega=0.8, interior_only=False, face_mean=None, bc=None, bd=None):
     """``sweeps`` weighted-Jacobi sweeps on fp64 fields [E, n, n] -> a new [E, n, n] fp64 tensor (the inputs are left
     alone); over all nodes against a zero ghost ring, or with the ring of the fields held (``interior_only``).
     ``face_mean`` None: srpde_pde_relax, the sweeps of theta * A u * inv_h2 = f; 0 arithmetic / 1 harmonic:
     srpde_div_relax, the sweeps of div(theta grad u) * inv_h2 = f with that mean on the faces.  ``bc``: a side mask
     (poisson.check_bc) of that form, through srpde_div_relax_bc: zero-flux sides have no ghost face.  None / 0: the
-    entry without one.  A mask goes with neither ``interior_only`` nor n < 2."""
+    entry without one.  A mask goes with neither ``interior_only`` nor n < 2.  ``bd``: boundary data [E, 4, n] or
+    [1, 4, n] fp64 on the fields' device (poisson.bc_data), through srpde_div_relax_bd: ghost values beyond the "d"
+    sides (all four without a mask), outward fluxes through the "n" sides; the same two refusals."""
     mask = _side_mask("pde_relax", bc, face_mean)
+    if bd is not None:
+        if face_mean is None:
+            raise ValueError("pde_relax: boundary data belongs to the divergence form (face_mean 0 / 1)")
+        if interior_only:
+            raise ValueError("pde_relax: boundary data with interior_only: the ring is held and no ghost face is read")
+        _fields("pde_relax", torch.float64, u, f, theta, bd)
+        if f.dim() != 3 or f.shape[1] != f.shape[2] or u.shape != f.shape or theta.shape != f.shape or f.shape[-1] < 2:
+            raise ValueError("pde_relax: u, f and theta must share one [E, n, n] shape with n >= 2")
+        E, n, _ = f.shape
+        if bd.dim() != 3 or bd.shape[0] not in (1, E) or tuple(bd.shape[1:]) != (4, n):
+            raise ValueError(f"pde_relax: boundary data must be [E, 4, n] or [1, 4, n], got {tuple(bd.shape)}")
+        sweeps = int(sweeps)
+        out = torch.empty_like(u)
+        nbytes = int(query("srpde_div_relax_workspace_size", E, n, sweeps))
+        ws = torch.empty(nbytes // 8, dtype=torch.float64, device=f.device) if nbytes else None
+        call("srpde_div_relax_bd", u.data_ptr(), f.data_ptr(), theta.data_ptr(), out.data_ptr(), E, n, int(face_mean),
+             mask, float(inv_h2), sweeps, float(omega), bd.data_ptr(), 4 * n if bd.shape[0] == E and E > 1 else 0,
+             _p(ws), nbytes, stream_ptr())
+        return out
     if mask and interior_only:
         raise ValueError("pde_relax: bc with interior_only: the ring is held and no ghost face is read")
     if mask and f.dim() == 3 and f.shape[-1] < 2:

@@ -29,7 +29,10 @@ implicitly with it (backward Euler or Crank-Nicolson), each solve warm-started f
 all of these makes chosen sides of the grid zero-flux (insulated, du/dn = 0) instead of the zero ghost ring: a 4-string
 of "d" / "n" for (row 0, row n - 1, column 0, column n - 1), preconditioned with the separable solve of the
 constant-coefficient operator with the same sides at the same condition bound; None (default) and "dddd" are today's
-calls.
+calls.  ``bc_data=`` (``bc_data()``) gives the sides values: u = g on a "d" side (the ghost ring holds g instead of 0),
+a prescribed outward flux q = theta du/dn through an "n" side -- an affine extension A u = D u - sigma u + b(data,
+theta) with the same iteration, preconditioner and bound, a stop rule on |f - b| (so Laplace's equation, f = 0 with
+g != 0, iterates) and a gradient in the data; None (default) makes exactly today's calls.
 """
 from __future__ import annotations
 
@@ -201,6 +204,87 @@ def sep_plan(n: int, bc, device="cuda"):
     return plan
 
 
+SIDES = ("row0", "row1", "col0", "col1")   # the order of the mask's bits and of boundary data's second axis
+
+
+def bc_data(n: int, bc=None, row0=0.0, row1=0.0, col0=0.0, col1=0.0, B: int = 1, device="cuda"):
+    """Boundary data for ``bc_data=``: a [B, 4, n] fp64 tensor on ``device`` from one scalar, [n] or [B, n] per side,
+    the sides in the pattern's order (row 0, row n - 1, column 0, column n - 1).  Entry k of a row side belongs to
+    column k, entry k of a column side to row k; a corner node receives data from both of its sides.  On a "d" side of
+    ``bc`` (every side for None) the entry is the value g of the ghost node one h beyond the edge node, on an "n" side
+    the outward flux q = theta du/dn through the face half a cell beyond it.  The layout does not depend on ``bc``,
+    which is only checked.  Built with torch operations, so a side given as a tensor that requires grad receives
+    one."""
+    check_bc(bc)
+    n, B = int(n), int(B)
+    if n < 2 or B < 1:
+        raise ValueError(f"bc_data: n >= 2 and B >= 1, got n={n} B={B}")
+    rows = []
+    for name, v in zip(SIDES, (row0, row1, col0, col1)):
+        if not isinstance(v, torch.Tensor):
+            a = np.asarray(v, dtype=np.float64)
+            if not np.isfinite(a).all():
+                raise ValueError(f"bc_data: {name} is not finite")
+            v = torch.from_numpy(np.array(a))           # (ascontiguousarray would make a scalar 1-d)
+        if v.dim() > 2 or (v.dim() >= 1 and v.shape[-1] != n) or (v.dim() == 2 and v.shape[0] not in (1, B)):
+            raise ValueError(f"bc_data: {name} must be a scalar, [n] or [B, n] with n={n} B={B}, got {tuple(v.shape)}")
+        rows.append(v.to(device=device, dtype=torch.float64).expand(B, n))
+    return torch.stack(rows, dim=1).contiguous()
+
+
+def _bd_check(data, field):
+    """The refusals of ``bc_data=`` against the field it goes with ([n, n] or [B, n, n], anything with a shape), as
+    ValueErrors before anything touches a device: shape, dtype, non-finite values.  Data that already lives on a device
+    is not read back (that would be a host sync): its values are the caller's."""
+    if data is None:
+        return
+    shape = tuple(field.shape) if hasattr(field, "shape") else np.shape(field)
+    n, B = int(shape[-1]), int(shape[0]) if len(shape) == 3 else 1
+    if not isinstance(data, (torch.Tensor, np.ndarray)):
+        raise ValueError(f"bc_data must be a tensor or an array (poisson.bc_data), got {type(data).__name__}")
+    if tuple(data.shape)[-2:] != (4, n) or len(data.shape) not in (2, 3) or (len(data.shape) == 3 and
+                                                                             data.shape[0] not in (1, B)):
+        raise ValueError(f"bc_data must be [4, n], [1, 4, n] or [B, 4, n] with n={n} B={B}, got {tuple(data.shape)}")
+    if data.dtype not in (torch.float64, np.float64):
+        raise ValueError(f"bc_data must be float64, got {data.dtype}")
+    if isinstance(data, np.ndarray):
+        if not np.isfinite(data).all():
+            raise ValueError("bc_data is not finite")
+    elif data.device.type == "cpu" and not bool(torch.isfinite(data).all()):
+        raise ValueError("bc_data is not finite")
+
+
+def _bd_fields(data, field, device):
+    """``bc_data=`` as the C entries take it: a contiguous [Bd, 4, n] fp64 tensor on ``device``, Bd in (1, B), checked
+    against the prepared ``field`` [B, n, n] (``_bd_check``); None stays None."""
+    if data is None:
+        return None
+    _bd_check(data, field)
+    if isinstance(data, np.ndarray):
+        data = torch.from_numpy(np.ascontiguousarray(data))
+    data = data.to(device)
+    if data.dim() == 2:
+        data = data.unsqueeze(0)
+    return data.contiguous()
+
+
+def _bd_stride(bd, B: int) -> int:
+    """The C entries' bd_stride: 4 n doubles between problems, 0 for one [4][n] shared by all."""
+    return 4 * bd.shape[-1] if bd.shape[0] == B else 0
+
+
+def _bd_grad(lam, theta, inv_h2: float, bc, bd, scale: float = 1.0):
+    """scale * srpde_div_bd_grad(lam), summed over the batch for shared data: the gradient in ``bd``'s shape."""
+    B, n = lam.shape[0], lam.shape[-1]
+    out = torch.empty(B, 4, n, dtype=torch.float64, device=lam.device)
+    if B:
+        call("srpde_div_bd_grad", lam.data_ptr(), theta.data_ptr(), out.data_ptr(), B, n, inv_h2, bc or 0,
+             stream_ptr(lam.device))
+    if bd.shape[0] != B:
+        out = out.sum(0, keepdim=True)
+    return out if scale == 1.0 else out * scale
+
+
 class NotConverged(RuntimeError):
     """solve_div left problems above their tolerance (maxit reached)."""
 
@@ -261,11 +345,14 @@ def precond_shift_for(theta, shift: float) -> float:
     return shift / float(np.sqrt(lo * hi))
 
 
-def _apply_div(u, theta, mean: int, inv_h2: float, shift: float = 0.0, bc=None):
+def _apply_div(u, theta, mean: int, inv_h2: float, shift: float = 0.0, bc=None, bd=None):
     """srpde_div_apply (shift 0: today's call) or srpde_div_apply_shift on prepared fields (_div_fields); with a side
-    mask ``bc`` srpde_div_apply_bc."""
+    mask ``bc`` srpde_div_apply_bc; with boundary data ``bd`` (_bd_fields) srpde_div_apply_bd."""
     y = torch.empty_like(u)
-    if u.shape[0] and bc is not None:
+    if u.shape[0] and bd is not None:
+        call("srpde_div_apply_bd", u.data_ptr(), theta.data_ptr(), y.data_ptr(), u.shape[0], u.shape[-1], mean,
+             inv_h2, shift, bc or 0, bd.data_ptr(), _bd_stride(bd, u.shape[0]), stream_ptr(u.device))
+    elif u.shape[0] and bc is not None:
         call("srpde_div_apply_bc", u.data_ptr(), theta.data_ptr(), y.data_ptr(), u.shape[0], u.shape[-1], mean,
              inv_h2, shift, bc, stream_ptr(u.device))
     elif u.shape[0] and shift == 0.0:
@@ -277,10 +364,15 @@ def _apply_div(u, theta, mean: int, inv_h2: float, shift: float = 0.0, bc=None):
     return y
 
 
-def _div_theta_grad(u, lam, theta, mean: int, inv_h2: float, scale: float, bc=None):
-    """srpde_div_theta_grad on prepared fields; with a side mask ``bc`` srpde_div_theta_grad_bc."""
+def _div_theta_grad(u, lam, theta, mean: int, inv_h2: float, scale: float, bc=None, bd=None):
+    """srpde_div_theta_grad on prepared fields; with a side mask ``bc`` srpde_div_theta_grad_bc; with boundary data
+    ``bd`` (u's) srpde_div_theta_grad_bd."""
     g = torch.empty_like(u)
-    if u.shape[0] and bc is not None:
+    if u.shape[0] and bd is not None:
+        call("srpde_div_theta_grad_bd", u.data_ptr(), lam.data_ptr(), theta.data_ptr(), g.data_ptr(), u.shape[0],
+             u.shape[-1], mean, inv_h2, scale, bc or 0, bd.data_ptr(), _bd_stride(bd, u.shape[0]),
+             stream_ptr(u.device))
+    elif u.shape[0] and bc is not None:
         call("srpde_div_theta_grad_bc", u.data_ptr(), lam.data_ptr(), theta.data_ptr(), g.data_ptr(), u.shape[0],
              u.shape[-1], mean, inv_h2, scale, bc, stream_ptr(u.device))
     elif u.shape[0]:
@@ -290,7 +382,7 @@ def _div_theta_grad(u, lam, theta, mean: int, inv_h2: float, scale: float, bc=No
 
 
 def div_theta_grad(u, lam, theta, face_mean: str = "harmonic", inv_h2: float = None, scale: float = 1.0,
-                   device="cuda", bc=None):
+                   device="cuda", bc=None, bc_data=None):
     """scale * G(u, lam; theta), the pair gradient of the divergence-form operator: a new [B, n, n] fp64 device tensor
     with G_a = inv_h2 * (sum over the four faces of node a of dc_ab/dtheta_a (u_b - u_a) (lam_b - lam_a)), where
     dc/dtheta_a is 0.5 (``"arithmetic"``), 2 tb^2 / (ta + tb)^2 (``"harmonic"``) and 1 towards the ghost ring (u and
@@ -298,14 +390,17 @@ def div_theta_grad(u, lam, theta, face_mean: str = "harmonic", inv_h2: float = N
     solve_div +G(u, lam) with lam the adjoint solve.  u, lam [n, n] or [B, n, n]; theta is broadcast; ``inv_h2``
     defaults to (n - 1)^2.  One launch, stream-ordered, no host sync, not itself differentiable
     (srpde_div_theta_grad; include/srpde.h states the rounding order).  ``bc`` (``check_bc``): dc/dtheta_a is 0
-    towards a zero-flux side (srpde_div_theta_grad_bc)."""
+    towards a zero-flux side (srpde_div_theta_grad_bc).  ``bc_data``: the boundary data of ``u`` -- beyond a "d" side u
+    is g, lam stays 0 -- so that d<lam, A u>/dtheta = -G still (srpde_div_theta_grad_bd); fluxes do not enter."""
     mean = check_face_mean(face_mean)
     bc = check_bc(bc)
+    _bd_check(bc_data, u)
     with torch.no_grad():
         u, theta, B, n = _div_fields(u, theta, device)
+        bd = _bd_fields(bc_data, u, u.device)
         lam = _dev_f64(lam, device).reshape(u.shape)
         return _div_theta_grad(u, lam, theta, mean, float((n - 1) ** 2 if inv_h2 is None else inv_h2), float(scale),
-                               bc)
+                               bc, bd)
 
 
 class _ApplyDiv(torch.autograd.Function):
@@ -313,20 +408,26 @@ class _ApplyDiv(torch.autograd.Function):
     depend on theta, so grad_theta = -G(u, grad_y; theta) as without it."""
 
     @staticmethod
-    def forward(ctx, u, theta, mean, inv_h2, shift=0.0, bc=None):
+    def forward(ctx, u, theta, mean, inv_h2, shift=0.0, bc=None, bd=None):
         u, theta = u.detach().contiguous(), theta.detach().contiguous()
-        ctx.save_for_backward(u, theta)
+        bd = None if bd is None else bd.detach()
+        ctx.save_for_backward(u, theta, bd)
         ctx.mean, ctx.inv_h2, ctx.shift, ctx.bc = mean, inv_h2, shift, bc
-        return _apply_div(u, theta, mean, inv_h2, shift, bc)
+        return _apply_div(u, theta, mean, inv_h2, shift, bc, bd)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gy):
-        u, theta = ctx.saved_tensors
+        # with boundary data y = (D - shift) u + b(bd, theta): the gradient in u is the homogeneous operator's, the
+        # one in theta sees g through u's halo, the one in bd is srpde_div_bd_grad of grad_y
+        u, theta, bd = ctx.saved_tensors
         gy = gy.contiguous()
         gu = _apply_div(gy, theta, ctx.mean, ctx.inv_h2, ctx.shift, ctx.bc) if ctx.needs_input_grad[0] else None
-        gth = _div_theta_grad(u, gy, theta, ctx.mean, ctx.inv_h2, -1.0, ctx.bc) if ctx.needs_input_grad[1] else None
-        return gu, gth, None, None, None, None
+        gth = None
+        if ctx.needs_input_grad[1]:
+            gth = _div_theta_grad(u, gy, theta, ctx.mean, ctx.inv_h2, -1.0, ctx.bc, bd)
+        gbd = _bd_grad(gy, theta, ctx.inv_h2, ctx.bc, bd) if bd is not None and ctx.needs_input_grad[6] else None
+        return gu, gth, None, None, None, None, gbd
 
 
 class _SolveDiv(torch.autograd.Function):
@@ -335,10 +436,11 @@ class _SolveDiv(torch.autograd.Function):
     grad_theta = +G(u, lam; theta), the shift not depending on theta.  Nothing depends on u0."""
 
     @staticmethod
-    def forward(ctx, f, theta, u0, mean, rtol, maxit, check_every, check, shift=0.0, pshift=0.0, bc=None):
+    def forward(ctx, f, theta, u0, mean, rtol, maxit, check_every, check, shift=0.0, pshift=0.0, bc=None, bd=None):
         f, theta = f.detach().contiguous(), theta.detach().contiguous()
-        u, iters, resid = _solve_div(f, theta, u0, mean, rtol, maxit, check_every, check, shift, pshift, bc=bc)
-        ctx.save_for_backward(u, theta)
+        bd = None if bd is None else bd.detach()
+        u, iters, resid = _solve_div(f, theta, u0, mean, rtol, maxit, check_every, check, shift, pshift, bc=bc, bd=bd)
+        ctx.save_for_backward(u, theta, bd)
         ctx.args, ctx.bc = (mean, rtol, maxit, check_every, check, shift, pshift), bc
         ctx.mark_non_differentiable(iters, resid)
         return u, iters, resid
@@ -346,17 +448,22 @@ class _SolveDiv(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gu, _giters, _gresid):
-        u, theta = ctx.saved_tensors
+        # with boundary data u = (D - shift)^-1 (f - b(bd, theta)): the adjoint solve stays homogeneous, the theta
+        # gradient sees g through u's halo, and grad_bd = -srpde_div_bd_grad(lam)
+        u, theta, bd = ctx.saved_tensors
         mean = ctx.args[0]
         lam = _solve_div(gu.contiguous(), theta, None, *ctx.args, bc=ctx.bc)[0]     # NotConverged propagates
+        inv_h2 = float((u.shape[-1] - 1) ** 2)
         gth = None
         if ctx.needs_input_grad[1]:
-            gth = _div_theta_grad(u, lam, theta, mean, float((u.shape[-1] - 1) ** 2), 1.0, ctx.bc)
-        return (lam if ctx.needs_input_grad[0] else None), gth, None, None, None, None, None, None, None, None, None
+            gth = _div_theta_grad(u, lam, theta, mean, inv_h2, 1.0, ctx.bc, bd)
+        gbd = _bd_grad(lam, theta, inv_h2, ctx.bc, bd, -1.0) if bd is not None and ctx.needs_input_grad[11] else None
+        return ((lam if ctx.needs_input_grad[0] else None), gth, None, None, None, None, None, None, None, None, None,
+                gbd)
 
 
 def apply_div(u, theta, face_mean: str = "harmonic", inv_h2: float = None, device="cuda", shift: float = 0.0,
-              bc=None):
+              bc=None, bc_data=None):
     """y = div(theta grad u) on the project's grid (zero ghost ring, h = 1 / (n - 1)): a new [B, n, n] fp64 device
     tensor.  The face coefficient between nodes a and b is 0.5 (ta + tb) (``"arithmetic"``) or 2 ta tb / (ta + tb)
     (``"harmonic"``), theta_a towards the ghost ring; ``inv_h2`` defaults to (n - 1)^2.  One launch, stream-ordered,
@@ -371,20 +478,29 @@ def apply_div(u, theta, face_mean: str = "harmonic", inv_h2: float = None, devic
 
     ``bc`` (``check_bc``, e.g. ``"ddnn"``): an "n" side is zero-flux -- its ghost faces have coefficient 0 instead of
     theta_a -- in the same launch (srpde_div_apply_bc); both gradients carry the pattern.  None (default) and
-    ``"dddd"`` are exactly today's calls."""
+    ``"dddd"`` are exactly today's calls.
+
+    ``bc_data`` (``bc_data()``; [4, n], [1, 4, n] shared by the batch, or [B, 4, n], fp64): the sides carry values, in
+    the same launch (srpde_div_apply_bd): beyond a "d" side of ``bc`` (all four for ``bc=None``) the ghost node holds
+    g instead of 0, through an "n" side flows the outward flux q, which adds q * sqrt(inv_h2) to the edge node:
+    y = D u - sigma u + b(data, theta).  The gradient in u is the homogeneous operator's, the one in theta sees g, and
+    the data gets one (srpde_div_bd_grad; summed over the batch when shared).  Wrong shape or dtype and, for data on
+    the host, non-finite values are ValueErrors.  None (default) is exactly today's call."""
     mean = check_face_mean(face_mean)
     shift = check_shift(shift)
     bc = check_bc(bc)
+    _bd_check(bc_data, u)
     u, theta, B, n = _div_fields(u, theta, device)
+    bd = _bd_fields(bc_data, u, u.device)
     inv_h2 = float((n - 1) ** 2 if inv_h2 is None else inv_h2)
-    if _wants_grad(u, theta):
-        return _ApplyDiv.apply(u, theta, mean, inv_h2, shift, bc)
-    return _apply_div(u, theta, mean, inv_h2, shift, bc)
+    if _wants_grad(u, theta, *(() if bd is None else (bd,))):
+        return _ApplyDiv.apply(u, theta, mean, inv_h2, shift, bc, bd)
+    return _apply_div(u, theta, mean, inv_h2, shift, bc, bd)
 
 
 def solve_div(f, theta, face_mean: str = "harmonic", rtol: float = DEFAULT_RTOL, maxit: int = None,
               check_every: int = 8, check: bool = True, return_info: bool = False, device="cuda", u0=None,
-              shift: float = 0.0, precond_shift: float = None, bc=None):
+              shift: float = 0.0, precond_shift: float = None, bc=None, bc_data=None):
     """u[B, n, n] (float64, on device) with div(theta grad u) = f per problem, by CG preconditioned with the
     sine-transform solve of the constant-coefficient operator (srpde_div_cg_*).  Convergence, |r| <= rtol |f|, is
     decided per problem on the device, and a converged problem is frozen, so a problem's u / iters / resid are the
@@ -420,7 +536,15 @@ def solve_div(f, theta, face_mean: str = "harmonic", rtol: float = DEFAULT_RTOL,
     every n), so the bound theta_max / theta_min and ``pcg_iterations`` hold for every pattern.  ``"nnnn"`` is singular
     without a shift and refused (ValueError); with one it is the insulated box.  u0, shift, precond_shift, both modes,
     capture (once ``sep_plan(n, bc)`` exists) and the gradients work as without.  None (default) and ``"dddd"`` make
-    exactly today's calls."""
+    exactly today's calls.
+
+    ``bc_data`` (as for ``apply_div``): u = g on the "d" sides, the outward flux q through the "n" sides; the problem
+    solved is (D - sigma) u = f - b(data, theta), started by srpde_div_cg_init_from_bd (also without ``u0``) and
+    iterated by today's entries: the iteration, the preconditioner (the sine plan for four "d" sides, the separable
+    one otherwise) and the bound are the homogeneous ones.  The stop rule is |r| <= rtol |f - b| and ``resid`` is
+    |r| / |f - b|: Laplace's equation, f = 0 with g != 0, has |f| = 0 but is not solved by u = 0.  The data gets a
+    gradient, minus srpde_div_bd_grad of the (homogeneous) adjoint solution.  ``"nnnn"`` without a shift stays
+    refused; whether its fluxes balance the forcing is the caller's business.  None (default) makes today's calls."""
     mean = check_face_mean(face_mean)
     shift = check_shift(shift)
     bc = check_bc(bc)
@@ -435,7 +559,9 @@ def solve_div(f, theta, face_mean: str = "harmonic", rtol: float = DEFAULT_RTOL,
     elif shift != 0.0 and (int(check_every) == 0 or torch.cuda.is_current_stream_capturing()):
         raise ValueError("solve_div: precond_shift=None reads theta's range back (a host sync): give precond_shift "
                          "in fixed-iteration mode (check_every=0) and under stream capture")
+    _bd_check(bc_data, f)
     f, theta, B, n = _div_fields(f, theta, device)
+    bd = _bd_fields(bc_data, f, f.device)
     if u0 is not None:
         u0 = _dev_f64(u0, device).detach()
         if u0.dim() == 2:
@@ -452,18 +578,20 @@ def solve_div(f, theta, face_mean: str = "harmonic", rtol: float = DEFAULT_RTOL,
         pshift = 0.0
     else:
         pshift = precond_shift_for(theta, shift) if precond_shift is None else precond_shift
-    if _wants_grad(f, theta):
-        out = _SolveDiv.apply(f, theta, u0, mean, float(rtol), maxit, check_every, bool(check), shift, pshift, bc)
+    if _wants_grad(f, theta, *(() if bd is None else (bd,))):
+        out = _SolveDiv.apply(f, theta, u0, mean, float(rtol), maxit, check_every, bool(check), shift, pshift, bc, bd)
     else:
-        out = _solve_div(f, theta, u0, mean, float(rtol), maxit, check_every, bool(check), shift, pshift, bc=bc)
+        out = _solve_div(f, theta, u0, mean, float(rtol), maxit, check_every, bool(check), shift, pshift, bc=bc,
+                         bd=bd)
     return out if return_info else out[0]
 
 
 def _solve_div(f, theta, u0, mean: int, rtol: float, maxit: int, check_every: int, check: bool, shift: float = 0.0,
-               pshift: float = 0.0, ws=None, out=None, bc=None):
+               pshift: float = 0.0, ws=None, out=None, bc=None, bd=None):
     """The srpde_div_cg_* call sequence on prepared fields -> (u, iters, resid); shift 0 is the unshifted entries'
     sequence, call for call; a side mask ``bc`` the *_bc entries' with the separable plan.  ``ws`` / ``out`` = (u,
-    iters, resid): the caller's buffers (diffuse reuses them)."""
+    iters, resid): the caller's buffers (diffuse reuses them).  Boundary data ``bd``: srpde_div_cg_init_from_bd starts
+    (u0 or not), on the plan and workspace that ``bc`` selects, and the same iterate / finish calls follow."""
     B, n = f.shape[0], f.shape[-1]
     if out is None:
         u = torch.empty_like(f)
@@ -481,7 +609,11 @@ def _solve_div(f, theta, u0, mean: int, rtol: float, maxit: int, check_every: in
     if ws is None:
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=f.device)
     sp = stream_ptr(f.device)
-    if bc is not None:
+    if bd is not None:
+        call("srpde_div_cg_init_from_bd", f.data_ptr(), 0 if u0 is None else u0.data_ptr(), theta.data_ptr(), B, n,
+             mean, bc or 0, shift, pshift, rtol, bd.data_ptr(), _bd_stride(bd, B), plan.data_ptr(), plan.numel(),
+             ws.data_ptr(), ws_bytes, sp)
+    elif bc is not None:
         if u0 is None:
             call("srpde_div_cg_init_bc", f.data_ptr(), B, n, bc, pshift, plan.data_ptr(), plan.numel(), ws.data_ptr(),
                  ws_bytes, sp)
@@ -503,7 +635,7 @@ def _solve_div(f, theta, u0, mean: int, rtol: float, maxit: int, check_every: in
     done_at = int(query("srpde_div_cg_done_offset", B, n))
     done = ws[done_at:done_at + 4 * B].view(torch.int32)
     k = 0
-    if u0 is not None and check_every and bool(done.all()):   # a u0 that already satisfies rtol: no chunk at all
+    if (u0 is not None or bd is not None) and check_every and bool(done.all()):   # rtol already met: no chunk at all
         k = maxit
     while k < maxit:
         count = min(check_every, maxit - k) if check_every else maxit
@@ -534,7 +666,7 @@ SCHEMES = ("be", "cn")
 
 def diffuse(u0, theta, f=None, dt: float = None, steps: int = 1, scheme: str = "be", face_mean: str = "harmonic",
             rtol: float = DEFAULT_RTOL, maxit: int = None, pcg_iters: int = None, precond_shift: float = None,
-            save_every: int = None, check: bool = False, check_every: int = 8, device="cuda", bc=None):
+            save_every: int = None, check: bool = False, check_every: int = 8, device="cuda", bc=None, bc_data=None):
     """``steps`` implicit time steps of u_t = div(theta grad u) - f from u0, the forcing constant in time (None: 0),
     on the project's grid (zero ghost ring).  Each step solves (D_theta - sigma I) u+ = rhs by the shifted
     sine-preconditioned CG, warm-started from the current state:
@@ -560,8 +692,14 @@ def diffuse(u0, theta, f=None, dt: float = None, steps: int = 1, scheme: str = "
     ``bc`` (``check_bc``, e.g. ``"nnnn"``, the insulated box: with f = None the sum of u is conserved up to the solves'
     tolerance): "n" sides are zero-flux in the operator, in Crank-Nicolson's right-hand side (srpde_div_step_rhs_bc)
     and in every solve (``solve_div(bc=)``); capture needs ``sep_plan(n, bc)`` first.  None (default) and ``"dddd"``
-    make exactly today's calls."""
+    make exactly today's calls.
+
+    ``bc_data`` (as for ``apply_div``), constant in time: u_t = D u + b(data, theta) - f.  Crank-Nicolson's right-hand
+    side carries the data (srpde_div_step_rhs_bd: 2 f - sigma u - (D u + b)), backward Euler's does not change, and
+    every solve is ``solve_div(bc_data=)``'s; differentiable in the data by the same composition.  None (default)
+    makes today's calls."""
     pattern, bc = bc, check_bc(bc)
+    _bd_check(bc_data, u0)
     if scheme not in SCHEMES:
         raise ValueError(f"unknown time scheme {scheme!r}: one of {SCHEMES}")
     mean = check_face_mean(face_mean)
@@ -585,6 +723,7 @@ def diffuse(u0, theta, f=None, dt: float = None, steps: int = 1, scheme: str = "
         raise ValueError("diffuse: precond_shift=None reads theta's range back (a host sync): give precond_shift "
                          "in fixed mode (pcg_iters) and under stream capture")
     u, theta, B, n = _div_fields(u0, theta, device)
+    bd = _bd_fields(bc_data, u, u.device)
     if f is not None:
         f = _dev_f64(f, device)
         if f.dim() == 2:
@@ -601,14 +740,14 @@ def diffuse(u0, theta, f=None, dt: float = None, steps: int = 1, scheme: str = "
     frames = []
     counts = torch.zeros(steps, B, dtype=torch.int32, device=u.device)
 
-    if _wants_grad(u, theta, *(() if f is None else (f,))):
+    if _wants_grad(u, theta, *(() if f is None else (f,)), *(() if bd is None else (bd,))):
         for s in range(steps):
             rhs = -sigma * u if f is None else (2.0 * f if cn else f) - sigma * u
             if cn:
-                rhs = rhs - apply_div(u, theta, face_mean, device=device, bc=pattern)
+                rhs = rhs - apply_div(u, theta, face_mean, device=device, bc=pattern, bc_data=bd)
             u, it, _ = solve_div(rhs, theta, face_mean=face_mean, rtol=rtol, maxit=it_max, check_every=chunk,
                                  check=not fixed, return_info=True, device=device, u0=u.detach(), shift=sigma,
-                                 precond_shift=pshift, bc=pattern)
+                                 precond_shift=pshift, bc=pattern, bc_data=bd)
             counts[s] = it
             if save_every and (s + 1) % int(save_every) == 0:
                 frames.append(u)
@@ -622,7 +761,10 @@ def diffuse(u0, theta, f=None, dt: float = None, steps: int = 1, scheme: str = "
             resid = torch.empty(B, dtype=torch.float64, device=u.device)
             fp = 0 if f is None else f.data_ptr()
         for s in range(steps if B else 0):
-            if bc is None:
+            if bd is not None:
+                call("srpde_div_step_rhs_bd", u.data_ptr(), fp, theta.data_ptr(), rhs.data_ptr(), B, n, mean, sigma,
+                     cn, bc or 0, bd.data_ptr(), _bd_stride(bd, B), stream_ptr(u.device))
+            elif bc is None:
                 call("srpde_div_step_rhs", u.data_ptr(), fp, theta.data_ptr(), rhs.data_ptr(), B, n, mean, sigma, cn,
                      stream_ptr(u.device))
             else:
@@ -630,7 +772,7 @@ def diffuse(u0, theta, f=None, dt: float = None, steps: int = 1, scheme: str = "
                      cn, bc, stream_ptr(u.device))
             # init_from copies the state into the workspace before finish overwrites it with the new one
             _solve_div(rhs, theta, u, mean, float(rtol), it_max, chunk, not fixed, sigma, pshift, ws=ws,
-                       out=(u, counts[s], resid), bc=bc)
+                       out=(u, counts[s], resid), bc=bc, bd=bd)
             if save_every and (s + 1) % int(save_every) == 0:
                 frames.append(u.clone())
     out = (u,)
@@ -642,7 +784,7 @@ def diffuse(u0, theta, f=None, dt: float = None, steps: int = 1, scheme: str = "
 
 
 def residual_metrics(u, f, theta, interior_only: bool = False, inv_h2: float = None, device="cuda",
-                     form: str = "pointwise", face_mean: str = "harmonic", bc=None):
+                     form: str = "pointwise", face_mean: str = "harmonic", bc=None, bc_data=None):
     """How well raw fields satisfy the discrete equation: [E, 2] fp64 device tensor of (RMS, max abs) of
     theta * A u / h^2 - f per example (A the 5-point stencil with a zero ghost ring).  u [E, n, n] fp32 or fp64
     (a tensor keeps its precision), f and theta fp64.  ``inv_h2`` defaults to (n - 1)^2, the whole-domain operator
@@ -650,11 +792,20 @@ def residual_metrics(u, f, theta, interior_only: bool = False, inv_h2: float = N
     larger solve, whose ring is not zero).  Stream-ordered, no host sync (srpde_pde_residual_metrics).
     ``form="divergence"``: (RMS, max abs) of div(theta grad u) - f with ``face_mean`` instead, through apply_div, in
     fp64 whatever u's precision -- and, through apply_div, differentiable in u, f and theta when one of them requires
-    grad (the pointwise metric is not); ``bc`` is apply_div's side pattern and belongs to that form."""
+    grad (the pointwise metric is not); ``bc`` is apply_div's side pattern and belongs to that form, and so does
+    ``bc_data``, apply_div's boundary data (the residual of A u = f with values on the sides); with ``interior_only``
+    the data is refused: the ring is left out and no ghost face counts."""
+    if bc_data is not None and check_form(form) != "divergence":
+        raise ValueError('bc_data belongs to form="divergence" (apply_div): the pointwise operator has the zero ghost '
+                         "ring")
+    if bc_data is not None and interior_only:
+        raise ValueError("residual_metrics: bc_data with interior_only: the ring is left out and no ghost face counts")
     if check_form(form) == "divergence":
+        check_bc(bc)
+        _bd_check(bc_data, f)
         f, theta, E, n = _div_fields(f, theta, device)
         u = _dev_f64(u, device).reshape(f.shape)
-        res = apply_div(u, theta, face_mean, inv_h2, device, bc=bc) - f
+        res = apply_div(u, theta, face_mean, inv_h2, device, bc=bc, bc_data=bc_data) - f
         if interior_only:
             res = res[:, 1:-1, 1:-1]
         res = res.reshape(E, -1)
@@ -676,7 +827,7 @@ def residual_metrics(u, f, theta, interior_only: bool = False, inv_h2: float = N
 
 
 def relax(u, f, theta, sweeps: int, omega: float = 0.8, interior_only: bool = False, inv_h2: float = None,
-          device="cuda", form: str = "pointwise", face_mean: str = "harmonic", bc=None):
+          device="cuda", form: str = "pointwise", face_mean: str = "harmonic", bc=None, bc_data=None):
     """``sweeps`` weighted-Jacobi sweeps of theta * A u / h^2 = f (A the 5-point stencil with a zero ghost ring):
     u <- u + (omega / 4) (A u - h^2 f / theta), each from the previous sweep's u.  It damps the error at the grid
     scale (for omega = 0.8 every component with a wavenumber >= pi / 2 shrinks by at least 0.6 per sweep) and, for
@@ -691,10 +842,20 @@ def relax(u, f, theta, sweeps: int, omega: float = 0.8, interior_only: bool = Fa
     ``bc`` (``check_bc``, e.g. ``"ddnn"``), with that form: an "n" side is zero-flux -- its ghost faces have coefficient
     0, in the sum that divides as well (srpde_div_relax_bc) -- so a solve_div(bc=) solution is a fixed point of its own
     smoother.  ``"nnnn"`` is allowed (a sweep inverts nothing); ``interior_only`` and n < 2 are refused with a pattern.
-    None (default) and ``"dddd"`` make today's call."""
+    None (default) and ``"dddd"`` make today's call.
+    ``bc_data`` (as for ``apply_div``), with that form: the sweeps of A u = f with values on the sides
+    (srpde_div_relax_bd): the ghost nodes beyond "d" sides are held at g, a node on an "n" side sweeps with
+    f - q * sqrt(inv_h2) in place of f, so a ``solve_div(bc_data=)`` solution is a fixed point -- a crop of a larger
+    solution can be smoothed on its own with the ring around it as g.  Refused with ``interior_only`` and n < 2."""
     from . import hipops as H
     mean = face_mean_arg(form, face_mean)
     bc = check_bc(bc)
+    if bc_data is not None:
+        if mean is None:
+            raise ValueError('bc_data belongs to form="divergence": the pointwise operator has the zero ghost ring')
+        if interior_only:
+            raise ValueError("relax: bc_data with interior_only: the ring is held and no ghost face is read")
+        _bd_check(bc_data, u)
     if bc is not None:
         if mean is None:
             raise ValueError('bc belongs to form="divergence": the pointwise operator has the zero ghost ring')
@@ -713,6 +874,9 @@ def relax(u, f, theta, sweeps: int, omega: float = 0.8, interior_only: bool = Fa
         theta = theta.expand_as(f).contiguous()
     n = u.shape[-1]
     inv_h2 = float((n - 1) ** 2 if inv_h2 is None else inv_h2)
+    if bc_data is not None:
+        bd = _bd_fields(bc_data, u, u.device).detach()
+        return H.pde_relax(u, f, theta, inv_h2, int(sweeps), float(omega), False, mean, bc, bd)
     return H.pde_relax(u, f, theta, inv_h2, int(sweeps), float(omega), interior_only, mean, bc)
 
 

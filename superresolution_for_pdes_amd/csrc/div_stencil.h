@@ -20,22 +20,10 @@ __device__ __forceinline__ T face_mean(T ta, T tb) {
 }
 
 // (cE (vE - v) + cW (vW - v)) + (cS (vS - v) + cN (vN - v)) on halo tiles around v and th (E is +1, S is +pitch);
-// has_*: that neighbour is a node of the grid
-template <bool HARM, typename T>
-__device__ __forceinline__ T face_sum(const T* v, const T* th, int pitch, bool has_w, bool has_e, bool has_n,
-                                      bool has_s) {
-  const T ta = th[0], vc = v[0];
-  const T cE = has_e ? face_mean<HARM>(ta, th[1]) : ta;
-  const T cW = has_w ? face_mean<HARM>(ta, th[-1]) : ta;
-  const T cS = has_s ? face_mean<HARM>(ta, th[pitch]) : ta;
-  const T cN = has_n ? face_mean<HARM>(ta, th[-pitch]) : ta;
-  return (cE * (v[1] - vc) + cW * (v[-1] - vc)) + (cS * (v[pitch] - vc) + cN * (v[-pitch] - vc));
-}
-
-// face_sum with a boundary pattern: ghost_*: the ghost face on that side of the GRID exists (a Dirichlet side; a
-// zero-flux side has none).  A missing ghost face has coefficient 0 where face_sum has ta, every other operation and
-// its place are face_sum's: four Dirichlet sides give face_sum's bits.  The halo holds 0 outside the grid, so a
-// missing face's term is 0 * (0 - v) = -+0, which changes no sum but an all-zero one's sign.
+// has_*: that neighbour is a node of the grid; ghost_*: the ghost face on that side of the GRID exists (a Dirichlet
+// side; a zero-flux side has none).  A face to a missing neighbour has coefficient ta where its ghost face exists and 0
+// where it does not, in the same place of the same sum.  The halo holds 0 outside the grid, so a missing face's term
+// is 0 * (0 - v) = -+0, which changes no sum but an all-zero one's sign.
 template <bool HARM, typename T>
 __device__ __forceinline__ T face_sum_bc(const T* v, const T* th, int pitch, bool has_w, bool has_e, bool has_n,
                                          bool has_s, bool ghost_w, bool ghost_e, bool ghost_n, bool ghost_s) {
@@ -47,6 +35,13 @@ __device__ __forceinline__ T face_sum_bc(const T* v, const T* th, int pitch, boo
   return (cE * (v[1] - vc) + cW * (v[-1] - vc)) + (cS * (v[pitch] - vc) + cN * (v[-pitch] - vc));
 }
 
+// the zero ghost ring: all four ghost faces exist
+template <bool HARM, typename T>
+__device__ __forceinline__ T face_sum(const T* v, const T* th, int pitch, bool has_w, bool has_e, bool has_n,
+                                      bool has_s) {
+  return face_sum_bc<HARM>(v, th, pitch, has_w, has_e, has_n, has_s, true, true, true, true);
+}
+
 // d face_mean(ta, tb) / d ta: 0.5, or 2 tb^2 / (ta + tb)^2 (towards the ghost ring c = ta and the derivative is 1)
 template <bool HARM, typename T>
 __device__ __forceinline__ T face_mean_da(T ta, T tb) {
@@ -54,22 +49,9 @@ __device__ __forceinline__ T face_mean_da(T ta, T tb) {
 }
 
 // The pair gradient of the operator in theta_a, sum over the node's faces of dc/dta (vb - va) (wb - wa), as
-// (gE + gW) + (gS + gN) with a face term g = (d * (vb - va)) * (wb - wa); tiles and has_* as for face_sum.  The halo
-// holds 0 for v and w outside the grid, so a ghost face gives (1 * (0 - va)) * (0 - wa) = va * wa exactly.
-template <bool HARM, typename T>
-__device__ __forceinline__ T face_grad_sum(const T* v, const T* w, const T* th, int pitch, bool has_w, bool has_e,
-                                           bool has_n, bool has_s) {
-  const T ta = th[0], vc = v[0], wc = w[0];
-  const T dE = has_e ? face_mean_da<HARM>(ta, th[1]) : T(1);
-  const T dW = has_w ? face_mean_da<HARM>(ta, th[-1]) : T(1);
-  const T dS = has_s ? face_mean_da<HARM>(ta, th[pitch]) : T(1);
-  const T dN = has_n ? face_mean_da<HARM>(ta, th[-pitch]) : T(1);
-  return ((dE * (v[1] - vc)) * (w[1] - wc) + (dW * (v[-1] - vc)) * (w[-1] - wc)) +
-         ((dS * (v[pitch] - vc)) * (w[pitch] - wc) + (dN * (v[-pitch] - vc)) * (w[-pitch] - wc));
-}
-
-// face_grad_sum with a boundary pattern (ghost_* as for face_sum_bc): a missing ghost face has derivative 0 where
-// face_grad_sum has 1, every other operation and its place are face_grad_sum's.
+// (gE + gW) + (gS + gN) with a face term g = (d * (vb - va)) * (wb - wa); tiles, has_* and ghost_* as for face_sum_bc:
+// towards a missing neighbour the derivative is 1 where the ghost face exists and 0 where it does not.  The halo holds
+// 0 for v and w outside the grid, so a ghost face gives (1 * (0 - va)) * (0 - wa) = va * wa exactly.
 template <bool HARM, typename T>
 __device__ __forceinline__ T face_grad_sum_bc(const T* v, const T* w, const T* th, int pitch, bool has_w, bool has_e,
                                               bool has_n, bool has_s, bool ghost_w, bool ghost_e, bool ghost_n,
@@ -81,6 +63,13 @@ __device__ __forceinline__ T face_grad_sum_bc(const T* v, const T* w, const T* t
   const T dN = has_n ? face_mean_da<HARM>(ta, th[-pitch]) : (ghost_n ? T(1) : T(0));
   return ((dE * (v[1] - vc)) * (w[1] - wc) + (dW * (v[-1] - vc)) * (w[-1] - wc)) +
          ((dS * (v[pitch] - vc)) * (w[pitch] - wc) + (dN * (v[-pitch] - vc)) * (w[-pitch] - wc));
+}
+
+// the zero ghost ring: all four ghost faces exist
+template <bool HARM, typename T>
+__device__ __forceinline__ T face_grad_sum(const T* v, const T* w, const T* th, int pitch, bool has_w, bool has_e,
+                                           bool has_n, bool has_s) {
+  return face_grad_sum_bc<HARM>(v, w, th, pitch, has_w, has_e, has_n, has_s, true, true, true, true);
 }
 
 // ---- Boundary data (the *_bd entries).  bd is one problem's [4][n] doubles, the sides in the mask's order: row 0,

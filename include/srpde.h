@@ -86,7 +86,9 @@ typedef struct ihipStream_t* hipStream_t;
  *      extended, the number kept (entries were added, none changed: a binding built against the earlier 23 header
  *      reads every argument as before): boundary values and prescribed fluxes for the divergence-form operator,
  *      srpde_div_apply_bd, srpde_div_step_rhs_bd, srpde_div_cg_init_from_bd, srpde_div_theta_grad_bd,
- *      srpde_div_bd_grad, srpde_div_relax_bd */
+ *      srpde_div_bd_grad, srpde_div_relax_bd
+ *      extended again, in the same way: the face fluxes of the divergence-form operator and their wall totals,
+ *      srpde_div_face_flux, srpde_div_face_flux_grad, srpde_div_wall_flux, srpde_div_wall_flux_grad */
 #define SRPDE_ABI_VERSION 23
 
 /* Kernel-family bits (per call; bit 0 of the same argument is the accumulate flag): the forward / dgrad
@@ -1026,6 +1028,61 @@ int srpde_div_bd_grad(const double* lam, const double* theta, double* out, int B
 int srpde_div_relax_bd(const double* u_in, const double* f, const double* theta, double* u_out, int E, int n,
                        int face_mean, int bc, double inv_h2, int sweeps, double omega, const double* bd,
                        long long bd_stride, void* workspace, size_t ws_bytes, hipStream_t stream);
+
+/* ---- Face fluxes and wall totals of the divergence-form operator (ABI 23, extended).  The grid, face_mean, the side
+ *      mask bc (0 .. 15) and bd / bd_stride are those of the *_bd entries, except that bd may be NULL here: g = 0 beyond
+ *      every Dirichlet side and q = 0 through every flux side.  inv_h = sqrt(inv_h2) and h = 1 / inv_h are formed once
+ *      on the host.  Nothing is refused for bc = 15: no solve is involved.
+ *      The fields are theta du/dx and theta du/dy on the faces, fp64:
+ *          Fx [B][n][n + 1]: entry (i, j) is the face between nodes (i, j - 1) and (i, j); j = 0 and j = n are the wall
+ *                            faces of column 0 and column n - 1.
+ *          Fy [B][n + 1][n]: entry (i, j) is the face between nodes (i - 1, j) and (i, j); i = 0 and i = n are the wall
+ *                            faces of row 0 and row n - 1.
+ *      Every operation is rounded once in the order written (no contraction):
+ *          a face between two nodes:       F = (c * (u_hi - u_lo)) * inv_h,  c = face_mean(theta_lo, theta_hi) as above;
+ *          a wall face, Dirichlet side:    c = theta_a of the edge node a and the ghost value is g:
+ *                                          low wall (theta_a * (u_a - g)) * inv_h, high wall (theta_a * (g - u_a)) * inv_h;
+ *          a wall face, flux side:         low wall -q, high wall +q, copied (q is the OUTWARD flux theta du/dn, and the
+ *                                          low walls' outward normal is -x / -y).
+ *      In exact arithmetic ((Fx[i][j+1] - Fx[i][j]) + (Fy[i+1][j] - Fy[i][j])) * inv_h is srpde_div_apply_bd at sigma = 0.
+ *      The wall totals are W [B][4], the sides in the mask's order: W_s = h * (the sum over the side's n wall faces of
+ *      the outward flux -Fy[0][k], +Fy[n][k], -Fx[k][0], +Fx[k][n]), the integral of theta du/dn over the wall.  A
+ *      Dirichlet side's term is (theta_a * (g - u_a)) * inv_h -- the bits of the face flux, its sign turned on a low
+ *      wall -- and a flux side's is q.  The sum is in fp64 in one fixed order that depends on n alone: thread t of 256
+ *      adds entries t, t + 256, ... in turn, then the 64 lanes of a wave by the xor butterfly and the four waves as
+ *      (0 + 1) + (2 + 3); then one product with h.  So W of a problem does not depend on B or on its place in the
+ *      batch, and sum_s W_s = h^2 * sum_a (A_bd u)_a at sigma = 0 in exact arithmetic: the discrete divergence theorem.
+ *      No atomics, no scratch; every pointer 8-byte aligned; no output may alias an input. ---- */
+/* Fx and Fy in one launch on srpde_div_apply_bd's 64 x 32 halo tiles: every node writes its low-x and its low-y face,
+ * the nodes of column n - 1 and of row n - 1 the high wall face too, so each face is written once. */
+int srpde_div_face_flux(const double* u, const double* theta, double* Fx, double* Fy, int B, int n, int face_mean,
+                        double inv_h2, int bc, const double* bd, long long bd_stride, hipStream_t stream);
+/* The adjoint of srpde_div_face_flux in u and theta, one gather launch: node a collects from its four faces
+ * gW = gFx[i][j], gE = gFx[i][j + 1], gN = gFy[i][j], gS = gFy[i + 1][j]:
+ *     gu_a     = ((cW * gW - cE * gE) + (cN * gN - cS * gS)) * inv_h
+ *     gtheta_a = (((dW * (u_a - u_W)) * gW + (dE * (u_E - u_a)) * gE)
+ *                + ((dN * (u_a - u_N)) * gN + (dS * (u_S - u_a)) * gS)) * inv_h
+ * with c the face coefficient and d its derivative in theta_a as in srpde_div_theta_grad_bd: theta_a and 1 towards a
+ * Dirichlet ghost face (u there is g), 0 towards a flux side's wall face, whose flux is data.  gu or gtheta may be NULL.
+ * The gradient in bd touches wall faces only: -+ theta_a * inv_h * gF on a Dirichlet side's low / high wall, -+ gF on
+ * a flux side's, which a caller forms from the edge rows. */
+int srpde_div_face_flux_grad(const double* u, const double* theta, const double* gFx, const double* gFy, double* gu,
+                             double* gtheta, int B, int n, int face_mean, double inv_h2, int bc, const double* bd,
+                             long long bd_stride, hipStream_t stream);
+/* W [B][4]: an edge gather and the fixed-order sum above, one workgroup per side and problem; reads the 4 n edge nodes
+ * of a problem, never its interior.  face_mean is checked and unused: a wall face has c = theta_a. */
+int srpde_div_wall_flux(const double* u, const double* theta, double* W, int B, int n, int face_mean, double inv_h2,
+                        int bc, const double* bd, long long bd_stride, hipStream_t stream);
+/* The adjoint of srpde_div_wall_flux, three [B][4][n] outputs (any may be NULL) in one edge-gather launch like
+ * srpde_div_bd_grad's.  With w = gW[b][s] * h and a the edge node of entry k of side s:
+ *     Dirichlet side:  gu_edge = -((theta_a * inv_h) * w),  gtheta_edge = ((g - u_a) * inv_h) * w,
+ *                      gbd = (theta_a * inv_h) * w
+ *     flux side:       gu_edge = 0, gtheta_edge = 0, gbd = w
+ * The caller adds the four edge rows into zero fields (a corner node receives from both of its sides) and sums gbd
+ * over the batch for shared data. */
+int srpde_div_wall_flux_grad(const double* gW, const double* u, const double* theta, double* gu_edge,
+                             double* gtheta_edge, double* gbd, int B, int n, double inv_h2, int bc, const double* bd,
+                             long long bd_stride, hipStream_t stream);
 
 /* ---- Row-sharded CG for ONE n x n problem over `world` ranks (the 640^2 ground
  *      truth of solve_multi_resolution, src/resolution_comparison.py:62-73).  Rank `rank` owns the

@@ -73,6 +73,10 @@
 //
 // Adjoint (srpde_div_theta_grad).  D_theta is symmetric, so the adjoint of the solve is the same solve, and the
 // gradient in theta of <lam, D_theta u> is the local pair gradient G(u, lam; theta) of div_theta_grad_kernel.
+//
+// Fluxes (srpde_div_face_flux, srpde_div_wall_flux and their _grad).  theta du/dx and theta du/dy on the faces, whose
+// difference quotient is A_bd u, from the same halo tiles; their integral over each wall from the edge nodes alone, in
+// one fixed order; both adjoints as gathers.  They read the state and change nothing of the solver.
 #include <cmath>
 #include <initializer_list>
 #include <type_traits>
@@ -527,6 +531,177 @@ __global__ __launch_bounds__(256) void div_bd_grad_kernel(const double* __restri
   out[((long long)b * 4 + side) * n + k] = ((bc >> side) & 1) ? inv_h * lv : (inv_h2 * theta[at]) * lv;
 }
 
+// ---- Face fluxes theta du/dx, theta du/dy and their wall totals (srpde_div_face_flux, srpde_div_wall_flux and their
+// gradients; include/srpde.h states the definitions and the rounding order).  The sides are always a mask with data,
+// and a null bd is data of zeros: g = 0 beyond Dirichlet sides, q = 0 through flux sides.
+
+// block b's boundary data, or null
+__device__ __forceinline__ const double* flux_bd(const DivSides& s, int b) {
+  return s.bd ? s.bd + (long long)b * s.bd_stride : nullptr;
+}
+
+// the halo tiles of u (g beyond Dirichlet sides, 0.0 elsewhere outside the grid) and theta (1.0 outside the grid)
+__device__ __forceinline__ void flux_stage(const double* __restrict__ u, const double* __restrict__ theta,
+                                           const double* __restrict__ bd, double* us, double* ts, long long base, int n,
+                                           int bc) {
+  div_halo_walk(base, n, [=](int i, bool in, long long at, int gy, int gx) {
+    double uv = 0.0, tv = 1.0;
+    if (in) {
+      uv = u[at];
+      tv = theta[at];
+    } else if (bd) {
+      uv = bd_halo(bd, gy, gx, n, bc);
+    }
+    us[i] = uv;
+    ts[i] = tv;
+  });
+  __syncthreads();
+}
+
+// Fx [B][n][n + 1], Fy [B][n + 1][n].  Every node writes its low-x and its low-y face; the nodes of column n - 1 and
+// of row n - 1 write the high wall face too: each face is written once, by one thread.  A face between two nodes is
+// (c * (u_hi - u_lo)) * inv_h with c = face_mean(theta_lo, theta_hi); a wall face of a Dirichlet side has c = theta_a
+// and the halo's g beyond it; a wall face of a flux side is -q (low wall) or +q (high wall), copied.
+template <bool HARM>
+__global__ __launch_bounds__(kDivThreads) void div_face_flux_kernel(const double* __restrict__ u,
+                                                                    const double* __restrict__ theta,
+                                                                    double* __restrict__ Fx, double* __restrict__ Fy,
+                                                                    double inv_h, int n, DivSides s) {
+  __shared__ double us[kDivLY * kDivLX];
+  __shared__ double ts[kDivLY * kDivLX];
+  const int b = blockIdx.z, bc = s.bc;
+  const double* __restrict__ bd = flux_bd(s, b);
+  const long long base = (long long)b * n * n;
+  flux_stage(u, theta, bd, us, ts, base, n, bc);
+
+  double* __restrict__ fx = Fx + (long long)b * n * (n + 1);
+  double* __restrict__ fy = Fy + (long long)b * (n + 1) * n;
+  div_node_walk(base, n, [=](long long, int gx, int gy, int c) {
+    const double ua = us[c], ta = ts[c];
+    const long long ax = (long long)gy * (n + 1) + gx, ay = (long long)gy * n + gx;
+    double w, v;
+    if (gx > 0) w = (face_mean<HARM>(ts[c - 1], ta) * (ua - us[c - 1])) * inv_h;
+    else if (!(bc & 4)) w = (ta * (ua - us[c - 1])) * inv_h;
+    else w = -(bd ? bd[2 * n + gy] : 0.0);
+    fx[ax] = w;
+    if (gx == n - 1) fx[ax + 1] = !(bc & 8) ? (ta * (us[c + 1] - ua)) * inv_h : (bd ? bd[3 * n + gy] : 0.0);
+    if (gy > 0) v = (face_mean<HARM>(ts[c - kDivLX], ta) * (ua - us[c - kDivLX])) * inv_h;
+    else if (!(bc & 1)) v = (ta * (ua - us[c - kDivLX])) * inv_h;
+    else v = -(bd ? bd[gx] : 0.0);
+    fy[ay] = v;
+    if (gy == n - 1) fy[ay + n] = !(bc & 2) ? (ta * (us[c + kDivLX] - ua)) * inv_h : (bd ? bd[n + gx] : 0.0);
+  });
+}
+
+// The adjoint of div_face_flux_kernel in u and theta, a gather: node a collects from its four faces, gW = gFx[i][j],
+// gE = gFx[i][j + 1], gN = gFy[i][j], gS = gFy[i + 1][j], with c and d = dc/dtheta_a of face_sum_bc / face_grad_sum_bc
+// (theta_a and 1 towards a Dirichlet ghost face, 0 towards a flux side's wall face, whose flux is data):
+//     gu_a     = ((cW * gW - cE * gE) + (cN * gN - cS * gS)) * inv_h
+//     gtheta_a = (((dW * (u_a - u_W)) * gW + (dE * (u_E - u_a)) * gE)
+//               + ((dN * (u_a - u_N)) * gN + (dS * (u_S - u_a)) * gS)) * inv_h
+// Either output may be null.  gFx and gFy are read from memory: neighbouring lanes share their faces in the cache.
+template <bool HARM>
+__global__ __launch_bounds__(kDivThreads) void div_face_flux_grad_kernel(const double* __restrict__ u,
+                                                                         const double* __restrict__ theta,
+                                                                         const double* __restrict__ gFx,
+                                                                         const double* __restrict__ gFy,
+                                                                         double* __restrict__ gu,
+                                                                         double* __restrict__ gth, double inv_h, int n,
+                                                                         DivSides s) {
+  __shared__ double us[kDivLY * kDivLX];
+  __shared__ double ts[kDivLY * kDivLX];
+  const int b = blockIdx.z, bc = s.bc;
+  const long long base = (long long)b * n * n;
+  flux_stage(u, theta, flux_bd(s, b), us, ts, base, n, bc);
+
+  const double* __restrict__ gx_ = gFx + (long long)b * n * (n + 1);
+  const double* __restrict__ gy_ = gFy + (long long)b * (n + 1) * n;
+  div_node_walk(base, n, [=](long long at, int gx, int gy, int c) {
+    const double ua = us[c], ta = ts[c];
+    const long long ax = (long long)gy * (n + 1) + gx, ay = (long long)gy * n + gx;
+    const double gW = gx_[ax], gE = gx_[ax + 1], gN = gy_[ay], gS = gy_[ay + n];
+    const bool has_w = gx > 0, has_e = gx + 1 < n, has_n = gy > 0, has_s = gy + 1 < n;
+    const bool ghost_w = !(bc & 4), ghost_e = !(bc & 8), ghost_n = !(bc & 1), ghost_s = !(bc & 2);
+    if (gu) {
+      const double cW = has_w ? face_mean<HARM>(ta, ts[c - 1]) : (ghost_w ? ta : 0.0);
+      const double cE = has_e ? face_mean<HARM>(ta, ts[c + 1]) : (ghost_e ? ta : 0.0);
+      const double cN = has_n ? face_mean<HARM>(ta, ts[c - kDivLX]) : (ghost_n ? ta : 0.0);
+      const double cS = has_s ? face_mean<HARM>(ta, ts[c + kDivLX]) : (ghost_s ? ta : 0.0);
+      gu[at] = ((cW * gW - cE * gE) + (cN * gN - cS * gS)) * inv_h;
+    }
+    if (gth) {
+      const double dW = has_w ? face_mean_da<HARM>(ta, ts[c - 1]) : (ghost_w ? 1.0 : 0.0);
+      const double dE = has_e ? face_mean_da<HARM>(ta, ts[c + 1]) : (ghost_e ? 1.0 : 0.0);
+      const double dN = has_n ? face_mean_da<HARM>(ta, ts[c - kDivLX]) : (ghost_n ? 1.0 : 0.0);
+      const double dS = has_s ? face_mean_da<HARM>(ta, ts[c + kDivLX]) : (ghost_s ? 1.0 : 0.0);
+      gth[at] = (((dW * (ua - us[c - 1])) * gW + (dE * (us[c + 1] - ua)) * gE) +
+                 ((dN * (ua - us[c - kDivLX])) * gN + (dS * (us[c + kDivLX] - ua)) * gS)) * inv_h;
+    }
+  });
+}
+
+// the edge node of entry k of a side (the mask's order: row 0, row n - 1, column 0, column n - 1)
+__device__ __forceinline__ long long flux_edge_node(int side, int k, int n) {
+  const int gy = side == 0 ? 0 : (side == 1 ? n - 1 : k);
+  const int gx = side == 2 ? 0 : (side == 3 ? n - 1 : k);
+  return (long long)gy * n + gx;
+}
+
+// W [B][4] = h * (the sum over a side's n wall faces of the outward flux): (theta_a * (g - u_a)) * inv_h on a Dirichlet
+// side -- minus the low wall's face flux, plus the high wall's, the same bits -- and q on a flux side.  grid (4 sides,
+// B): thread t adds entries t, t + 256, ... in turn, then block_sum, so the order depends on n alone.
+__global__ __launch_bounds__(kRedThreads) void div_wall_flux_kernel(const double* __restrict__ u,
+                                                                    const double* __restrict__ theta,
+                                                                    double* __restrict__ W, int n, double inv_h,
+                                                                    double h, DivSides s) {
+  __shared__ double red[4];
+  const int side = blockIdx.x, b = blockIdx.y;
+  const double* __restrict__ bd = flux_bd(s, b);
+  const bool flux = (s.bc >> side) & 1;
+  const long long base = (long long)b * n * n;
+  double acc = 0.0;
+  for (int k = threadIdx.x; k < n; k += kRedThreads) {
+    const double dv = bd ? bd[side * n + k] : 0.0;
+    double t = dv;
+    if (!flux) {
+      const long long at = base + flux_edge_node(side, k, n);
+      t = (theta[at] * (dv - u[at])) * inv_h;
+    }
+    acc = acc + t;
+  }
+  const double sum = block_sum(acc, red);
+  if (threadIdx.x == 0) W[(long long)b * 4 + side] = h * sum;
+}
+
+// The adjoint of div_wall_flux_kernel, three [B][4][n] outputs (any may be null), with w = gW[b][side] * h and a the
+// edge node of entry k:  Dirichlet side: gu_edge = -((theta_a * inv_h) * w), gtheta_edge = ((g - u_a) * inv_h) * w,
+// gbd = (theta_a * inv_h) * w;  flux side: 0.0, 0.0 and w.  grid (ceil(n / 256), 4, B), as div_bd_grad_kernel.
+__global__ __launch_bounds__(256) void div_wall_flux_grad_kernel(const double* __restrict__ gW,
+                                                                 const double* __restrict__ u,
+                                                                 const double* __restrict__ theta,
+                                                                 double* __restrict__ gu_edge,
+                                                                 double* __restrict__ gth_edge,
+                                                                 double* __restrict__ gbd, int n, double inv_h,
+                                                                 double h, DivSides s) {
+  const int k = (int)blockIdx.x * 256 + threadIdx.x, side = blockIdx.y, b = blockIdx.z;
+  if (k >= n) return;
+  const double* __restrict__ bd = flux_bd(s, b);
+  const double w = gW[(long long)b * 4 + side] * h;
+  const long long o = ((long long)b * 4 + side) * n + k;
+  double guv = 0.0, gtv = 0.0, gbv = w;
+  if (!((s.bc >> side) & 1)) {
+    const long long at = (long long)b * n * n + flux_edge_node(side, k, n);
+    const double dv = bd ? bd[side * n + k] : 0.0;
+    const double tw = theta[at] * inv_h;
+    guv = -(tw * w);
+    gtv = ((dv - u[at]) * inv_h) * w;
+    gbv = tw * w;
+  }
+  if (gu_edge) gu_edge[o] = guv;
+  if (gth_edge) gth_edge[o] = gtv;
+  if (gbd) gbd[o] = gbv;
+}
+
 __global__ __launch_bounds__(256) void div_finish_kernel(DivCG g, double* __restrict__ u, int* __restrict__ iters,
                                                          double* __restrict__ resid, long long total, int B) {
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
@@ -967,6 +1142,92 @@ int srpde_div_cg_finish(double* u, int* iters, double* resid, int B, int n, void
   const long long total = (long long)B * n * n;
   hipLaunchKernelGGL(div_finish_kernel, dim3(elementwise_grid(total)), dim3(256), 0, stream, g, u, iters, resid, total,
                      B);
+  SRPDE_LAUNCH_CHECK(name);
+  return 0;
+}
+
+// the checks the four flux entries share: the operator's shape limits, the face mean, the mask, inv_h2, and the data,
+// which may be null here (zeros)
+static int div_flux_check(const char* name, int B, int n, int face_mean, double inv_h2, int bc, const double* bd,
+                          long long bd_stride) {
+  if (int rc = div_check(name, B, n, face_mean)) return rc;
+  if (int rc = div_check_sides(name, n, mask_sides(bc))) return rc;
+  if (int rc = div_check_inv_h2(name, inv_h2)) return rc;
+  if (reinterpret_cast<uintptr_t>(bd) & 7u) SRPDE_FAIL(kErrAlign, "%s: bd not 8-byte aligned", name);
+  if (bd_stride != 0 && bd_stride != 4LL * n)
+    SRPDE_FAIL(kErrArg, "%s: bd_stride=%lld is neither 4 n = %lld ([B][4][n]) nor 0 (one [4][n] for every problem)", name,
+               bd_stride, 4LL * n);
+  return 0;
+}
+
+int srpde_div_face_flux(const double* u, const double* theta, double* Fx, double* Fy, int B, int n, int face_mean,
+                        double inv_h2, int bc, const double* bd, long long bd_stride, hipStream_t stream) {
+  const char* name = "srpde_div_face_flux";
+  SRPDE_CHECK_ARG(u && theta && Fx && Fy, "%s: null pointer", name);
+  if (int rc = div_flux_check(name, B, n, face_mean, inv_h2, bc, bd, bd_stride)) return rc;
+  if (int rc = div_check_aligned8(name, {u, theta, Fx, Fy})) return rc;
+  if (int rc = div_check_alias(name, "Fx", Fx, {u, theta, bd, Fy})) return rc;
+  if (int rc = div_check_alias(name, "Fy", Fy, {u, theta, bd})) return rc;
+  const DivSides s = data_sides(bc, bd, bd_stride, std::sqrt(inv_h2));
+  div_dispatch(s, false, face_mean != 0, false, [&](auto, auto HARM, auto, auto) {
+    hipLaunchKernelGGL((div_face_flux_kernel<HARM()>), div_grid(B, n), dim3(kDivThreads), 0, stream, u, theta, Fx, Fy,
+                       s.inv_h, n, s);
+  });
+  SRPDE_LAUNCH_CHECK(name);
+  return 0;
+}
+
+int srpde_div_face_flux_grad(const double* u, const double* theta, const double* gFx, const double* gFy, double* gu,
+                             double* gtheta, int B, int n, int face_mean, double inv_h2, int bc, const double* bd,
+                             long long bd_stride, hipStream_t stream) {
+  const char* name = "srpde_div_face_flux_grad";
+  SRPDE_CHECK_ARG(u && theta && gFx && gFy, "%s: null pointer", name);
+  if (int rc = div_flux_check(name, B, n, face_mean, inv_h2, bc, bd, bd_stride)) return rc;
+  if (int rc = div_check_aligned8(name, {u, theta, gFx, gFy, gu, gtheta})) return rc;
+  if (gu)
+    if (int rc = div_check_alias(name, "gu", gu, {u, theta, gFx, gFy, bd, gtheta})) return rc;
+  if (gtheta)
+    if (int rc = div_check_alias(name, "gtheta", gtheta, {u, theta, gFx, gFy, bd})) return rc;
+  if (!gu && !gtheta) return 0;
+  const DivSides s = data_sides(bc, bd, bd_stride, std::sqrt(inv_h2));
+  div_dispatch(s, false, face_mean != 0, false, [&](auto, auto HARM, auto, auto) {
+    hipLaunchKernelGGL((div_face_flux_grad_kernel<HARM()>), div_grid(B, n), dim3(kDivThreads), 0, stream, u, theta,
+                       gFx, gFy, gu, gtheta, s.inv_h, n, s);
+  });
+  SRPDE_LAUNCH_CHECK(name);
+  return 0;
+}
+
+int srpde_div_wall_flux(const double* u, const double* theta, double* W, int B, int n, int face_mean, double inv_h2,
+                        int bc, const double* bd, long long bd_stride, hipStream_t stream) {
+  const char* name = "srpde_div_wall_flux";
+  SRPDE_CHECK_ARG(u && theta && W, "%s: null pointer", name);
+  if (int rc = div_flux_check(name, B, n, face_mean, inv_h2, bc, bd, bd_stride)) return rc;
+  if (int rc = div_check_aligned8(name, {u, theta, W})) return rc;
+  if (int rc = div_check_alias(name, "W", W, {u, theta, bd})) return rc;
+  const DivSides s = data_sides(bc, bd, bd_stride, std::sqrt(inv_h2));
+  hipLaunchKernelGGL(div_wall_flux_kernel, dim3(4, B), dim3(kRedThreads), 0, stream, u, theta, W, n, s.inv_h,
+                     1.0 / s.inv_h, s);
+  SRPDE_LAUNCH_CHECK(name);
+  return 0;
+}
+
+int srpde_div_wall_flux_grad(const double* gW, const double* u, const double* theta, double* gu_edge,
+                             double* gtheta_edge, double* gbd, int B, int n, double inv_h2, int bc, const double* bd,
+                             long long bd_stride, hipStream_t stream) {
+  const char* name = "srpde_div_wall_flux_grad";
+  SRPDE_CHECK_ARG(gW && u && theta, "%s: null pointer", name);
+  if (int rc = div_flux_check(name, B, n, 0, inv_h2, bc, bd, bd_stride)) return rc;
+  if (int rc = div_check_aligned8(name, {gW, u, theta, gu_edge, gtheta_edge, gbd})) return rc;
+  for (double* out : {gu_edge, gtheta_edge, gbd})
+    if (out)
+      if (int rc = div_check_alias(name, "an output", out, {gW, u, theta, bd})) return rc;
+  if ((gu_edge && (gu_edge == gtheta_edge || gu_edge == gbd)) || (gbd && gbd == gtheta_edge))
+    SRPDE_FAIL(kErrArg, "%s: two outputs are the same buffer", name);
+  if (!gu_edge && !gtheta_edge && !gbd) return 0;
+  const DivSides s = data_sides(bc, bd, bd_stride, std::sqrt(inv_h2));
+  hipLaunchKernelGGL(div_wall_flux_grad_kernel, dim3(ceil_div(n, 256), 4, B), dim3(256), 0, stream, gW, u, theta,
+                     gu_edge, gtheta_edge, gbd, n, s.inv_h, 1.0 / s.inv_h, s);
   SRPDE_LAUNCH_CHECK(name);
   return 0;
 }

@@ -32,7 +32,10 @@ constant-coefficient operator with the same sides at the same condition bound; N
 calls.  ``bc_data=`` (``bc_data()``) gives the sides values: u = g on a "d" side (the ghost ring holds g instead of 0),
 a prescribed outward flux q = theta du/dn through an "n" side -- an affine extension A u = D u - sigma u + b(data,
 theta) with the same iteration, preconditioner and bound, a stop rule on |f - b| (so Laplace's equation, f = 0 with
-g != 0, iterates) and a gradient in the data; None (default) makes exactly today's calls.
+g != 0, iterates) and a gradient in the data; None (default) makes exactly today's calls.  ``face_flux`` returns the
+fluxes theta du/dx and theta du/dy of that discretisation on the faces, ``wall_flux`` their integral over each of the
+four walls (the discrete divergence theorem: the four sum to h^2 sum(apply_div)), and ``effective_coefficient`` the
+homogenised coefficient of a theta field from a unit-gradient solve and its wall fluxes; all three are differentiable.
 """
 from __future__ import annotations
 
@@ -781,6 +784,214 @@ def diffuse(u0, theta, f=None, dt: float = None, steps: int = 1, scheme: str = "
     if check:
         out += (counts,)
     return out if len(out) > 1 else out[0]
+
+
+def _flux_args(mean: int, inv_h2: float, bc, bd, B: int):
+    """The tail (face_mean, inv_h2, bc, bd, bd_stride) of the flux entries' arguments; bd None is their NULL."""
+    return (mean, inv_h2, bc or 0, 0 if bd is None else bd.data_ptr(), 0 if bd is None else _bd_stride(bd, B))
+
+
+def _face_flux(u, theta, mean: int, inv_h2: float, bc, bd):
+    """srpde_div_face_flux on prepared fields -> (Fx [B, n, n + 1], Fy [B, n + 1, n])."""
+    B, n = u.shape[0], u.shape[-1]
+    Fx = torch.empty(B, n, n + 1, dtype=torch.float64, device=u.device)
+    Fy = torch.empty(B, n + 1, n, dtype=torch.float64, device=u.device)
+    if B:
+        call("srpde_div_face_flux", u.data_ptr(), theta.data_ptr(), Fx.data_ptr(), Fy.data_ptr(), B, n,
+             *_flux_args(mean, inv_h2, bc, bd, B), stream_ptr(u.device))
+    return Fx, Fy
+
+
+def _wall_flux(u, theta, mean: int, inv_h2: float, bc, bd):
+    """srpde_div_wall_flux on prepared fields -> W [B, 4]."""
+    B, n = u.shape[0], u.shape[-1]
+    W = torch.empty(B, 4, dtype=torch.float64, device=u.device)
+    if B:
+        call("srpde_div_wall_flux", u.data_ptr(), theta.data_ptr(), W.data_ptr(), B, n,
+             *_flux_args(mean, inv_h2, bc, bd, B), stream_ptr(u.device))
+    return W
+
+
+def _side_is_flux(bc, side: int) -> bool:
+    return bool(((bc or 0) >> side) & 1)
+
+
+class _FaceFlux(torch.autograd.Function):
+    """(Fx, Fy) = srpde_div_face_flux.  grad_u and grad_theta are one srpde_div_face_flux_grad; the data enters wall
+    faces only, so its gradient is four slice expressions: -+ theta_a inv_h gF on a "d" side's low / high wall, -+ gF
+    on an "n" side's."""
+
+    @staticmethod
+    def forward(ctx, u, theta, mean, inv_h2, bc, bd):
+        u, theta = u.detach().contiguous(), theta.detach().contiguous()
+        bd = None if bd is None else bd.detach()
+        ctx.save_for_backward(u, theta, bd)
+        ctx.mean, ctx.inv_h2, ctx.bc = mean, inv_h2, bc
+        return _face_flux(u, theta, mean, inv_h2, bc, bd)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gFx, gFy):
+        u, theta, bd = ctx.saved_tensors
+        B, n = u.shape[0], u.shape[-1]
+        gFx, gFy = gFx.contiguous(), gFy.contiguous()
+        gu = torch.empty_like(u) if ctx.needs_input_grad[0] else None
+        gth = torch.empty_like(u) if ctx.needs_input_grad[1] else None
+        if B and (gu is not None or gth is not None):
+            call("srpde_div_face_flux_grad", u.data_ptr(), theta.data_ptr(), gFx.data_ptr(), gFy.data_ptr(),
+                 0 if gu is None else gu.data_ptr(), 0 if gth is None else gth.data_ptr(), B, n,
+                 *_flux_args(ctx.mean, ctx.inv_h2, ctx.bc, bd, B), stream_ptr(u.device))
+        gbd = None
+        if bd is not None and ctx.needs_input_grad[5]:
+            inv_h = float(np.sqrt(ctx.inv_h2))
+            walls = ((gFy[:, 0, :], theta[:, 0, :], -1.0), (gFy[:, n, :], theta[:, n - 1, :], 1.0),
+                     (gFx[:, :, 0], theta[:, :, 0], -1.0), (gFx[:, :, n], theta[:, :, n - 1], 1.0))
+            gbd = torch.stack([sign * gF if _side_is_flux(ctx.bc, s) else sign * ((ta * inv_h) * gF)
+                               for s, (gF, ta, sign) in enumerate(walls)], dim=1)
+            if bd.shape[0] != B:
+                gbd = gbd.sum(0, keepdim=True)
+        return gu, gth, None, None, None, gbd
+
+
+class _WallFlux(torch.autograd.Function):
+    """W = srpde_div_wall_flux.  One srpde_div_wall_flux_grad gives the three gradients on the edges, [B, 4, n] each;
+    the edge rows of u and theta are added into zero fields in the sides' order (a corner node receives from both of
+    its sides), the data's is summed over the batch when shared."""
+
+    @staticmethod
+    def forward(ctx, u, theta, mean, inv_h2, bc, bd):
+        u, theta = u.detach().contiguous(), theta.detach().contiguous()
+        bd = None if bd is None else bd.detach()
+        ctx.save_for_backward(u, theta, bd)
+        ctx.inv_h2, ctx.bc = inv_h2, bc
+        return _wall_flux(u, theta, mean, inv_h2, bc, bd)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gW):
+        u, theta, bd = ctx.saved_tensors
+        B, n = u.shape[0], u.shape[-1]
+        need_u, need_th = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        need_bd = bd is not None and ctx.needs_input_grad[5]
+        gW = gW.contiguous()
+        edges = [torch.empty(B, 4, n, dtype=torch.float64, device=u.device) if need else None
+                 for need in (need_u, need_th, need_bd)]
+        if B and any(e is not None for e in edges):
+            call("srpde_div_wall_flux_grad", gW.data_ptr(), u.data_ptr(), theta.data_ptr(),
+                 *(0 if e is None else e.data_ptr() for e in edges), B, n, ctx.inv_h2, ctx.bc or 0,
+                 0 if bd is None else bd.data_ptr(), 0 if bd is None else _bd_stride(bd, B), stream_ptr(u.device))
+
+        def field(e):
+            if e is None:
+                return None
+            g = torch.zeros_like(u)
+            g[:, 0, :] += e[:, 0]
+            g[:, n - 1, :] += e[:, 1]
+            g[:, :, 0] += e[:, 2]
+            g[:, :, n - 1] += e[:, 3]
+            return g
+
+        gbd = edges[2]
+        if gbd is not None and bd.shape[0] != B:
+            gbd = gbd.sum(0, keepdim=True)
+        return field(edges[0]), field(edges[1]), None, None, None, gbd
+
+
+def _flux_prepare(u, theta, face_mean, inv_h2, device, bc, bc_data):
+    mean = check_face_mean(face_mean)
+    bc = check_bc(bc)
+    _bd_check(bc_data, u)
+    u, theta, B, n = _div_fields(u, theta, device)
+    bd = _bd_fields(bc_data, u, u.device)
+    return u, theta, mean, float((n - 1) ** 2 if inv_h2 is None else inv_h2), bc, bd
+
+
+def face_flux(u, theta, face_mean: str = "harmonic", inv_h2: float = None, device="cuda", bc=None, bc_data=None):
+    """(Fx, Fy): the fluxes theta du/dx and theta du/dy of ``apply_div``'s discretisation on the faces, new fp64 device
+    tensors.  Fx [B, n, n + 1]: entry (i, j) is the face between nodes (i, j - 1) and (i, j), j = 0 and j = n the wall
+    faces of column 0 and column n - 1; Fy [B, n + 1, n]: entry (i, j) is the face between nodes (i - 1, j) and (i, j),
+    i = 0 and i = n the wall faces of row 0 and row n - 1.  A face between two nodes is c (u_hi - u_lo) sqrt(inv_h2)
+    with ``apply_div``'s face coefficient c; a wall face of a "d" side has c = theta_a and the ghost value g of
+    ``bc_data`` (0 without); a wall face of an "n" side carries the prescribed outward flux, -q on a low wall and +q on
+    a high one (0 without data).  So ((Fx[i, j+1] - Fx[i, j]) + (Fy[i+1, j] - Fy[i, j])) sqrt(inv_h2) is
+    ``apply_div(u, theta, ..., bc=, bc_data=)`` up to rounding.  u [n, n] or [B, n, n]; theta is broadcast; ``inv_h2``
+    defaults to (n - 1)^2; ``bc`` and ``bc_data`` are ``apply_div``'s.  One launch, stream-ordered, no host sync
+    (srpde_div_face_flux; include/srpde.h states the rounding order).
+
+    Differentiable in u, theta and ``bc_data`` when grad mode is on and one of them requires grad (one
+    srpde_div_face_flux_grad, a few slices for the data; once differentiable); otherwise exactly the call above."""
+    u, theta, mean, inv_h2, bc, bd = _flux_prepare(u, theta, face_mean, inv_h2, device, bc, bc_data)
+    if _wants_grad(u, theta, *(() if bd is None else (bd,))):
+        return _FaceFlux.apply(u, theta, mean, inv_h2, bc, bd)
+    return _face_flux(u, theta, mean, inv_h2, bc, bd)
+
+
+def wall_flux(u, theta, face_mean: str = "harmonic", inv_h2: float = None, device="cuda", bc=None, bc_data=None):
+    """W [B, 4] (fp64, on device): the integral of the outward flux theta du/dn over each wall, the sides in the
+    pattern's order (row 0, row n - 1, column 0, column n - 1): W_s = h * sum over the side's n wall faces of
+    -Fy[0, k], +Fy[n, k], -Fx[k, 0], +Fx[k, n] of ``face_flux``, h = 1 / sqrt(inv_h2).  The sum of the four is
+    h^2 * sum(apply_div(u, theta, ..., bc=, bc_data=)) up to rounding -- the discrete divergence theorem: for a solution
+    of div(theta grad u) = f the walls pass h^2 sum(f).  Reads the 4 n edge nodes of a problem only, sums in fp64 in
+    one fixed order that depends on n alone (a problem's W does not depend on the batch), one launch, no host sync
+    (srpde_div_wall_flux).  ``face_mean`` is checked and changes nothing: a wall face has c = theta_a.
+
+    Differentiable in u, theta and ``bc_data`` (one srpde_div_wall_flux_grad and slice adds; a shared [1, 4, n] or
+    [4, n] data gradient is summed over the batch; once differentiable)."""
+    u, theta, mean, inv_h2, bc, bd = _flux_prepare(u, theta, face_mean, inv_h2, device, bc, bc_data)
+    if _wants_grad(u, theta, *(() if bd is None else (bd,))):
+        return _WallFlux.apply(u, theta, mean, inv_h2, bc, bd)
+    return _wall_flux(u, theta, mean, inv_h2, bc, bd)
+
+
+EFFECTIVE_PATTERNS = ("ddnn", "nndd")   # effective_coefficient's sides for axis 0 (flow across the rows) and axis 1
+
+
+def effective_coefficient(theta, axis: int = 0, face_mean: str = "harmonic", rtol: float = DEFAULT_RTOL,
+                          maxit: int = None, pcg_iters: int = None, device="cuda"):
+    """theta_eff [B] (fp64, on device): the homogenised coefficient of each theta field [n, n] or [B, n, n] along
+    ``axis`` (0: across the rows, 1: across the columns).  Solves div(theta grad u) = 0 with u = 1 on the ghost nodes
+    beyond the first wall of the axis, u = 0 beyond the second and the other two sides insulated (``"ddnn"`` /
+    ``"nndd"`` with ``bc_data()``), and returns
+        theta_eff = 0.5 (W_first - W_second) (n + 1) / n
+    from ``wall_flux``: the flux per unit wall length over the mean gradient.  The ghost nodes are n + 1 cells apart
+    and a wall is n cells wide, so a uniform theta gives theta exactly and h cancels.  Layers parallel to the flow give
+    the mean of theta across them; layers across the flow with the harmonic mean give
+    (n + 1) / (sum_a 1 / theta_a + 0.5 (1 / theta_0 + 1 / theta_{n-1})).
+
+    Differentiable in theta by composition of the autograd ``solve_div`` with ``wall_flux``.  ``rtol`` and ``maxit``
+    are ``solve_div``'s; ``pcg_iters`` = k selects its fixed-iteration mode (exactly k iterations, no host read, so the
+    call is capturable once ``sep_plan(n, pattern)`` exists; ``pcg_iterations`` bounds k).  theta must be positive
+    (checked where the host can see it: arrays and CPU tensors)."""
+    if axis not in (0, 1):
+        raise ValueError(f"effective_coefficient: axis must be 0 or 1, got {axis!r}")
+    mean_name = FACE_MEANS[check_face_mean(face_mean)]
+    if pcg_iters is not None and int(pcg_iters) < 1:
+        raise ValueError("effective_coefficient: pcg_iters must be >= 1")
+    if not isinstance(theta, torch.Tensor):
+        theta = np.asarray(theta, dtype=np.float64)
+    if len(theta.shape) not in (2, 3) or theta.shape[-1] != theta.shape[-2] or theta.shape[-1] < 2:
+        raise ValueError(f"effective_coefficient: theta must be [n, n] or [B, n, n] with n >= 2, got "
+                         f"{tuple(theta.shape)}")
+    if isinstance(theta, np.ndarray):
+        if not (theta > 0.0).all():
+            raise ValueError("effective_coefficient: theta must be positive")
+    elif theta.device.type == "cpu" and not bool((theta.detach() > 0).all()):
+        raise ValueError("effective_coefficient: theta must be positive")
+    theta = _dev_f64(theta, device)
+    if theta.dim() == 2:
+        theta = theta.unsqueeze(0)
+    n = theta.shape[-1]
+    pattern = EFFECTIVE_PATTERNS[axis]
+    # the sides as device scalars: bc_data then copies nothing from the host, which a stream capture would refuse
+    sides = {name: torch.full((), 1.0 if s == 2 * axis else 0.0, dtype=torch.float64, device=theta.device)
+             for s, name in enumerate(SIDES)}
+    data = bc_data(n, pattern, device=theta.device, **sides)
+    fixed = pcg_iters is not None
+    u = solve_div(torch.zeros_like(theta), theta, face_mean=mean_name, rtol=rtol,
+                  maxit=int(pcg_iters) if fixed else maxit, check_every=0 if fixed else 8, check=not fixed,
+                  device=device, bc=pattern, bc_data=data)
+    W = wall_flux(u, theta, face_mean=mean_name, device=device, bc=pattern, bc_data=data)
+    return (0.5 * (n + 1) / n) * (W[:, 2 * axis] - W[:, 2 * axis + 1])
 
 
 def residual_metrics(u, f, theta, interior_only: bool = False, inv_h2: float = None, device="cuda",

@@ -88,7 +88,9 @@ typedef struct ihipStream_t* hipStream_t;
  *      srpde_div_apply_bd, srpde_div_step_rhs_bd, srpde_div_cg_init_from_bd, srpde_div_theta_grad_bd,
  *      srpde_div_bd_grad, srpde_div_relax_bd
  *      extended again, in the same way: the face fluxes of the divergence-form operator and their wall totals,
- *      srpde_div_face_flux, srpde_div_face_flux_grad, srpde_div_wall_flux, srpde_div_wall_flux_grad */
+ *      srpde_div_face_flux, srpde_div_face_flux_grad, srpde_div_wall_flux, srpde_div_wall_flux_grad
+ *      extended again, in the same way: boundary data in the physics loss and the sample stream,
+ *      srpde_physics_loss_div_fwd_bd, srpde_stream_walls */
 #define SRPDE_ABI_VERSION 23
 
 /* Kernel-family bits (per call; bit 0 of the same argument is the accumulate flag): the forward / dgrad
@@ -1028,6 +1030,32 @@ int srpde_div_bd_grad(const double* lam, const double* theta, double* out, int B
 int srpde_div_relax_bd(const double* u_in, const double* f, const double* theta, double* u_out, int E, int n,
                        int face_mean, int bc, double inv_h2, int sweeps, double omega, const double* bd,
                        long long bd_stride, void* workspace, size_t ws_bytes, hipStream_t stream);
+/* srpde_physics_loss_div_fwd_bc with boundary data on the kind-0 (whole-domain) samples (ABI 23, extended).  bd is
+ * FP32 here, [Bd][4][n] in RAW units (not normalised), 4-byte aligned, the sides and the meaning of an entry as above: g
+ * at the ghost node beyond a Dirichlet side of bc, the outward flux q through a flux side; bd_stride = 4 n floats
+ * between samples or 0 for one [4][n] shared by all (anything else is refused).  The kind-0 residual keeps the split
+ * form and gains the affine term b of srpde_div_apply_bd:
+ *     r = ((u_std a(y) + u_mean (-k_d theta) + beta) / h^2 + Q inv_h - f) / f_std
+ * beta = (tE + tW) + (tS + tN), a term theta_a * g for a ghost face on a Dirichlet side and 0.0 for every other face;
+ * Q = (qE + qW) + (qS + qN), an absent term 0.0, only at nodes with a flux-side ghost face; inv_h = sqrt(inv_h2_std),
+ * formed once on the host in fp64 and rounded to fp32.  A corner node takes data from both of its sides.  The order of
+ * the fp32 operations, each rounded once unless the compiler contracts a product into the sum that follows it:
+ *     1. lap = fma(u_std, a(y), u_mean * (-k_d theta)), as srpde_physics_loss_div_fwd_bc;
+ *     2. at an edge node: lap + beta;
+ *     3. num = lap * inv_h2_std - f, the expression of srpde_physics_loss_div_fwd_bc;
+ *     4. at a node with a flux-side ghost face: num + Q * inv_h;
+ *     5. r = num / f_std.
+ * (f is subtracted before the flux term is added, so that zero data gives the numbers of the _bc entry; a zero may
+ * differ in sign.)  b does not depend on y: the gradient is the _bc entry's Dt(m r) with this r, scaled by
+ * srpde_physics_loss_bwd.  A kind-1 sample is computed bit for bit as by srpde_physics_loss_div_fwd; its rows of bd are
+ * never read, whatever they hold.  The kernel is the _bc entry's with the kind-0 samples' data staged once into LDS
+ * (4 n floats per sample behind the three tiles, 52 KiB at n = 64): the same tiles, samples per workgroup, fp64
+ * partials in fixed order, workspace (srpde_physics_loss_div_workspace_size) and two launches; no atomics, no scratch.
+ * bd == NULL runs srpde_physics_loss_div_fwd_bc. */
+int srpde_physics_loss_div_fwd_bd(const float* y, const float* t, const float* x, const int* kind, const float* stats,
+                                  int B, int n, int face_mean, int bc, float weight, float inv_h2_std,
+                                  float inv_h2_sub, const float* bd, long long bd_stride, float* loss, float* dy_unit,
+                                  void* workspace, size_t ws_bytes, hipStream_t stream);
 
 /* ---- Face fluxes and wall totals of the divergence-form operator (ABI 23, extended).  The grid, face_mean, the side
  *      mask bc (0 .. 15) and bd / bd_stride are those of the *_bd entries, except that bd may be NULL here: g = 0 beyond
@@ -1116,6 +1144,8 @@ int srpde_poisson_rows_finish(double* u, int* iters, int n, int nloc, int maxit,
  *          field 0, element 0: k1 from words 0,1 and k2 from words 2,3
  *          field 0, element 1: start_x from words 0,1 and start_y from words 2,3
  *          field 1, element e: theta pixels 2e (words 0,1) and 2e + 1 (words 2,3) of the row-major [n][n] grid
+ *          field 2, element e = 0 .. 7: side e >> 1 of the boundary data (srpde_stream_walls), cosine modes
+ *                              m = 2 (e & 1) from words 0,1 and m + 1 from words 2,3
  *      A value in [lo, hi) is lo + (hi - lo) * u (a rounded product, then a rounded sum), a start is
  *      (int)floor(u * max_start), so 0 <= start < max_start as np.random.randint(0, max_start).  All entries are
  *      stream-ordered, keep no state and never synchronise the host. ---- */
@@ -1140,6 +1170,18 @@ int srpde_stream_draw(long long seed, long long sample0, int B, double k_lo, dou
 int srpde_stream_window(const double* u, const double* f, const double* theta, const int* starts,
                         const double* u_coarse_in, int B, int ns, int nf, float* u_fine, float* f_fine,
                         float* theta_fine, float* u_coarse, hipStream_t stream);
+/* Smooth random boundary data for samples sample0 .. sample0 + B - 1 on a side of n nodes (ABI 23, extended), the
+ * layout of the *_bd entries: bd [B][4][n] fp64, the sides in the order of the mask bc (0 .. 15).  Side s has four
+ * coefficients from field 2: c_m = (amp * (2 u - 1)) / (m + 1), m = 0 .. 3, with u the [0, 1) double above (2 u - 1 is
+ * exact; the product, then the quotient, rounded once each) and amp = g_amp on a Dirichlet side (bit clear: the entries
+ * are ghost values), q_amp on a flux side (bit set: outward fluxes).  Then, every operation rounded once (no contraction),
+ *     bd[b][s][k] = (c0 cos(0) + c1 cos(pi k / (n - 1))) + (c2 cos(2 pi k / (n - 1)) + c3 cos(3 pi k / (n - 1)))
+ * with the argument reduced in integers, cos(pi m k / (n - 1)) = cospi(((m k) mod 2 (n - 1)) / (n - 1)).  So |bd| <=
+ * (25 / 12) amp.  bd_half (nullable) [B][4][(n + 1) / 2] = bd[..., ::2], the data of the stride-2 coarse solve;
+ * bd_f32 (nullable) [B][4][n] is the fp32 cast of bd, what srpde_physics_loss_div_fwd_bd reads.  One launch, a pure
+ * function of (seed, sample, bc, g_amp, q_amp, n); n >= 2, finite amplitudes. */
+int srpde_stream_walls(long long seed, long long sample0, int B, int n, int bc, double g_amp, double q_amp, double* bd,
+                       double* bd_half, float* bd_f32, hipStream_t stream);
 
 #ifdef __cplusplus
 }

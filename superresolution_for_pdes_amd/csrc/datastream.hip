@@ -6,6 +6,7 @@
 // arguments, and
 //   srpde_stream_draw    writes k12, starts and theta for B consecutive samples        [1 launch]
 //   srpde_stream_window  crops / strides the solved fp64 fields into the fp32 training fields  [1 launch]
+//   srpde_stream_walls   writes smooth random boundary data for B consecutive samples           [1 launch]
 // with srpde_forcing_batched, the Poisson solvers and srpde_pde_dataset_assemble in between.
 //
 // Generator: Philox4x32-10 (Salmon et al., SC'11), a pure function of (seed, sample, field, element):
@@ -15,6 +16,8 @@
 // comes from an ordered pair of output words (a, b): u = (((uint64)a << 32 | b) >> 11) * 2^-53, in [0, 1).
 //   field 0 (scalars): element 0 -> k1 (words 0,1), k2 (words 2,3); element 1 -> start_x (0,1), start_y (2,3)
 //   field 1 (theta)  : element e -> pixels 2e (words 0,1) and 2e + 1 (words 2,3) of the row-major [n][n] grid
+//   field 2 (walls)  : element e = 0 .. 7 -> side e >> 1 (row 0, row n - 1, column 0, column n - 1), the coefficients of
+//                      its cosine modes m = 2 (e & 1) (words 0,1) and m + 1 (words 2,3): c = (amp * (2 u - 1)) / (m + 1)
 // A value in a range is lo + (hi - lo) * u as a rounded product, then a rounded sum (contraction off), a start is
 // (int)floor(u * max_start): both are what numpy computes from the same u, bit for bit.  u * max_start never
 // rounds up to max_start (max_start * 2^-53 is at least half an ulp below it), so the upper bound is exclusive.
@@ -25,7 +28,7 @@ namespace srpde {
 
 constexpr uint32_t kPhiloxM0 = 0xD2511F53u, kPhiloxM1 = 0xCD9E8D57u;
 constexpr uint32_t kPhiloxW0 = 0x9E3779B9u, kPhiloxW1 = 0xBB67AE85u;
-constexpr int kFieldScalars = 0, kFieldTheta = 1;
+constexpr int kFieldScalars = 0, kFieldTheta = 1, kFieldWalls = 2;
 
 struct Words4 {
   uint32_t w0, w1, w2, w3;
@@ -157,6 +160,45 @@ __global__ __launch_bounds__(256) void stream_window_kernel(const double* __rest
   }
 }
 
+// c = (amp * (2 u - 1)) / (m + 1): 2 u - 1 is exact, the product and the quotient are rounded once each
+__device__ __forceinline__ double wall_coef(double amp, double u, int m) {
+#pragma clang fp contract(off)
+  const double v = 2.0 * u - 1.0;
+  const double t = amp * v;
+  return t / (double)(m + 1);
+}
+
+// cos(pi m k / (n - 1)), the argument reduced in integers
+__device__ __forceinline__ double wall_cos(int m, int k, int n1) { return cospi((double)((m * k) % (2 * n1)) / (double)n1); }
+
+// One thread per entry (sample, side, k) of bd [B][4][n]: the side's four coefficients from its two field-2 elements,
+// then (c0 cos(0) + c1 cos(pi k / (n - 1))) + (c2 cos(2 pi k / (n - 1)) + c3 cos(3 pi k / (n - 1))).  An even k also
+// writes entry k / 2 of bd_half [B][4][(n + 1) / 2] (nullable); bd_f32 (nullable) is the fp32 cast.
+__global__ __launch_bounds__(256) void stream_walls_kernel(long long seed, long long sample0, int B, int n, int bc,
+                                                           double g_amp, double q_amp, double* __restrict__ bd,
+                                                           double* __restrict__ bd_half, float* __restrict__ bd_f32) {
+#pragma clang fp contract(off)
+  const long long total = (long long)B * 4 * n;
+  const int nh = (n + 1) / 2, n1 = n - 1;
+  for (long long q = blockIdx.x * (long long)blockDim.x + threadIdx.x; q < total;
+       q += (long long)gridDim.x * blockDim.x) {
+    const long long row = q / n, b = row >> 2;
+    const int k = (int)(q - row * n), side = (int)(row & 3);
+    const long long sample = (long long)((unsigned long long)sample0 + (unsigned long long)b);
+    const double amp = (bc >> side) & 1 ? q_amp : g_amp;
+    const Words4 lo = stream_words(seed, sample, kFieldWalls, 2 * side);
+    const Words4 hi = stream_words(seed, sample, kFieldWalls, 2 * side + 1);
+    const double c0 = wall_coef(amp, uniform53(lo.w0, lo.w1), 0), c1 = wall_coef(amp, uniform53(lo.w2, lo.w3), 1);
+    const double c2 = wall_coef(amp, uniform53(hi.w0, hi.w1), 2), c3 = wall_coef(amp, uniform53(hi.w2, hi.w3), 3);
+    const double t0 = c0 * wall_cos(0, k, n1), t1 = c1 * wall_cos(1, k, n1);
+    const double t2 = c2 * wall_cos(2, k, n1), t3 = c3 * wall_cos(3, k, n1);
+    const double v = (t0 + t1) + (t2 + t3);
+    bd[q] = v;
+    if (bd_f32) bd_f32[q] = (float)v;
+    if (bd_half && !(k & 1)) bd_half[row * nh + (k >> 1)] = v;
+  }
+}
+
 }  // namespace srpde
 
 using namespace srpde;
@@ -195,6 +237,21 @@ int srpde_stream_draw(long long seed, long long sample0, int B, double k_lo, dou
                      stream, seed, sample0, B, k_lo, k_hi, theta_mode, theta_lo, theta_hi, n, max_start, k12, starts,
                      theta, theta_half);
   SRPDE_LAUNCH_CHECK("srpde_stream_draw");
+  return 0;
+}
+
+int srpde_stream_walls(long long seed, long long sample0, int B, int n, int bc, double g_amp, double q_amp, double* bd,
+                       double* bd_half, float* bd_f32, hipStream_t stream) {
+  SRPDE_CHECK_ARG(bd, "srpde_stream_walls: null bd");
+  if (B <= 0 || n < 2 || n > 16384) SRPDE_FAIL(kErrShape, "srpde_stream_walls: bad shape B=%d n=%d (n >= 2)", B, n);
+  if (bc < 0 || bc > 15)
+    SRPDE_FAIL(kErrArg, "srpde_stream_walls: bc=%d is not a side mask (bits 0..3: row 0, row n-1, column 0, column n-1)",
+               bc);
+  if (!(g_amp == g_amp) || !(q_amp == q_amp) || g_amp - g_amp != 0.0 || q_amp - q_amp != 0.0)
+    SRPDE_FAIL(kErrArg, "srpde_stream_walls: amplitudes g_amp=%g q_amp=%g are not finite", g_amp, q_amp);
+  hipLaunchKernelGGL(stream_walls_kernel, dim3(elementwise_grid((long long)B * 4 * n)), dim3(256), 0, stream, seed,
+                     sample0, B, n, bc, g_amp, q_amp, bd, bd_half, bd_f32);
+  SRPDE_LAUNCH_CHECK("srpde_stream_walls");
   return 0;
 }
 

@@ -60,7 +60,7 @@ __device__ __forceinline__ float stencil5(const float* p, int pitch) {
 // theta * L (the header's formulas): q = m r theta, the adjoint is A on q.  LDS per sample: the y and q halo tiles and
 // the y - t plane.
 struct PointwiseLoss {
-  static constexpr bool kDiv = false;
+  static constexpr bool kDiv = false, kBd = false;
   static size_t lds_floats(int n) { return 2 * (size_t)(n + 2) * (n + 2) + (size_t)n * n; }
 };
 
@@ -81,9 +81,21 @@ struct PointwiseLoss {
 // missing ghost faces is still symmetric -- and D_theta 1 = -k_d theta, k_d the number of the node's Dirichlet ghost
 // faces.  A kind-1 sample counts interior nodes only: its m r is 0 on the ring, so no ghost coefficient reaches its
 // loss or its gradient, and it is computed with mask 0, as DivLoss<HARM, false> computes it.
-template <bool HARM, bool BC = false>
+//
+// BD (srpde_physics_loss_div_fwd_bd): boundary data on the kind-0 samples, raw units, [4][n] floats per sample in the
+// mask's side order: the ghost value g beyond a Dirichlet side, the outward flux q through a flux side.  The operator
+// gains the affine term b of srpde_div_apply_bd, which does not depend on y:
+//     r = ((((sigma_u a(y) + mu_u (-k_d theta)) + beta) ih2 - f) + Q inv_h) / sigma_f
+// beta = (tE + tW) + (tS + tN), a term theta_a * g for a Dirichlet ghost face and 0.0 otherwise; Q = (qE + qW) +
+// (qS + qN), added at nodes with a flux-side ghost face only.  The line that forms (.) ih2 - f is the one every
+// instance shares, so zero data gives the BC instance's numbers.  The gradient is Dt(m r) with this r, the adjoint pass
+// untouched.  The kind-0 samples' data is staged once into 4 n floats of LDS behind the three tiles (a crop's row is
+// neither loaded nor read); the tiles, the samples per workgroup (still chosen from the three tiles alone), the
+// partials and the workspace are the BC instance's: 52 KiB at n = 64.
+template <bool HARM, bool BC = false, bool BD = false>
 struct DivLoss {
-  static constexpr bool kDiv = true, kHarm = HARM, kBc = BC;
+  static_assert(BC || !BD, "boundary data rides on the instance with a side mask (mask 0: four Dirichlet sides)");
+  static constexpr bool kDiv = true, kHarm = HARM, kBc = BC, kBd = BD;
   static size_t lds_floats(int n) { return 3 * (size_t)(n + 2) * (n + 2); }
 };
 
@@ -117,13 +129,15 @@ __device__ __forceinline__ int loss_ghost_count(int miss, int i, int j, int n, i
     return miss;
 }
 
-// grid: ceil(B / spw) workgroups; dynamic LDS: spw * Op::lds_floats(n) floats; bc: the side mask, read by
-// DivLoss<HARM, true> alone
+// grid: ceil(B / spw) workgroups; dynamic LDS: spw * Op::lds_floats(n) floats (kBd: + spw * 4 n for the walls); bc: the
+// side mask, read by DivLoss<HARM, true> alone; bd [Bd][4][n], bd_stride (4 n or 0) and inv_h: read by
+// DivLoss<HARM, true, true> alone
 template <class Op>
 __global__ __launch_bounds__(kPhysThreads) void physics_loss_kernel(
     const float* __restrict__ y, const float* __restrict__ t, const float* __restrict__ x,
     const int* __restrict__ kind, const float* __restrict__ stats, int B, int n, int spw, float weight, float ih2_std,
-    float ih2_sub, float* __restrict__ dy, double* __restrict__ part, int bc) {
+    float ih2_sub, float* __restrict__ dy, double* __restrict__ part, int bc, const float* __restrict__ bd,
+    long long bd_stride, float inv_h) {
   extern __shared__ float lds[];
   __shared__ double sh[4];
   __shared__ long long shM;
@@ -161,6 +175,15 @@ __global__ __launch_bounds__(kPhysThreads) void physics_loss_kernel(
     }
     if (!inner) qtile[k] = 0.f;
   }
+  // stage the walls of the kind-0 samples behind the tiles, once
+  [[maybe_unused]] float* wall = tile3 + (size_t)spw * T2;   // [spw][4][n] (boundary data only)
+  if constexpr (Op::kBd) {
+    const int W = 4 * n;
+    for (int k = tid; k < ns * W; k += kPhysThreads) {
+      const int s = k / W;
+      wall[k] = kind[b0 + s] ? 0.f : bd[(long long)(b0 + s) * bd_stride + (k - s * W)];
+    }
+  }
   // M = sum of the masks of the whole batch, from the kinds (only the gradient's scale needs it here)
   if (dy != nullptr) {
     long long cnt = 0;
@@ -188,8 +211,25 @@ __global__ __launch_bounds__(kPhysThreads) void physics_loss_kernel(
       const int miss = (i == 0) + (i == n - 1) + (j == 0) + (j == n - 1);
       m = !kd || miss == 0;
       const float d1 = -(float)loss_ghost_count<Op>(miss, i, j, n, sb) * ttile[c];
-      const float lap = fmaf(sg_u, ay, mu_u * d1);
-      r = (lap * ih2 - f) / sg_f;
+      float lap = fmaf(sg_u, ay, mu_u * d1);
+      float qh = 0.f;                           // Q inv_h of a node with a flux-side ghost face
+      if constexpr (Op::kBd) {
+        if (!kd && miss) {                      // an edge node of a whole-domain sample
+          const float* w = wall + s * 4 * n;
+          const float ta = ttile[c];
+          const bool eN = i == 0, eS = i == n - 1, eW = j == 0, eE = j == n - 1;
+          const float tN = eN && !(sb & 1) ? ta * w[j] : 0.f, tS = eS && !(sb & 2) ? ta * w[n + j] : 0.f;
+          const float tW = eW && !(sb & 4) ? ta * w[2 * n + i] : 0.f, tE = eE && !(sb & 8) ? ta * w[3 * n + i] : 0.f;
+          lap += (tE + tW) + (tS + tN);
+          const float qN = eN && (sb & 1) ? w[j] : 0.f, qS = eS && (sb & 2) ? w[n + j] : 0.f;
+          const float qW = eW && (sb & 4) ? w[2 * n + i] : 0.f, qE = eE && (sb & 8) ? w[3 * n + i] : 0.f;
+          if ((eN && (sb & 1)) || (eS && (sb & 2)) || (eW && (sb & 4)) || (eE && (sb & 8)))
+            qh = ((qE + qW) + (qS + qN)) * inv_h;
+        }
+      }
+      float num = lap * ih2 - f;
+      if constexpr (Op::kBd) num += qh;
+      r = num / sg_f;
       d = ytile[c] - tv;
       qv = r;
     } else {
@@ -352,11 +392,13 @@ static size_t phys_workspace_size(int B, int n, size_t lds_floats) {
 
 // the checks and the two launches of both loss entries; name: the entry's, kernel and lds_floats: its operator's,
 // face_mean: the divergence entries' argument (checked in its place among the others), null for the pointwise entry;
-// bc: srpde_physics_loss_div_fwd_bc's side mask, 0 for the other entries
+// bc: srpde_physics_loss_div_fwd_bc's side mask, 0 for the other entries; bd, bd_stride: srpde_physics_loss_div_fwd_bd's
+// boundary data, null for the other entries
 static int phys_loss_launch(const char* name, PhysLossKernel kernel, size_t lds_floats, const int* face_mean,
                             const float* y, const float* t, const float* x, const int* kind, const float* stats, int B,
                             int n, float weight, float inv_h2_std, float inv_h2_sub, float* loss, float* dy_unit,
-                            void* workspace, size_t ws_bytes, hipStream_t stream, int bc = 0) {
+                            void* workspace, size_t ws_bytes, hipStream_t stream, int bc = 0, const float* bd = nullptr,
+                            long long bd_stride = 0) {
   SRPDE_CHECK_ARG(y && t && x && kind && stats && loss && workspace, "%s: null pointer", name);
   if (B <= 0 || n < kPhysMinN || n > kPhysMaxN)
     SRPDE_FAIL(kErrShape, "%s: bad shape B=%d n=%d (B >= 1, %d <= n <= %d)", name, B, n, kPhysMinN, kPhysMaxN);
@@ -367,10 +409,15 @@ static int phys_loss_launch(const char* name, PhysLossKernel kernel, size_t lds_
                name, bc);
   if (reinterpret_cast<uintptr_t>(workspace) & 7u) SRPDE_FAIL(kErrAlign, "%s: workspace not 8-byte aligned", name);
   if (ws_bytes < phys_workspace_size(B, n, lds_floats)) SRPDE_FAIL(kErrWorkspace, "%s: workspace too small", name);
+  if (bd && bd_stride != 0 && bd_stride != 4LL * n)
+    SRPDE_FAIL(kErrArg, "%s: bd_stride=%lld (4 n = %d floats between samples, or 0 for one shared [4][n])", name,
+               bd_stride, 4 * n);
   const int spw = phys_spw(lds_floats), nb = phys_blocks(B, lds_floats);
+  const size_t lds = (size_t)spw * (lds_floats + (bd ? 4 * (size_t)n : 0)) * sizeof(float);
+  const float inv_h = (float)sqrt((double)inv_h2_std);
   double* part = static_cast<double*>(workspace);
-  hipLaunchKernelGGL(kernel, dim3(nb), dim3(kPhysThreads), (size_t)spw * lds_floats * sizeof(float), stream, y, t, x,
-                     kind, stats, B, n, spw, weight, inv_h2_std, inv_h2_sub, dy_unit, part, bc);
+  hipLaunchKernelGGL(kernel, dim3(nb), dim3(kPhysThreads), lds, stream, y, t, x, kind, stats, B, n, spw, weight,
+                     inv_h2_std, inv_h2_sub, dy_unit, part, bc, bd, bd_stride, inv_h);
   SRPDE_LAUNCH_CHECK(name);
   hipLaunchKernelGGL(physics_loss_final_kernel, dim3(1), dim3(kPhysThreads), 0, stream, part, nb,
                      (long long)B * n * n, weight, loss);
@@ -416,6 +463,21 @@ int srpde_physics_loss_div_fwd_bc(const float* y, const float* t, const float* x
   return phys_loss_launch("srpde_physics_loss_div_fwd_bc", kernel, DivLoss<false>::lds_floats(n), &face_mean, y, t, x,
                           kind, stats, B, n, weight, inv_h2_std, inv_h2_sub, loss, dy_unit, workspace, ws_bytes, stream,
                           bc);
+}
+
+// bd == NULL is srpde_physics_loss_div_fwd_bc, kernel for kernel
+int srpde_physics_loss_div_fwd_bd(const float* y, const float* t, const float* x, const int* kind, const float* stats,
+                                  int B, int n, int face_mean, int bc, float weight, float inv_h2_std,
+                                  float inv_h2_sub, const float* bd, long long bd_stride, float* loss, float* dy_unit,
+                                  void* workspace, size_t ws_bytes, hipStream_t stream) {
+  if (!bd)
+    return srpde_physics_loss_div_fwd_bc(y, t, x, kind, stats, B, n, face_mean, bc, weight, inv_h2_std, inv_h2_sub,
+                                         loss, dy_unit, workspace, ws_bytes, stream);
+  return phys_loss_launch("srpde_physics_loss_div_fwd_bd",
+                          face_mean == 1 ? physics_loss_kernel<DivLoss<true, true, true>>
+                                         : physics_loss_kernel<DivLoss<false, true, true>>,
+                          DivLoss<false>::lds_floats(n), &face_mean, y, t, x, kind, stats, B, n, weight, inv_h2_std,
+                          inv_h2_sub, loss, dy_unit, workspace, ws_bytes, stream, bc, bd, bd_stride);
 }
 
 int srpde_physics_loss_bwd(const float* dy_unit, long long count, const float* gout, float* dy, hipStream_t stream) {

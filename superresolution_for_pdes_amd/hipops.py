@@ -1003,6 +1003,27 @@ def stream_window(u, f, theta, starts, nf, u_coarse_in=None, out=None):
     return tuple(out)
 
 
+def stream_walls(seed, sample0, B, n, bc=0, amps=(0.0, 0.0), half=False, f32=False, device="cuda"):
+    """srpde_stream_walls: smooth random boundary data of samples sample0 .. sample0 + B - 1 on sides of n nodes ->
+    (bd [B, 4, n] fp64, bd[..., ::2] or None, the fp32 cast of bd or None).  ``bc``: a side mask 0 .. 15 (0: four
+    Dirichlet sides); ``amps`` = (g_amp, q_amp), the amplitude of the values on "d" sides and of the fluxes on "n"
+    sides.  ``f32`` may be the tensor to write the cast into (contiguous [B, 4, n] fp32, e.g. row slices of a batch's
+    buffer).  One launch; seed, indices and sizes are kernel arguments."""
+    mask = _side_mask("stream_walls", bc, 0)
+    bd = torch.empty(B, 4, n, dtype=torch.float64, device=device)
+    bd_half = torch.empty(B, 4, (n + 1) // 2, dtype=torch.float64, device=device) if half else None
+    if isinstance(f32, torch.Tensor):
+        bd_f32 = f32
+        _fields("stream_walls", F32, bd_f32)
+        if tuple(bd_f32.shape) != (B, 4, n):
+            raise ValueError(f"stream_walls: the fp32 output is [{B}, 4, {n}], got {tuple(bd_f32.shape)}")
+    else:
+        bd_f32 = torch.empty(B, 4, n, dtype=F32, device=device) if f32 else None
+    call("srpde_stream_walls", int(seed), int(sample0), int(B), int(n), mask, float(amps[0]), float(amps[1]),
+         bd.data_ptr(), _p(bd_half), _p(bd_f32), stream_ptr())
+    return bd, bd_half, bd_f32
+
+
 def upsample_bwd(dout, dx, n, h, w, ho, wo, accumulate, gate=None, bn=None):
     """``gate = (dsa, wg)``: the upsampled tensor's gradient is dout + dsa (x) wg (the attention
     gating gradient left unapplied by att_bwd(dg=None)).  ``bn = (y, mean, invstd, gamma, beta)``: the BN +
@@ -1225,14 +1246,19 @@ def _side_mask(name, bc, face_mean):
     return bc
 
 
-def physics_loss_fwd(y, t, x, kind, stats, weight, inv_h2, want_grad=True, face_mean=None, bc=None):
+def physics_loss_fwd(y, t, x, kind, stats, weight, inv_h2, want_grad=True, face_mean=None, bc=None, bd=None):
     """srpde_physics_loss_fwd: y, t [B, 1, n, n] and x [B, 3, n, n] fp32, kind [B] int32, stats 6 floats, all on one
     device -> (loss [3] = (mse + weight * pde, mse, pde), the gradient for grad_out = 1 or None).  ``inv_h2``: the
     1 / h^2 of (kind 0, kind 1).  Without ``want_grad`` no gradient is computed or written.  ``face_mean`` None: the
     pointwise residual theta * L u - f; 0 (arithmetic) or 1 (harmonic): the divergence-form residual
     div(theta grad u) - f through srpde_physics_loss_div_fwd.  ``bc``: a side mask (poisson.check_bc) for the
-    kind-0 samples of the divergence form, through srpde_physics_loss_div_fwd_bc; None / 0: the entry without one."""
+    kind-0 samples of the divergence form, through srpde_physics_loss_div_fwd_bc; None / 0: the entry without one.
+    ``bd``: boundary data of the kind-0 samples in raw units, [B, 4, n] or [1, 4, n] fp32 on the fields' device
+    (ghost values beyond the "d" sides, all four without a mask; outward fluxes through the "n" sides), through
+    srpde_physics_loss_div_fwd_bd; None: the calls above."""
     mask = _side_mask("physics_loss_fwd", bc, face_mean)
+    if bd is not None and face_mean is None:
+        raise ValueError("physics_loss_fwd: boundary data belongs to the divergence form (face_mean 0 / 1)")
     _fields("physics_loss_fwd", F32, y, t, x, stats)
     _fields("physics_loss_fwd", torch.int32, kind)
     if y.dim() != 4 or y.shape[1] != 1 or y.shape[2] != y.shape[3] or t.shape != y.shape:
@@ -1247,6 +1273,16 @@ def physics_loss_fwd(y, t, x, kind, stats, weight, inv_h2, want_grad=True, face_
     ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=y.device)
     loss = torch.empty(3, dtype=F32, device=y.device)
     unit = torch.empty_like(y) if want_grad else None
+    if bd is not None:
+        _fields("physics_loss_fwd", F32, bd)
+        if bd.dim() != 3 or bd.shape[0] not in (1, B) or tuple(bd.shape[1:]) != (4, n):
+            raise ValueError(f"physics_loss_fwd: boundary data must be [{B}, 4, {n}] or [1, 4, {n}], got "
+                             f"{tuple(bd.shape)}")
+        call("srpde_physics_loss_div_fwd_bd", y.data_ptr(), t.data_ptr(), x.data_ptr(), kind.data_ptr(),
+             stats.data_ptr(), B, n, int(face_mean), mask, float(weight), float(inv_h2[0]), float(inv_h2[1]),
+             bd.data_ptr(), 4 * n if bd.shape[0] == B and B > 1 else 0, loss.data_ptr(), _p(unit), ws.data_ptr(),
+             nbytes, stream_ptr())
+        return loss, unit
     if mask:
         call("srpde_physics_loss_div_fwd_bc", y.data_ptr(), t.data_ptr(), x.data_ptr(), kind.data_ptr(),
              stats.data_ptr(), B, n, int(face_mean), mask, float(weight), float(inv_h2[0]), float(inv_h2[1]),

@@ -73,14 +73,18 @@ class DeviceBatchLoader:
     batch is world x batch_size, as under torch DDP).  ``shard_batches`` (evaluation): the
     single-process batches themselves are dealt round-robin to the ranks, unpadded, so the
     all-reduced (sum of batch losses, batch count) gives exactly the single-process mean.
-    ``with_kind``: batches are (inputs, targets, kind), the dataset's ``batch(idx, with_kind=True)``."""
+    ``with_kind``: batches are (inputs, targets, kind), the dataset's ``batch(idx, with_kind=True)``.
+    ``with_bd``: one more element, the samples' boundary data (online.FrozenSet.batch(idx, with_kind, with_bd=True))."""
 
     def __init__(self, dataset, batch_size, shuffle=False, seed=0, rank=0, world=1, drop_last=False,
-                 shard_batches=False, with_kind=False):
+                 shard_batches=False, with_kind=False, with_bd=False):
         self.ds, self.bs, self.shuffle = dataset, batch_size, shuffle
         self.seed, self.rank, self.world, self.drop_last = seed, rank, world, drop_last
         self.shard_batches = shard_batches
+        if with_bd and not with_kind:       # train_model reads a batch by position: (inputs, targets, kind, bd)
+            raise ValueError("DeviceBatchLoader: with_bd goes with with_kind=True (batches are read by position)")
         self.with_kind = with_kind
+        self.with_bd = with_bd
         self.epoch = 0
 
     def _indices(self):
@@ -108,6 +112,9 @@ class DeviceBatchLoader:
         idx = self._indices().to(self.ds.inputs.device)
         self.epoch += 1
         for b in self._batches(idx):
+            if self.with_bd:
+                yield self.ds.batch(b, with_kind=self.with_kind, with_bd=True)
+                continue
             yield self.ds.batch(b, with_kind=True) if self.with_kind else self.ds.batch(b)
 
 
@@ -133,16 +140,24 @@ def _global_means(totals, count, device):
 
 
 def _unpack(batch, device):
-    """(inputs, targets, kind or None) of a 2- or 3-tuple batch, on ``device``."""
+    """(inputs, targets, kind or None, bd or None) of a 2-, 3- or 4-tuple batch (inputs, targets[, kind[, bd]]), on
+    ``device``.  Read by position: boundary data is always the fourth element, which is why the loaders refuse
+    ``with_bd`` without ``with_kind``."""
     inputs, targets = batch[0].to(device), batch[1].to(device)
-    return inputs, targets, (batch[2].to(device) if len(batch) > 2 else None)
+    return (inputs, targets, (batch[2].to(device) if len(batch) > 2 else None),
+            (batch[3].to(device) if len(batch) > 3 else None))
 
 
-def _criterion_call(criterion, outputs, targets, inputs, kind):
+def _criterion_call(criterion, outputs, targets, inputs, kind, bd=None):
     if getattr(criterion, "needs_inputs", False):
         if kind is None:
             raise ValueError("this criterion needs (inputs, targets, kind) batches: build the loaders with "
                              "with_kind=True")
+        if getattr(criterion, "needs_bd", False):
+            if bd is None:
+                raise ValueError("this criterion needs (inputs, targets, kind, bd) batches: build the loaders with "
+                                 "with_kind=True, with_bd=True")
+            return criterion(outputs, targets, inputs, kind, bd)
         return criterion(outputs, targets, inputs, kind)
     return criterion(outputs, targets)
 
@@ -167,10 +182,10 @@ def train_model(model: nn.Module, train_loader, val_loader, criterion: nn.Module
         tacc = torch.zeros(2, dtype=torch.float64, device=device) if terms else None
         nb = 0
         for batch in train_loader:
-            inputs, targets, kind = _unpack(batch, device)
+            inputs, targets, kind, bd = _unpack(batch, device)
             optimizer.zero_grad()
             outputs = model(inputs)
-            loss = _criterion_call(criterion, outputs, targets, inputs, kind)
+            loss = _criterion_call(criterion, outputs, targets, inputs, kind, bd)
             loss.backward()
             if fused:
                 optimizer.step(max_grad_norm=grad_clip)
@@ -196,8 +211,8 @@ def train_model(model: nn.Module, train_loader, val_loader, criterion: nn.Module
         vb = 0
         with torch.no_grad():
             for batch in val_loader:
-                inputs, targets, kind = _unpack(batch, device)
-                vacc += _criterion_call(criterion, model(inputs), targets, inputs, kind).detach()
+                inputs, targets, kind, bd = _unpack(batch, device)
+                vacc += _criterion_call(criterion, model(inputs), targets, inputs, kind, bd).detach()
                 if terms:
                     vtacc += criterion.last_terms[1:]
                 vb += 1
@@ -357,11 +372,22 @@ def arg_parser():
                     help='with --online and --operator divergence: the sides of the samples\' problem, four of "d" '
                          '(zero ghost ring) / "n" (zero flux) for (row 0, row n-1, column 0, column n-1), e.g. ddnn; '
                          "it reaches the stream, the validation set and the --pde-div-weight term")
+    ap.add_argument("--bc-data", type=float, nargs=2, metavar=("G_AMP", "Q_AMP"), default=None,
+                    help="with --online and --operator divergence: smooth random boundary data on every sample's walls "
+                         "(online.SampleStream(boundary=)): values of amplitude G_AMP beyond the \"d\" sides of --bc "
+                         "(all four without it), outward fluxes of amplitude Q_AMP through its \"n\" sides; it reaches "
+                         "the stream, the validation set and the --pde-div-weight term")
     return ap
 
 
 def check_operator_args(args):
-    """The refusals of --operator / --face-mean / --pde-div-weight / --bc, before any device work."""
+    """The refusals of --operator / --face-mean / --pde-div-weight / --bc / --bc-data, before any device work."""
+    if getattr(args, "bc_data", None) is not None:
+        if args.online is None or args.operator != "divergence":
+            raise SystemExit("--bc-data needs --online and --operator divergence (the pointwise solvers and the fixed "
+                             "dataset generators have the zero ghost ring)")
+        if not all(np.isfinite(v) for v in args.bc_data):
+            raise SystemExit("--bc-data: two finite amplitudes G_AMP Q_AMP")
     if args.bc is not None:
         from .poisson import check_bc
         try:
@@ -404,22 +430,28 @@ def online_loaders(args, config, rank, world, device):
     if args.online < 1:
         raise SystemExit("--online: at least one step per epoch")
     stream = SampleStream(42, config["batch_size"], theta_range=args.online_theta, solver=args.solver, rank=rank,
-                          world=world, device=device, form=args.operator, face_mean=args.face_mean, bc=args.bc)
+                          world=world, device=device, form=args.operator, face_mean=args.face_mean, bc=args.bc,
+                          boundary=None if args.bc_data is None else tuple(args.bc_data))
     with_kind = args.pde_weight > 0 or args.pde_div_weight > 0
+    if args.bc_data is not None and args.pde_div_weight > 0:   # the term needs the walls the samples were solved with
+        return (OnlineBatchLoader(stream, args.online, with_kind=True, with_bd=True),
+                stream.validation_loader(ONLINE_VAL_SAMPLES, config["batch_size"], with_kind=True, with_bd=True))
     return (OnlineBatchLoader(stream, args.online, with_kind=with_kind),
             stream.validation_loader(ONLINE_VAL_SAMPLES, config["batch_size"], with_kind=with_kind))
 
 
-def physics_criterion(weight, stats, save_dir=None, form="pointwise", face_mean="harmonic", bc=None):
+def physics_criterion(weight, stats, save_dir=None, form="pointwise", face_mean="harmonic", bc=None, bc_data=None):
     """The criterion of --pde-weight (``form="pointwise"``) or --pde-div-weight (``"divergence"``, with the run's
-    ``face_mean`` and ``bc``); with ``save_dir`` its settings go to physics_loss.json beside config.json."""
+    ``face_mean`` and ``bc``; ``bc_data``: the run's --bc-data amplitudes, and the criterion then takes each batch's
+    boundary data); with ``save_dir`` its settings go to physics_loss.json beside config.json."""
     from .functional import PhysicsMSELoss
-    criterion = PhysicsMSELoss(weight, stats, form=form, face_mean=face_mean, bc=bc)
+    criterion = PhysicsMSELoss(weight, stats, form=form, face_mean=face_mean, bc=bc, bc_data=bc_data is not None)
     if save_dir is not None:
         with open(Path(save_dir) / "physics_loss.json", "w") as f:
             json.dump({"weight": criterion.weight, "inv_h2": list(criterion.inv_h2),
                        "stats": [float(v) for v in stats.detach().cpu()], "form": criterion.form,
-                       "face_mean": criterion.face_mean if form == "divergence" else None, "bc": criterion.bc},
+                       "face_mean": criterion.face_mean if form == "divergence" else None, "bc": criterion.bc,
+                       "bc_data": None if bc_data is None else [float(v) for v in bc_data]},
                       f, indent=4)
     return criterion
 
@@ -458,6 +490,8 @@ def main(argv=None):
             recorded.update(operator=args.operator, face_mean=args.face_mean)
         if args.bc is not None:
             recorded.update(bc=args.bc)
+        if args.bc_data is not None:
+            recorded.update(bc_data=list(args.bc_data))
         with open(save_dir / "config.json", "w") as f:
             json.dump(recorded, f, indent=4)
     writer = ScalarWriter(str(save_dir / "tensorboard")) if rank == 0 else None
@@ -487,7 +521,7 @@ def main(argv=None):
         net = DataParallel(model)
     if args.pde_div_weight > 0:
         criterion = physics_criterion(args.pde_div_weight, stats, save_dir if rank == 0 else None, "divergence",
-                                      args.face_mean, args.bc)
+                                      args.face_mean, args.bc, args.bc_data)
     elif with_kind:
         criterion = physics_criterion(args.pde_weight, stats, save_dir if rank == 0 else None)
     else:

@@ -1053,6 +1053,7 @@ template <int BM, int BN, int WM, int WN>
 static int launch_fwd(const ConvParams& p, hipStream_t st) {
   const int nbm = ceil_div(p.P, BM), nbn = ceil_div(p.Cout, BN);
   const size_t lds = (size_t)2 * (BM + BN) * LDK * sizeof(float);
+  note_kernel("conv_igemm_fwd_kernel<%d, %d, %d, %d>", BM, BN, WM, WN);
   hipLaunchKernelGGL((conv_igemm_fwd_kernel<BM, BN, WM, WN>), dim3(nbm * nbn), dim3(256), lds, st, p);
   SRPDE_LAUNCH_CHECK("srpde_conv_fwd");
   return 0;
@@ -1074,6 +1075,7 @@ static int launch_fwd_v2(ConvParams p, hipStream_t st, void* ws, size_t ws_bytes
   // into F K-pieces so that round runs on ~F x more CUs for 1/F of the time
   plan_tail(p, T, slots, BM, BN, ws, ws_bytes);
   const int grid = T - p.ntail + p.ntail * p.tsplit;
+  note_kernel("conv_fwd_v2_kernel<%d, %d, %d, %d, %d>", BM, BN, WM, WN, HP);
   hipLaunchKernelGGL((conv_fwd_v2_kernel<BM, BN, WM, WN, HP>), dim3(grid), dim3(256), lds, st, p);
   SRPDE_LAUNCH_CHECK("srpde_conv_fwd(v2)");
   if (p.ntail > 0) {
@@ -1097,6 +1099,7 @@ template <int BM, int BN, int WM, int WN>
 static int launch_wgrad(const WgradParams& p, hipStream_t st, const WgradBn* bn = nullptr) {
   const int nb = ceil_div(p.Cout, BM) * ceil_div(p.K, BN) * p.splits;
   const size_t lds = (size_t)2 * BKP * ((BM + 4) + (BN + 4)) * sizeof(float);
+  note_kernel("conv_wgrad_kernel<%d, %d, %d, %d, %s>", BM, BN, WM, WN, bn != nullptr ? "true" : "false");
   if (bn != nullptr)
     hipLaunchKernelGGL((conv_wgrad_kernel<BM, BN, WM, WN, true>), dim3(nb), dim3(256), lds, st, p, *bn);
   else
@@ -1109,6 +1112,7 @@ template <int BM, int BN, int WM, int WN>
 static int launch_wgrad_v2(const WgradParams& p, hipStream_t st) {
   const int nb = ceil_div(p.Cout, BM) * ceil_div(p.K, BN) * p.splits;
   const size_t lds = (size_t)2 * (BM / 32 + BN / 32) * GSTR;
+  note_kernel("conv_wgrad_v2_kernel<%d, %d, %d, %d, 2>", BM, BN, WM, WN);
   hipLaunchKernelGGL((conv_wgrad_v2_kernel<BM, BN, WM, WN, 2>), dim3(nb), dim3(256), lds, st, p);
   SRPDE_LAUNCH_CHECK("srpde_conv_wgrad(v2)");
   return 0;

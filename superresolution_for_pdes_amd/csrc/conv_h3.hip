@@ -1122,7 +1122,8 @@ __global__ __launch_bounds__(WM * WN * 64, 1) void conv_wgrad_h3p_kernel(WgradPa
   constexpr int DA = (NA + NW - 1) / NW, DB = (NB + NW - 1) / NW, DPW = DA + DB;   // DMA ops per wave per stage
   static_assert(IMG_A % 1024 == 0 && IMG_B % 1024 == 0, "images must be whole KiB");
   static_assert(PS % 16 == 0 && (NST - 2) * DPW <= 63, "stage geometry");
-  // (the per-issue coordinate advance wraps at most one image row and one image: PS < H * W)
+  // (the per-issue coordinate advance wraps at most one image row and one image: psy is taken modulo H, so a
+  // stage may span several small images)
   extern __shared__ __attribute__((aligned(16))) float smem[];
   char* lds = reinterpret_cast<char*>(smem);
   char* const sink = lds + NST * STAGE;
@@ -1148,7 +1149,9 @@ __global__ __launch_bounds__(WM * WN * 64, 1) void conv_wgrad_h3p_kernel(WgradPa
   // (past NA / NB: a spare zero-fill into the sink).  LDS destinations are wave-uniform; per lane: a
   // running byte offset (advanced by one stage of pixels per issue) and, for B, the image
   // coordinates of its pixel.
-  const int psy = PS / p.W, psx = PS - psy * p.W;       // one stage of pixels in image rows / columns
+  // one stage of pixels in image rows / columns; the row count modulo H: only the row within its image matters,
+  // and y + psy + 1 < 2 H keeps the advance to one wrap when PS > H * W (4 x 4 images: 8 rows per stage)
+  const int psy = (PS / p.W) % p.H, psx = PS % p.W;
   const unsigned astep = (unsigned)(PS * p.lddy * 2), bstep = (unsigned)(PS * p.Cin * 2);
   int a_row[DA];
   unsigned a_off[DA];
@@ -1549,7 +1552,7 @@ __global__ __launch_bounds__(XF ? 704 : 576, 1) void conv_wgrad_h3h_kernel(Wgrad
   const int colb = 2 * ((lane & 16) + 4 * (lane & 3));
   const int h = lane >> 5, qq = (lane & 15) >> 2;
   const int HW = p.H * p.W;
-  const int psy = PS / p.W, psx = PS - psy * p.W;
+  const int psy = (PS / p.W) % p.H, psx = PS % p.W;   // rows modulo H: one wrap per advance, as in h3p
   int px[NBP][2], py[NBP][2];
 #pragma unroll
   for (int kk = 0; kk < NBP; ++kk)

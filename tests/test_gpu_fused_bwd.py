@@ -238,9 +238,8 @@ def test_enc1_conv1_weight_gradient_with_fused_bn_backward(n):
     x = torch.randn(n, 3, 40, 40, device=DEV, generator=g)
     x[:, 1] = 1.0
     t = torch.randn(n, 1, 40, 40, device=DEV, generator=g)
-    # srpde_conv_wgrad_bnb's fp32 kernel does not report its name to srpde_last_kernel (its LAUNCH_TAP record
-    # carries the launch before it), so the launch is identified by its entry: one call on the fused run, whose
-    # record the tap holds, and none on the unfused run
+    # the launch is identified by its entry (srpde_conv_wgrad_bnb's fp32 kernel shares its name with the plain
+    # fp32 weight gradient's): one call on the fused run, whose record the tap holds, and none on the unfused run
     _, grads_f = _step(model, x, t, True, "_FUSE_WGRAD_BN", ())
     assert LAST_ENTRIES.count("srpde_conv_wgrad_bnb") == 1 and len(LAST_LAUNCHES) == len(LAST_ENTRIES)
     _, grads_u = _step(model, x, t, False, "_FUSE_WGRAD_BN", ())
